@@ -113,6 +113,40 @@ def load_state(m, sc):
         m.density.copy_(sc['density']); m.k0.copy_(sc['k0']); m.mask_cache.mask.copy_(sc['mask'])
 
 
+DUMP_SAMPLE_VOXELS = 1 << 19      # grid voxels written by --dump-outputs (a fixed, seeded sample when the grid is larger)
+DUMP_MAX_BYTES = 64 << 20
+
+
+def step_outputs(m, loss):
+    """What the caller of the timed step holds after it, as float32 / float64 host arrays: the step's loss and the
+    parameters it updated -- the MLP's in full, the two grids at a fixed, seeded sample of voxels (the same sample in
+    every run of the same --world).  Grids are written voxel-major: density [n], k0 [n, C] at the linear voxel
+    indices in `grid_sample_index` (x * Y * Z + y * Z + z)."""
+    out = {} if loss is None else {'loss': loss.detach().float().cpu().numpy()}       # (None: --steps 0)
+    for name, p in m.named_parameters():
+        if name not in ('density', 'k0'):
+            out[name] = p.detach().float().cpu().numpy()
+    n_vox = m.density.numel()
+    C = m.k0.shape[1]
+    if n_vox <= DUMP_SAMPLE_VOXELS:
+        idx = np.arange(n_vox, dtype=np.int64)
+    else:
+        idx = np.sort(np.random.default_rng(0).choice(n_vox, DUMP_SAMPLE_VOXELS, replace=False))
+    at = torch.from_numpy(idx).to(m.density.device)
+    out['grid_sample_index'] = idx.astype(np.float64)
+    out['density'] = m.density.detach().reshape(-1)[at].cpu().numpy()
+    out['k0'] = m.k0.detach().permute(0, 2, 3, 4, 1).reshape(-1, C)[at].cpu().numpy()
+    assert sum(a.nbytes for a in out.values()) <= DUMP_MAX_BYTES
+    return out
+
+
+def dump_outputs(arrays, dirname):
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(dirname, name + '.npy'), a)
+
+
 def ray_pool(workload, half, n_rays, device, base_seed, n_batches):
     from directvoxgo_amd import scenes
     pool = []
@@ -143,7 +177,9 @@ def count_samples(m, batch, rk):
     return M0, M1, M3
 
 
-def timed_region(step_fn, pool, steps, warmup, world, profile=True):
+def timed_region(step_fn, pool, steps, warmup, world, profile=True, after_timed=None):
+    """`after_timed(loss)`: called with the loss of the last timed step once the clock has stopped, before the
+    profiling pass moves the model on."""
     from directvoxgo_amd import _lib as L
     for i in range(warmup):
         step_fn(*pool[i % len(pool)], global_step=5000 + i)
@@ -151,12 +187,17 @@ def timed_region(step_fn, pool, steps, warmup, world, profile=True):
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
+    loss = None
     for i in range(steps):
-        step_fn(*pool[(warmup + i) % len(pool)], global_step=5000 + warmup + i)
+        del loss                      # (only the last step's loss is kept: nothing of an earlier step stays alive)
+        loss = step_fn(*pool[(warmup + i) % len(pool)], global_step=5000 + warmup + i)
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
     dt = time.perf_counter() - t0
+    if after_timed is not None:
+        after_timed(loss)
+    del loss
     prof = {}
     if profile:
         # per-kernel durations: the same K steps again with every kernel on ONE stream.  In the timed region above
@@ -408,6 +449,9 @@ def main():
     ap.add_argument('--single-stream', action='store_true',
                     help='timed region without the second-stream overlap of the colour-head weight gradients: every launch '
                          'of a kernel then runs alone, so rocprofv3 --stats averages agree with the HIP-event averages')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help="after the timed steps, write what the primary workload's last timed step computed to DIR/<name>.npy "
+                         '(float32 / float64, at most 64 MB: the loss, the MLP parameters, a fixed sample of the grids)')
     ap.add_argument('--backend', default='nccl', help="torch.distributed backend for N > 1 ('nccl' = RCCL on ROCm)")
     ap.add_argument('--dry-run', action='store_true',
                     help='launcher / rendezvous check without touching a GPU: every rank joins the process group (use --backend '
@@ -446,7 +490,7 @@ def main():
 
     from directvoxgo_amd.train import FINE_TRAIN, TrainStep
 
-    def run(workload, steps, warmup, profile, graph=False):
+    def run(workload, steps, warmup, profile, graph=False, dump=None):
         sc, m = build(workload, args.world, args.rays, device, seed=777)
         load_state(m, sc)
         rk = dict(near=sc['near'], far=sc['far'], bg=1, stepsize=sc['stepsize'])
@@ -454,13 +498,15 @@ def main():
         M0, M_d, M_k = count_samples(m, pool[0], rk)
         step = TrainStep(m, dict(FINE_TRAIN), rk, overlap_wgrad=not args.single_stream)
         captured = bool(graph) and step.capture(*pool[0], global_step=5000)
-        dt, prof = timed_region(step, pool, steps, warmup, world, profile and not captured)
+        write = (lambda loss: dump_outputs(step_outputs(m, loss), dump)) if dump else None
+        dt, prof = timed_region(step, pool, steps, warmup, world, profile and not captured, after_timed=write)
         run.captured = captured
         run.adam_in_brick = bool(getattr(step, 'last_fused_adam', False))     # did the scatter launch carry the Adam update?
         end_counts = count_samples(m, pool[0], rk)          # the optimizer moves the scene: how far did the workload drift?
         return sc, m, rk, dt, prof, (M0, M_d, M_k), end_counts
 
-    sc, m, rk, dt, prof, (M0, M_d, M_k), end_counts = run(args.workload, args.steps, args.warmup, True, graph=args.graph)
+    sc, m, rk, dt, prof, (M0, M_d, M_k), end_counts = run(args.workload, args.steps, args.warmup, True, graph=args.graph,
+                                                          dump=args.dump_outputs if rank == 0 else None)
     primary_captured = bool(getattr(run, 'captured', False))
     adam_in_brick = bool(getattr(run, 'adam_in_brick', False))
     n_total = args.rays * world
