@@ -2,15 +2,20 @@
 
   get_rays / ndc_rays / get_rays_of_a_view   /root/reference/lib/ray_utils.py:9-85 (same argument
                                              meaning; built on the device the pose lives on)
-  render_viewpoints                          /root/reference/run.py:57-143 without the PNG / metric
-                                             side: chunks of rays under no_grad, `render_depth` on
-                                             (the reference uses 8192; rays are independent, so the
-                                             image is identical for any chunk and 65536 halves the
-                                             per-view time on MI355X: 43 -> 21 ms at 800x800);
-                                             the last chunk may be empty (run.py:91) and is accepted.
+  render_viewpoints                          /root/reference/run.py:57-143: chunks of rays under
+                                             no_grad, `render_depth` on (the reference uses 8192; rays
+                                             are independent, so the image is identical for any chunk
+                                             and 65536 halves the per-view time on MI355X: 43 -> 21 ms
+                                             at 800x800); the last chunk may be empty (run.py:91) and
+                                             is accepted.  With gt_imgs, PSNR / SSIM per view on the
+                                             device (metrics.py), printed as run.py:126-128 does;
+                                             savedir writes '{:03d}.png' with Pillow (run.py:132-137).
+  evaluate_viewpoints                        the same, returning the per-view metrics as well.
 Multi-GPU inference (section 8e): images are embarrassingly parallel -- rank r renders poses
 r, r+P, ... and the results are gathered; no all-reduce.
 """
+import os
+
 import numpy as np
 import torch
 import torch.distributed as dist
@@ -85,12 +90,56 @@ def get_rays_of_a_view(H, W, K, c2w, ndc, inverse_y, flip_x, flip_y, mode='cente
     return rays_o, rays_d, viewdirs
 
 
+def apply_render_factor(HW, Ks, render_factor):
+    """run.py:65-69: sizes and intrinsics of copies divided by render_factor (floor division of the float intrinsics too,
+    as the reference does)."""
+    if render_factor == 0:
+        return HW, Ks
+    HW = np.copy(HW)
+    Ks = np.copy(Ks)
+    HW //= render_factor
+    Ks[:, :2, :3] //= render_factor
+    return HW, Ks
+
+
 @torch.no_grad()
 def render_viewpoints(model, render_poses, HW, Ks, ndc, render_kwargs, flip_x=False, flip_y=False, chunk=65536,
-                      distributed=False, ray_kernel=True):
+                      distributed=False, ray_kernel=True, gt_imgs=None, savedir=None, render_factor=0, eval_ssim=False,
+                      eval_lpips_alex=False, eval_lpips_vgg=False):
     """-> (rgbs [n,H,W,3], depths [n,H,W,1]) as numpy arrays (every rank gets all images when
-    ``distributed``)."""
+    ``distributed``).  The metric arguments are those of run.py:57-143; see evaluate_viewpoints."""
+    res = evaluate_viewpoints(model, render_poses, HW, Ks, ndc, render_kwargs, flip_x=flip_x, flip_y=flip_y, chunk=chunk,
+                              distributed=distributed, ray_kernel=ray_kernel, gt_imgs=gt_imgs, savedir=savedir,
+                              render_factor=render_factor, eval_ssim=eval_ssim, eval_lpips_alex=eval_lpips_alex,
+                              eval_lpips_vgg=eval_lpips_vgg)
+    return res['rgbs'], res['depths']
+
+
+@torch.no_grad()
+def evaluate_viewpoints(model, render_poses, HW, Ks, ndc, render_kwargs, flip_x=False, flip_y=False, chunk=65536,
+                        distributed=False, ray_kernel=True, gt_imgs=None, savedir=None, render_factor=0, eval_ssim=False,
+                        eval_lpips_alex=False, eval_lpips_vgg=False):
+    """Render the views and, given ground truth, score them (run.py:57-143).
+
+    -> {'rgbs': [n,H,W,3], 'depths': [n,H,W,1] (numpy), 'psnr': [n] floats or None, 'ssim': [n] floats or None}.
+    Metrics are computed only when ``gt_imgs is not None and render_factor == 0`` (run.py:116), SSIM only with
+    ``eval_ssim``; each view is scored on the device from the rendered tensor (gt_imgs[i] may be a numpy array, uploaded,
+    or a device tensor).  ``distributed``: every rank scores the views it rendered and the metrics travel with the
+    gathered images, so every rank returns the same lists in view order; only rank 0 prints and writes ``savedir``.
+    LPIPS is not provided: it needs pretrained AlexNet / VGG weights this project cannot fetch."""
+    if eval_lpips_alex or eval_lpips_vgg:
+        raise NotImplementedError('LPIPS is not provided: it needs pretrained AlexNet / VGG weights (the lpips package), '
+                                  'which this project does not ship or fetch')
     assert len(render_poses) == len(HW) and len(HW) == len(Ks)
+    if savedir is not None:
+        try:
+            import PIL.Image  # noqa: F401
+        except ImportError as e:
+            raise ImportError('render_viewpoints(savedir=...) writes PNGs with Pillow, which is not installed') from e
+    HW, Ks = apply_render_factor(HW, Ks, render_factor)
+    score = gt_imgs is not None and render_factor == 0
+    if score:
+        from .metrics import image_metrics
     world = dist.get_world_size() if distributed else 1
     rank = dist.get_rank() if distributed else 0
     dev = next(model.parameters()).device
@@ -123,15 +172,46 @@ def render_viewpoints(model, render_poses, HW, Ks, ndc, render_kwargs, flip_x=Fa
                 ro, rd, vd = rays_o[p0:p0 + n], rays_d[p0:p0 + n], viewdirs[p0:p0 + n]
             res = model(ro, rd, vd, global_step=c, **kwargs)
             out_rgb.append(res['rgb_marched']); out_depth.append(res['depth'])
-        mine[i] = (torch.cat(out_rgb).reshape(H, W, 3), torch.cat(out_depth).reshape(H, W, 1))
+        rgb = torch.cat(out_rgb).reshape(H, W, 3)
+        scores = None
+        if score:            # run.py:116-121, on the device before the view leaves it
+            gt = gt_imgs[i]
+            gt = torch.as_tensor(np.asarray(gt, np.float32) if not isinstance(gt, torch.Tensor) else gt).to(dev, torch.float32)
+            s, sse, _ = image_metrics(rgb, gt, max_val=1, filter_size=11 if eval_ssim else 1)
+            scores = (sse, s if eval_ssim else None, n_pix * 3)
+        mine[i] = (rgb, torch.cat(out_depth).reshape(H, W, 1), scores)
+
+    def host(v):
+        rgb, depth, scores = v
+        if scores is not None:
+            sse, s, n_val = scores
+            mse = float(sse[0]) / n_val
+            scores = (float('inf') if mse == 0 else float(-10. * np.log10(mse)), float(s[0]) if s is not None else None)
+        return rgb.cpu(), depth.cpu(), scores
+
+    mine = {k: host(v) for k, v in mine.items()}
     if distributed and world > 1:
         gathered = [None] * world
-        dist.all_gather_object(gathered, {k: (a.cpu(), b.cpu()) for k, (a, b) in mine.items()})
+        dist.all_gather_object(gathered, mine)
         mine = {k: v for part in gathered for k, v in part.items()}
     idx = sorted(mine)
-    rgbs = np.stack([mine[i][0].cpu().numpy() for i in idx]) if idx else np.zeros((0,))
-    depths = np.stack([mine[i][1].cpu().numpy() for i in idx]) if idx else np.zeros((0,))
-    return rgbs, depths
+    rgbs = np.stack([mine[i][0].numpy() for i in idx]) if idx else np.zeros((0,))
+    depths = np.stack([mine[i][1].numpy() for i in idx]) if idx else np.zeros((0,))
+    psnrs = [mine[i][2][0] for i in idx] if score else None
+    ssims = [mine[i][2][1] for i in idx] if score and eval_ssim else None
+    if rank == 0:
+        if psnrs:
+            print('Testing psnr', np.mean(psnrs), '(avg)')
+            if eval_ssim:
+                print('Testing ssim', np.mean(ssims), '(avg)')
+        if savedir is not None:
+            from PIL import Image
+            from .metrics import to8b
+            print(f'Writing images to {savedir}')
+            os.makedirs(savedir, exist_ok=True)
+            for k in range(len(rgbs)):
+                Image.fromarray(to8b(rgbs[k])).save(os.path.join(savedir, '{:03d}.png'.format(k)))
+    return {'rgbs': rgbs, 'depths': depths, 'psnr': psnrs, 'ssim': ssims}
 
 
 # ----------------------------------------------------------------------------------------------

@@ -503,6 +503,28 @@ int dvgo_adam_upd_multi(float* const* params, const float* const* grads, float* 
                         float beta1, float beta2, float eps,
                         const float* step_size_dev /* NULL, or the step size on the device */, void* stream);
 
+/* ---------------------------------------------------------------------------------
+ * Image metrics of rendered views.  lib/utils.py:88-134 (rgb_ssim) / run.py:116-121
+ * img0, img1 [n,H,W,3] fp32, contiguous: n same-sized pairs (one call per view size).
+ *   ssim_sum[n] (double): the sum of the SSIM map of each pair over its (H-fs+1) x (W-fs+1) x 3 entries;
+ *                         SSIM = ssim_sum / that count.
+ *   sse[n]      (double): sum over all H*W*3 values of (img0 - img1)^2 (the difference squared in fp32, as run.py:117
+ *                         forms it); PSNR = -10 log10(sse / (H*W*3)).
+ *   ssim_map: NULL, or [n, H-fs+1, W-fs+1, 3] fp32.
+ *   taps: HOST array of the filter_size Gaussian taps, computed in float64 as lib/utils.py:101-105 does;
+ *   c1 = (k1 max_val)^2, c2 = (k2 max_val)^2.
+ *   workspace: DEVICE scratch of at least dvgo_image_metrics_workspace_bytes(n, H, W, filter_size) bytes.
+ * The x^2, y^2, xy products are rounded to fp32 as the reference forms them; blurs, map and sums are fp64.  Results are
+ * bitwise reproducible and the same for an image whether it is scored alone or at any place in a batch.
+ * DVGO_EINVAL: H or W < filter_size (the reference's empty mean, nan), non-positive sizes, null pointers, a short
+ * workspace.  DVGO_ERANGE: filter_size > 16, H*W*3 >= 2^31, or more than 2^31 tiles.  n == 0 is a no-op.
+ * dvgo_image_metrics_workspace_bytes returns the byte count, or the error code for the sizes.
+ * --------------------------------------------------------------------------------- */
+int64_t dvgo_image_metrics_workspace_bytes(int64_t n, int H, int W, int filter_size);
+int dvgo_image_metrics(const float* img0, const float* img1, int64_t n, int H, int W, const double* taps, int filter_size,
+                       double c1, double c2, double* ssim_sum, double* sse, float* ssim_map,
+                       void* workspace, int64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
