@@ -525,6 +525,38 @@ int dvgo_image_metrics(const float* img0, const float* img1, int64_t n, int H, i
                        double c1, double c2, double* ssim_sum, double* sse, float* ssim_map,
                        void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------
+ * Geometry export: a triangle mesh of the density level set.  Extends the reference's debug exports (run.py:514-553:
+ * --export_coarse_only / --export_fine_only dense volumes; tools/vis_volume.py: thresholded voxel cloud) to a closed
+ * surface, by marching tetrahedra on the Freudenthal split of an extraction lattice (csrc/mesh.hip).
+ *
+ * The lattice has Rx x Ry x Rz points, padded by one empty point per side: P = R + 2 per axis, at most 2^28 points
+ * (padding included; DVGO_ERANGE above).  A point is inside when its field value > iso.
+ * dvgo_mesh_field: field [Px, Py, Pz] fp32 of the padded lattice.  Unpadded point (i, j, k) holds
+ *     copy != 0: density[i, j, k] (requires R == (X, Y, Z))
+ *     copy == 0: the trilinear sample of density [X, Y, Z] (X, Y, Z >= 2) at grid-index coordinates g = g0 + i * gs
+ *                per axis (the corner weights of grid_sample_fwd, zero outside the grid)
+ *   unless mask (NULL: all occupied) [MX, MY, MZ] says 0 at the world point box_min + i * spacing, looked up as
+ *   maskcache_lookup does (round(fma(xyz, mask_scale, mask_shift)), out of range = 0).  Padding and masked-out
+ *   points hold iso - 1.  g0, gs, box_min, spacing, mask_scale, mask_shift: HOST arrays of 3.
+ * dvgo_mesh_count: edge_mask [Px*Py*Pz] (uint8: bit d set when the edge to the neighbour in direction
+ *   x, y, z, xy, xz, yz, xyz crosses the surface), partials [2 * ceil(Px*Py*Pz / 256)], bases [2 * (that + 1)]
+ *   (uint32); bases ends with the totals (V, F): the caller reads those 8 bytes to size the outputs.
+ * dvgo_mesh_emit: verts [V, 3] and normals [V, 3] fp32 (world coordinates box_min + i * spacing per axis; unit
+ *   normals pointing to lower field values), faces [F, 3] int32 wound outward, in the order DESIGN.md 6c defines.
+ *   n_verts / n_faces: the V and F of dvgo_mesh_count (writes past them are dropped).
+ * No atomics: the outputs are a function of the field alone.
+ * --------------------------------------------------------------------------------- */
+int dvgo_mesh_field(const float* density, int X, int Y, int Z, const uint8_t* mask, int MX, int MY, int MZ,
+                    const float* mask_scale, const float* mask_shift, int Rx, int Ry, int Rz, const float* g0,
+                    const float* gs, const float* box_min, const float* spacing, int copy, float iso, float* field,
+                    void* stream);
+int dvgo_mesh_count(const float* field, int Px, int Py, int Pz, float iso, uint8_t* edge_mask, uint32_t* partials,
+                    uint32_t* bases, void* stream);
+int dvgo_mesh_emit(const float* field, const uint8_t* edge_mask, const uint32_t* bases, int Px, int Py, int Pz,
+                   float iso, const float* box_min, const float* spacing, int64_t n_verts, int64_t n_faces,
+                   float* verts, float* normals, int32_t* faces, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
