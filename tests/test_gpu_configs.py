@@ -7,9 +7,10 @@
             grid from num_voxels = 256^3 / mpi_depth = 128, 9 features, 64-wide head, 4096 rays x 255 NDC samples,
             dense total variation on both grids in the step.
 
-No oracle run is affordable at these sizes, so each test holds the fused path against the op-by-op HIP path
-(`fused=False`: every kernel of it is pinned bit-exact / to tolerance against the oracle in test_gpu_ops.py) on the
-same inputs, plus size-independent properties (sum w + T = 1, depth range, the inverse_y / pose-flip identity).
+Here each test holds the fused path against the op-by-op HIP path (`fused=False`) on the same inputs, plus
+size-independent properties (sum w + T = 1, depth range, the inverse_y / pose-flip identity).  The same shapes are held
+against the CPU oracle itself -- features bit for bit, values, grid and colour-head gradients, dense TV, rendered pixels --
+in tests/test_gpu_fullsize_oracle.py (tests/render_oracle.py runs them in seconds).
 """
 import numpy as np
 import pytest
