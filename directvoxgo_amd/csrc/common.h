@@ -35,6 +35,13 @@ static inline bool dvgo_fits(int64_t work) { return work >= 0 && work < ((int64_
 //   ATen grid_sampler_3d corner weights as differences to the opposite corner.
 // Kept operation for operation identical to oracle/dvgo_oracle.c (ora_corners) so that
 // floor() decisions and weights are bit-identical; compiled with -ffp-contract=off.
+// ReLU of the colour head, as torch computes it: IEEE 754-2019 maximum (one v_maximum3_f32 on gfx950), so NaN
+// propagates and max(-0, +0) = +0.  fmaxf is maxNum: fmaxf(NaN, 0) = 0 hid a non-finite input behind a finite colour.
+__device__ __forceinline__ float dvgo_relu(float z) { return __builtin_elementwise_maximum(z, 0.0f); }
+// Its mask bit: torch's threshold_backward passes the gradient unless the output is <= 0, i.e. for z > 0 and for NaN.
+// After dvgo_relu, +0 is the only zero, so that is "bit pattern non-zero".
+__device__ __forceinline__ unsigned int dvgo_relu_bit(float r) { return __float_as_uint(r) != 0u ? 1u : 0u; }
+
 // --------------------------------------------------------------------------------------
 struct TriSetup {
   int i0, j0, k0;        // floor corner (may be -1 or size-1 at the faces)

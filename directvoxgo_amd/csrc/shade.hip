@@ -139,7 +139,7 @@ __device__ __forceinline__ void shade_tile_forward(const ShadeLds<WIDTH, S1>& L,
 #pragma unroll
     for (int s = 0; s < S1; ++s) acc1[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(L.w1a[t][s][lane], x[s], acc1[t], 0, 0, 0);
 #pragma unroll
-    for (int r = 0; r < 16; ++r) acc1[t][r] = fmaxf(acc1[t][r], 0.0f);
+    for (int r = 0; r < 16; ++r) acc1[t][r] = dvgo_relu(acc1[t][r]);
     __builtin_amdgcn_sched_barrier(0);       // one tile's A-operand reads at a time (three waves per SIMD: 170 registers)
   }
   float p[3] = {0.0f, 0.0f, 0.0f};
@@ -157,11 +157,11 @@ __device__ __forceinline__ void shade_tile_forward(const ShadeLds<WIDTH, S1>& L,
       __builtin_amdgcn_sched_barrier(0);
     }
 #pragma unroll
-    for (int r = 0; r < 16; ++r) acc2[r] = fmaxf(acc2[r], 0.0f);
+    for (int r = 0; r < 16; ++r) acc2[r] = dvgo_relu(acc2[r]);
     if (H2tile != nullptr) {
       unsigned int bits = 0u;
 #pragma unroll
-      for (int r = 0; r < 16; ++r) bits |= (acc2[r] > 0.0f ? 1u : 0u) << r;
+      for (int r = 0; r < 16; ++r) bits |= dvgo_relu_bit(acc2[r]) << r;
       mask2 |= (unsigned long long)bits << (16 * t2);
       shade_store_tile(stage, acc2, H2tile + 32 * t2, WIDTH, lane, rows_valid);
     }
@@ -239,7 +239,7 @@ shade_fwd_kernel(const float* __restrict__ feat, int C, int c_view0, int n_view,
 #pragma unroll
         for (int t = 0; t < T; ++t) {
 #pragma unroll
-          for (int r = 0; r < 16; ++r) mask1 |= (unsigned long long)(acc1[t][r] > 0.0f ? 1u : 0u) << (16 * t + r);
+          for (int r = 0; r < 16; ++r) mask1 |= (unsigned long long)dvgo_relu_bit(acc1[t][r]) << (16 * t + r);
         }
         masks[(row * 2 + 0) * 2 + h] = mask1;
         masks[(row * 2 + 1) * 2 + h] = mask2;
@@ -451,7 +451,7 @@ shade_wgrad_kernel(const float* __restrict__ G1, const float* __restrict__ gz, c
   const int xrow = tid / TPR, xcol = tid - xrow * TPR;
   {
     const int64_t row = (int64_t)blockIdx.x * 32 + xrow;
-    ray_nx = ray_id[row < M ? row : M - 1];
+    ray_nx = M > 0 ? ray_id[row < M ? row : M - 1] : 0;    // (M = 0 in capacity mode: no tile runs, read nothing)
   }
 #define SHADE_WGRAD_DMA(TILE, BUF)                                                                              \
   {                                                                                                             \

@@ -199,11 +199,11 @@ shade_fwd_x3_kernel(const float* __restrict__ feat, int C, int c_view0, int n_vi
       for (int s = 0; s < KS1; ++s)
         x3_mfma6(acc, L.w1s[t][s][0][lane], L.w1s[t][s][1][lane], L.w1s[t][s][2][lane], x3[s][0], x3[s][1], x3[s][2]);
 #pragma unroll
-      for (int r = 0; r < 16; ++r) acc[r] = fmaxf(acc[r], 0.0f);
+      for (int r = 0; r < 16; ++r) acc[r] = dvgo_relu(acc[r]);
       if (train) {                             // post-ReLU activations (weight gradients) + their sign bits
-        unsigned int bits = 0u;                // (after the ReLU: positive <=> bit pattern non-zero; -0 cannot occur)
+        unsigned int bits = 0u;                // (after dvgo_relu: +0 is the only zero, so bits != 0 <=> z > 0 or NaN)
 #pragma unroll
-        for (int r = 0; r < 16; ++r) bits |= min(__float_as_uint(acc[r]), 1u) << r;
+        for (int r = 0; r < 16; ++r) bits |= dvgo_relu_bit(acc[r]) << r;
         mask1 |= (unsigned long long)bits << (16 * t);
         if (!(experiment & 512)) x3_store_tile(stage, acc, H1 + tile * 32 * WIDTH + 32 * t, WIDTH, lane, rows_valid);
       }
@@ -239,11 +239,11 @@ shade_fwd_x3_kernel(const float* __restrict__ feat, int C, int c_view0, int n_vi
         __builtin_amdgcn_sched_barrier(0);
       }
 #pragma unroll
-      for (int r = 0; r < 16; ++r) acc2[r] = fmaxf(acc2[r], 0.0f);
+      for (int r = 0; r < 16; ++r) acc2[r] = dvgo_relu(acc2[r]);
       if (train) {
         unsigned int bits = 0u;
 #pragma unroll
-        for (int r = 0; r < 16; ++r) bits |= min(__float_as_uint(acc2[r]), 1u) << r;
+        for (int r = 0; r < 16; ++r) bits |= dvgo_relu_bit(acc2[r]) << r;
         mask2 |= (unsigned long long)bits << (16 * t2);
         if (!(experiment & 512)) x3_store_tile(stage, acc2, H2 + tile * 32 * WIDTH + 32 * t2, WIDTH, lane, rows_valid);
       }
