@@ -10,9 +10,14 @@ Two execution paths produce the same dict:
   fused=True   (default) csrc/march.hip: 4 kernels, 1 host sync per forward;
   fused=False  the reference's own op-by-op orchestration on the drop-in ops of
                render_utils.py / ops.py (what a maintainer gets by only swapping the bindings).
-The fork-specific LIIF / positional-encoding experiments of the reference model
-(implicit_voxel_feat, posbase_pe, rgbnet_full_implicit; lib/dvgo.py:40-41,100-122,329-410) are
-outside the north-star path and raise NotImplementedError.
+`posbase_pe=P > 0` (lib/dvgo.py:97-107,528-534, the switch of configs/nerf and configs/nsvf) colours a sample from
+the positional encoding of its position instead of the feature grid: the colour head's input is
+cat([pts, sin(pts (x) posfreq), cos(pts (x) posfreq), viewdirs_emb]), there is no diffuse term, and k0 -- still allocated,
+still in the state_dict -- is neither read nor trained (its .grad stays None, as in the reference).  The fused path runs
+the head as csrc/shade_pe.hip (width 128, d_in <= 96) on positions the march writes in place of features.
+The fork's other experiments raise NotImplementedError: rgbnet_full_implicit (the reference's own forward reads a k0 it
+never assigns, lib/dvgo.py:498-522) and the LIIF option implicit_voxel_feat (lib/dvgo.py:329-410; only the tri-plane
+configs set it, and its branches read an undefined k0 or unpack four values into three names, lib/dvgo.py:336).
 """
 import numpy as np
 import torch
@@ -24,7 +29,7 @@ from . import render_utils as render_utils_hip
 from ._lib import _flt, _i64, _int, f3, ptr, stream_of
 from .fused import MarchConfig, composite, composite_depth, fused_hit, fused_march
 from .ops import Alphas2Weights, MaskCache, Raw2Alpha, grid_sample, segment_coo, total_variation_add_grad
-from .shade import shade, viewdir_embed
+from .shade import posenc_supported, shade, shade_posenc, viewdir_embed
 
 
 def _as_f32(x):
@@ -94,8 +99,12 @@ class DirectVoxGO(nn.Module):
                  posbase_pe=0, implicit_voxel_feat=False,
                  channels_last=True, fused=True, verbose=False, **kwargs):
         super().__init__()
-        if posbase_pe > 0 or implicit_voxel_feat or rgbnet_full_implicit:
-            raise NotImplementedError('fork-specific LIIF / posbase_pe / full-implicit variants are out of scope')
+        if rgbnet_full_implicit:
+            raise NotImplementedError('rgbnet_full_implicit: the reference forward reads k0 before assigning it '
+                                      '(lib/dvgo.py:498-522), so there is no behaviour to reproduce')
+        if implicit_voxel_feat:
+            raise NotImplementedError('implicit_voxel_feat (LIIF) is a tri-plane-only experiment whose dvgo branches are '
+                                      'broken in the reference (undefined k0; lib/dvgo.py:336 unpacks 4 values into 3)')
         self.verbose = verbose
         self.fused = bool(fused)
         self.fused_shade = True          # fp32-MFMA colour head (csrc/shade.hip) when the rgbnet has the default shape
@@ -122,6 +131,11 @@ class DirectVoxGO(nn.Module):
             'rgbnet_full_implicit': rgbnet_full_implicit,
             'rgbnet_depth': rgbnet_depth, 'rgbnet_width': rgbnet_width, 'viewbase_pe': viewbase_pe,
         }
+        # the reference's posbase_pe (lib/dvgo.py:97-107); in get_kwargs() only when set, so that the kwargs and checkpoints of
+        # the other models stay as they were
+        self.posbase_pe = int(posbase_pe) if rgbnet_dim > 0 else 0
+        if posbase_pe > 0:
+            self.rgbnet_kwargs['posbase_pe'] = posbase_pe
         if rgbnet_dim <= 0:
             self.k0_dim = 3                 # colour grid, coarse stage (lib/dvgo.py:83-87)
             self.rgbnet = None
@@ -129,7 +143,11 @@ class DirectVoxGO(nn.Module):
             self.k0_dim = rgbnet_dim        # feature grid + shallow MLP (lib/dvgo.py:88-131)
             self.rgbnet_direct = rgbnet_direct
             self.register_buffer('viewfreq', torch.FloatTensor([(2 ** i) for i in range(viewbase_pe)]))
-            dim0 = (3 + 3 * viewbase_pe * 2) + (self.k0_dim if rgbnet_direct else self.k0_dim - 3)
+            if self.posbase_pe > 0:
+                self.register_buffer('posfreq', torch.FloatTensor([(2 ** i) for i in range(self.posbase_pe)]))
+                dim0 = (3 + 3 * viewbase_pe * 2) + (3 + 3 * self.posbase_pe * 2)
+            else:
+                dim0 = (3 + 3 * viewbase_pe * 2) + (self.k0_dim if rgbnet_direct else self.k0_dim - 3)
             self.rgbnet = make_rgbnet(dim0, rgbnet_width, rgbnet_depth)
         self.k0 = nn.Parameter(self._alloc_k0(ws))
 
@@ -319,6 +337,25 @@ class DirectVoxGO(nn.Module):
             return torch.sigmoid(rgb_logit)
         return torch.sigmoid(rgb_logit + k0_diffuse)
 
+    @property
+    def uses_posenc(self):
+        """True when the colour head reads the positional encoding of the sample positions and not k0 (posbase_pe > 0,
+        fine stage): k0 then gets no gradient and is never updated."""
+        return self.rgbnet is not None and self.posbase_pe > 0
+
+    def _shade_posenc(self, pts, viewdirs, ray_id):
+        """lib/dvgo.py:524-534 (posbase_pe > 0): rgb from the positions' encoding and the view embedding, no diffuse term."""
+        if self.fused and self.fused_shade and viewdirs.is_cuda and viewdirs.dim() == 2:
+            rgb = shade_posenc(self.rgbnet, pts, viewdir_embed(viewdirs, self.viewfreq), ray_id, self.posfreq)
+            if rgb is not None:
+                return rgb
+        viewdirs_emb = (viewdirs.unsqueeze(-1) * self.viewfreq).flatten(-2)
+        viewdirs_emb = torch.cat([viewdirs, viewdirs_emb.sin(), viewdirs_emb.cos()], -1)
+        viewdirs_emb = viewdirs_emb.flatten(0, -2)[ray_id]
+        pos_emb = (pts.unsqueeze(-1) * self.posfreq).flatten(-2)
+        pos_emb = torch.cat([pts, pos_emb.sin(), pos_emb.cos()], -1)
+        return torch.sigmoid(mlp_forward(self.rgbnet, torch.cat([pos_emb, viewdirs_emb], -1)))
+
     # ------------------------------------------------------------------ forward (H2)
     def _march_cfg(self, near, far, stepsize):
         key = (float(near), float(far), float(stepsize))
@@ -346,7 +383,8 @@ class DirectVoxGO(nn.Module):
     def can_keep_count_on_device(self):
         """True when `forward(..., _capacity=True)` is available: the fused march with the fused colour head."""
         from .shade import head_layers
-        return bool(self.fused and self.fused_shade and self.rgbnet is not None and head_layers(self.rgbnet) is not None)
+        return bool(self.fused and self.fused_shade and self.rgbnet is not None and not self.uses_posenc
+                    and head_layers(self.rgbnet) is not None)
 
     def _forward_fused(self, rays_o, rays_d, viewdirs, near, far, stepsize, bg, render_depth=False, _capacity=False,
                        **_unused):
@@ -356,10 +394,17 @@ class DirectVoxGO(nn.Module):
         N = len(rays_o)
         cfg = self._march_cfg(near, far, stepsize)
         _capacity = bool(_capacity) and self.can_keep_count_on_device() and viewdirs.is_cuda and viewdirs.dim() == 2
-        weights, alpha, alphainv_last, k0, ray_id, step_id, off3 = fused_march(
-            self.density, self.k0, rays_o, rays_d, cfg, capacity=_capacity)
-        m_dev = off3[N:] if _capacity else None
-        rgb = self._shade(k0, viewdirs, ray_id, m_dev)
+        if self.uses_posenc:
+            # the march writes the kept samples' positions where it would write their k0 features; k0 is not read
+            weights, alpha, alphainv_last, pts, ray_id, step_id, off3 = fused_march(
+                self.density, self.k0.detach()[:, :0], rays_o, rays_d, cfg, positions=True)
+            m_dev = None
+            rgb = self._shade_posenc(pts, viewdirs, ray_id)
+        else:
+            weights, alpha, alphainv_last, k0, ray_id, step_id, off3 = fused_march(
+                self.density, self.k0, rays_o, rays_d, cfg, capacity=_capacity)
+            m_dev = off3[N:] if _capacity else None
+            rgb = self._shade(k0, viewdirs, ray_id, m_dev)
         rgb_marched = composite(weights, rgb, alphainv_last, ray_id, off3, bg, m_dev)
         ret = {'alphainv_last': alphainv_last, 'weights': weights, 'rgb_marched': rgb_marched,
                'raw_alpha': alpha, 'raw_rgb': rgb, 'ray_id': ray_id}
@@ -389,8 +434,11 @@ class DirectVoxGO(nn.Module):
             mask = weights > self.fast_color_thres
             weights, alpha = weights[mask], alpha[mask]
             ray_pts, ray_id, step_id = ray_pts[mask], ray_id[mask], step_id[mask]
-        k0 = self.grid_sampler(ray_pts, self.k0)
-        rgb = self._shade(k0, viewdirs, ray_id)
+        if self.uses_posenc:       # (the reference also interpolates k0 here and never uses the result: skipped)
+            rgb = self._shade_posenc(ray_pts, viewdirs, ray_id)
+        else:
+            k0 = self.grid_sampler(ray_pts, self.k0)
+            rgb = self._shade(k0, viewdirs, ray_id)
         rgb_marched = segment_coo(src=(weights.unsqueeze(-1) * rgb), index=ray_id,
                                   out=torch.zeros([N, 3], device=rays_o.device), reduce='sum')
         rgb_marched = rgb_marched + alphainv_last.unsqueeze(-1) * render_kwargs['bg']

@@ -197,12 +197,18 @@ def extract_mesh(model, alpha_thres=0.5, resolution=None, bbox=None, color=True)
 
 @torch.no_grad()
 def vertex_colors(model, verts, normals):
-    """model._shade of k0 at the vertices, seen head-on from outside (view direction -normal) -> [V,3] in [0,1]."""
+    """model._shade of k0 at the vertices, seen head-on from outside (view direction -normal) -> [V,3] in [0,1].
+    A positional-encoding model (posbase_pe > 0) colours from the vertex positions themselves; its k0 is not read."""
     out = torch.empty((verts.shape[0], 3), dtype=torch.float32, device=verts.device)
+    posenc = getattr(model, 'uses_posenc', False)
     for i in range(0, verts.shape[0], COLOR_CHUNK):
         v, nrm = verts[i:i + COLOR_CHUNK], normals[i:i + COLOR_CHUNK]
-        k0 = model.grid_sampler(v, model.k0)
-        rgb = model._shade(k0, (-nrm).contiguous(), torch.arange(v.shape[0], device=v.device))
+        rid = torch.arange(v.shape[0], device=v.device)
+        if posenc:
+            rgb = model._shade_posenc(v.contiguous(), (-nrm).contiguous(), rid)
+        else:
+            k0 = model.grid_sampler(v, model.k0)
+            rgb = model._shade(k0, (-nrm).contiguous(), rid)
         out[i:i + v.shape[0]] = rgb[:, :3]
     return out
 

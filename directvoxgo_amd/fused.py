@@ -151,7 +151,7 @@ def split_grid_rows(G, density, k0):
 
 class _FusedMarch(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, density, k0, rays_o, rays_d, cfg, capacity=False):
+    def forward(ctx, density, k0, rays_o, rays_d, cfg, capacity=False, positions=False):
         for x, n in ((rays_o, 'rays_o'), (rays_d, 'rays_d')):
             check_input(x, n); check_f32(x, n)
         if not (density.is_cuda and k0.is_cuda):
@@ -282,6 +282,9 @@ class _FusedMarch(torch.autograd.Function):
                    ptr(start), ptr(dirs), _flt(cfg.stepdist), cfg.xyz_min_h, cfg.xyz_max_h, ptr(k0), _int(C),
                    _int(X), _int(Y), _int(Z), _i64(sC), _i64(sX), _i64(sY), _i64(sZ), ptr(ray_id), ptr(step_id),
                    ptr(weights), ptr(alpha), ptr(feat), st)
+            if positions:              # the kept samples' positions in place of the (zero-channel) features
+                from .shade import march_positions
+                feat = march_positions(start, dirs, ray_id, step_id, cfg.stepdist)
         ctx.cfg = cfg
         ctx.geom = (X, Y, Z, C, sC, sX, sY, sZ, stride, N)
         ctx.bricks = (brick_off, brick_cur, brick_cnt, extra_brick, slice_len, n_entries) if bricks else None
@@ -291,7 +294,7 @@ class _FusedMarch(torch.autograd.Function):
         ctx.save_for_backward(rec2, n2, n_steps, cum if cum is not None else n_steps, off3, start, dirs, last,
                               ray_id, step_id)
         off3 = off3[:N + 1]
-        ctx.mark_non_differentiable(alpha, ray_id, step_id, off3)
+        ctx.mark_non_differentiable(alpha, ray_id, step_id, off3, *((feat,) if positions else ()))
         ctx.set_materialize_grads(False)     # no zero-filled [M3] int64 'gradients' for the id outputs (33 MB per step)
         return weights, alpha, last, feat, ray_id, step_id, off3
 
@@ -361,14 +364,14 @@ class _FusedMarch(torch.autograd.Function):
                            cfg.xyz_min_h, cfg.xyz_max_h, ptr(None), _int(C), _int(X), _int(Y), _int(Z), ptr(None), ptr(None),
                            *tail, ptr(tiles), _int(3), st)
                     cap.stepped = True
-                    return None, None, None, None, None, None
+                    return None, None, None, None, None, None, None
                 if fuse and brick_union._active is None:
                     tail = cap.adam()
                     L.call('dvgo_brick_accumulate', *items, ptr(recs), ptr(start), ptr(dirs), _flt(cfg.stepdist),
                            cfg.xyz_min_h, cfg.xyz_max_h, ptr(g_feat), _int(C), _int(X), _int(Y), _int(Z), ptr(None), ptr(None),
                            *tail, ptr(None), _int(0), st)
                     cap.stepped = True
-                    return None, None, None, None, None, None
+                    return None, None, None, None, None, None, None
                 grad_k0 = torch.empty_like(ctx.k0_meta, memory_format=torch.preserve_format)
                 grad_density = torch.empty_like(ctx.density_meta)
                 assert grad_k0.stride() == ctx.k0_meta.stride() and grad_density.is_contiguous()
@@ -376,7 +379,7 @@ class _FusedMarch(torch.autograd.Function):
                        cfg.xyz_min_h, cfg.xyz_max_h, ptr(g_feat), _int(C), _int(X), _int(Y), _int(Z), ptr(grad_k0),
                        ptr(grad_density), ptr(None), ptr(None), ptr(None), _flt(0), _int(0),
                        ptr(None), ptr(None), ptr(None), _flt(0), _int(0), _flt(0), _flt(0), _flt(0), ptr(None), ptr(None), _int(0), st)
-                return grad_density, grad_k0, None, None, None, None
+                return grad_density, grad_k0, None, None, None, None, None
 
             # worth its two extra full-grid passes (zero 64 B, split 116 B per voxel) from ~1 kept sample per 6 voxels
             combined = (COMBINED_GRID_GRAD and want_k0 and want_d and C == 12 and M3 * COMBINED_MIN_RATIO >= X * Y * Z and tuple(ctx.density_meta.shape[2:]) == (X, Y, Z)
@@ -393,7 +396,7 @@ class _FusedMarch(torch.autograd.Function):
                 cap = grid_rows_capture._active
                 if cap is not None and cap.G is None and cap.density is ctx.density_meta and cap.k0 is ctx.k0_meta:
                     cap.G = G                  # the optimizer consumes the rows; no dense gradients are produced
-                    return None, None, None, None, None, None
+                    return None, None, None, None, None, None, None
                 grad_k0 = torch.empty_like(ctx.k0_meta, memory_format=torch.preserve_format)
                 grad_density = torch.empty_like(ctx.density_meta)
                 assert grad_k0.stride() == ctx.k0_meta.stride() and grad_density.is_contiguous()
@@ -409,7 +412,7 @@ class _FusedMarch(torch.autograd.Function):
                 if want_d:
                     grad_density = torch.zeros_like(ctx.density_meta)
                     density_bwd(grad_density, 1, None)
-        return grad_density, grad_k0, None, None, None, None
+        return grad_density, grad_k0, None, None, None, None, None
 
 
 @torch.no_grad()
@@ -438,12 +441,14 @@ def fused_hit(rays_o, rays_d, cfg):
     return hit
 
 
-def fused_march(density, k0, rays_o, rays_d, cfg, capacity=False):
+def fused_march(density, k0, rays_o, rays_d, cfg, capacity=False, positions=False):
     """-> weights [M3], raw_alpha [M3], alphainv_last [N], k0 features [M3,C], ray_id, step_id [M3],
     off3 [N+1] (exclusive offsets of each ray's samples in the M3 arrays).
     `capacity=True`: no host synchronisation; the M3-sized outputs are allocated at their upper bound and only their
-    first off3[N] rows are defined (pass `off3[N:]` as `m_dev` to the consumers)."""
-    return _FusedMarch.apply(density, k0, rays_o.contiguous(), rays_d.contiguous(), cfg, capacity)
+    first off3[N] rows are defined (pass `off3[N:]` as `m_dev` to the consumers).
+    `positions=True` (positional-encoding colour head): k0 must have zero channels (nothing is read from it) and the
+    fourth output is the kept samples' positions [M3,3] instead of the features, with no gradient."""
+    return _FusedMarch.apply(density, k0, rays_o.contiguous(), rays_d.contiguous(), cfg, capacity, positions)
 
 
 class _Composite(torch.autograd.Function):

@@ -82,20 +82,10 @@ def viewdir_embed(viewdirs, viewfreq):
 
 def head_layers(rgbnet):
     """(lin1, lin2, lin3) when the module tree is the 3-layer head the kernel implements, else None."""
-    if not isinstance(rgbnet, nn.Sequential) or len(rgbnet) != 4:
+    layers = head_layers_any_din(rgbnet)       # built: 128 (configs/default.py) and 64 (configs/llff, lib/dmpigo.py)
+    if layers is None or layers[0].in_features > 40:
         return None
-    a, r, mid, c = rgbnet
-    if not (isinstance(a, nn.Linear) and isinstance(r, nn.ReLU) and isinstance(c, nn.Linear)):
-        return None
-    if not (isinstance(mid, nn.Sequential) and len(mid) == 2 and isinstance(mid[0], nn.Linear) and isinstance(mid[1], nn.ReLU)):
-        return None
-    width = a.out_features
-    if width not in (128, 64) or mid[0].in_features != width or mid[0].out_features != width or c.in_features != width \
-            or c.out_features != 3:
-        return None          # built: 128 (configs/default.py) and 64 (configs/llff, lib/dmpigo.py)
-    if a.in_features > 40:
-        return None
-    return a, mid[0], c
+    return layers
 
 
 def _scratch(width, device):
@@ -196,3 +186,113 @@ def shade(rgbnet, feat, emb, ray_id, diffuse, m_dev=None):
         return None
     return _Shade.apply(feat, emb, ray_id, l1.weight, l1.bias, l2.weight, l2.bias, l3.weight, l3.bias, diffuse,
                         torch.is_grad_enabled(), m_dev)
+
+
+def posenc_supported(rgbnet, n_freq, emb_dim):
+    """True when the positional-encoding head kernels (csrc/shade_pe.hip) are built for this head: the 3-layer head of
+    width 128 with d_in = 3 + 6 * n_freq + emb_dim <= 96."""
+    layers = head_layers_any_din(rgbnet)
+    return (layers is not None and layers[0].out_features == 128 and 1 <= n_freq
+            and layers[0].in_features == 3 + 6 * n_freq + emb_dim <= 96)
+
+
+def head_layers_any_din(rgbnet):
+    """(lin1, lin2, lin3) of a Sequential(Linear, ReLU, Sequential(Linear, ReLU), Linear) head of width 128 or 64,
+    whatever its input width."""
+    if not isinstance(rgbnet, nn.Sequential) or len(rgbnet) != 4:
+        return None
+    a, r, mid, c = rgbnet
+    if not (isinstance(a, nn.Linear) and isinstance(r, nn.ReLU) and isinstance(c, nn.Linear)):
+        return None
+    if not (isinstance(mid, nn.Sequential) and len(mid) == 2 and isinstance(mid[0], nn.Linear) and isinstance(mid[1], nn.ReLU)):
+        return None
+    width = a.out_features
+    if width not in (128, 64) or mid[0].in_features != width or mid[0].out_features != width or c.in_features != width \
+            or c.out_features != 3:
+        return None
+    return a, mid[0], c
+
+
+class _ShadePosenc(torch.autograd.Function):
+    """rgb of the positional-encoding head (csrc/shade_pe.hip).  Positions and view embedding carry no gradient; the
+    backward produces the six parameter gradients (the weight-gradient kernel honours `defer_wgrad`)."""
+
+    @staticmethod
+    def forward(ctx, pts, emb, ray_id, freq, W1, b1, W2, b2, W3, b3, train):
+        M = pts.shape[0]
+        P, E = freq.shape[0], emb.shape[1]
+        width, d_in = W1.shape
+        pts, emb, freq = pts.contiguous(), emb.contiguous(), freq.contiguous()
+        train = bool(train) and any(ctx.needs_input_grad)
+        dev = pts.device
+        rgb = torch.empty((M, 3), dtype=torch.float32, device=dev)
+        H1 = torch.empty((M, width), dtype=torch.float32, device=dev) if train else None
+        H2 = torch.empty((M, width), dtype=torch.float32, device=dev) if train else None
+        masks = torch.empty((M, 4), dtype=torch.int64, device=dev) if train else None
+        with L.device_of(pts):
+            L.call('dvgo_shade_pe_fwd', ptr(pts), ptr(freq), _int(P), ptr(emb), _int(E), ptr(ray_id), _i64(M), ptr(W1.contiguous()),
+                   ptr(b1.contiguous()), ptr(W2.contiguous()), ptr(b2.contiguous()), ptr(W3.contiguous()), ptr(b3.contiguous()),
+                   _int(width), _int(d_in), ptr(rgb), ptr(H1), ptr(H2), ptr(masks), stream_of(pts))
+        if train:
+            ctx.save_for_backward(pts, emb, ray_id, freq, W2, W3, rgb, H1, H2, masks)
+            ctx.params = (W1, b1, W2, b2, W3, b3)
+            ctx.d_in = d_in
+        return rgb
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_rgb):
+        pts, emb, ray_id, freq, W2, W3, rgb, H1, H2, masks = ctx.saved_tensors
+        M, width, d_in = pts.shape[0], H1.shape[1], ctx.d_in
+        G1 = torch.empty_like(H1)
+        gz = torch.empty_like(rgb)
+        with L.device_of(pts):
+            L.call('dvgo_shade_pe_bwd', ptr(g_rgb.contiguous()), ptr(rgb), ptr(masks), _i64(M), ptr(W2.contiguous()),
+                   ptr(W3.contiguous()), _int(width), ptr(G1), ptr(gz), stream_of(pts))
+
+        def wgrad():
+            lib = L.lib()
+            lib.dvgo_shade_pe_record_size.restype = ctypes.c_int64
+            rec = int(lib.dvgo_shade_pe_record_size(width, d_in))
+            n_parts = max(1, min(N_PARTS, (M + 31) // 32))
+            part = torch.empty((n_parts, rec), dtype=torch.float32, device=pts.device)
+            tot = torch.empty(rec, dtype=torch.float32, device=pts.device)
+            with L.device_of(pts):
+                L.call('dvgo_shade_pe_wgrad', ptr(G1), ptr(gz), ptr(masks), ptr(W3.contiguous()), ptr(H1), ptr(H2), ptr(pts),
+                       ptr(freq), _int(freq.shape[0]), ptr(emb), _int(emb.shape[1]), ptr(ray_id), _i64(M), _int(width),
+                       _int(d_in), _int(n_parts), ptr(part), ptr(tot), stream_of(pts))
+            o = 0                                # the compact record of include/dvgo_hip.h: the gradients are views of it
+            gW2 = tot[o:o + width * width].view(width, width); o += width * width
+            gW1 = tot[o:o + width * d_in].view(width, d_in); o += width * d_in
+            gW3 = tot[o:o + 3 * width].view(3, width); o += 3 * width
+            gb1, gb2, gb3 = tot[o:o + width], tot[o + width:o + 2 * width], tot[o + 2 * width:o + 2 * width + 3]
+            return gW1, gb1, gW2, gb2, gW3, gb3
+
+        if defer_wgrad._active is not None:
+            defer_wgrad._active.submit(ctx.params, wgrad, pts.device)
+            return (None,) * 11
+        gW1, gb1, gW2, gb2, gW3, gb3 = wgrad()
+        return (None, None, None, None, gW1, gb1, gW2, gb2, gW3, gb3, None)
+
+
+def shade_posenc(rgbnet, pts, emb, ray_id, posfreq):
+    """rgb [M,3] = sigmoid(rgbnet(cat([pts, sin(pts (x) posfreq), cos(pts (x) posfreq), emb[ray_id]]))) -- the
+    positional-encoding head of lib/dvgo.py:528-534 -- or None when the head is not a shape the kernels were built for
+    (width 128, d_in <= 96).  `emb` is the per-ray view embedding (viewdir_embed), `pts` the kept samples' positions."""
+    if not pts.is_cuda or not posenc_supported(rgbnet, posfreq.shape[0], emb.shape[1]):
+        return None
+    l1, l2, l3 = head_layers_any_din(rgbnet)
+    return _ShadePosenc.apply(pts, emb, ray_id, posfreq, l1.weight, l1.bias, l2.weight, l2.bias, l3.weight, l3.bias,
+                              torch.is_grad_enabled())
+
+
+@torch.no_grad()
+def march_positions(start, dirs, ray_id, step_id, stepdist):
+    """pts [M,3] of the fused march's kept samples: start + dir * stepdist * step_id (csrc/shade_pe.hip), bitwise what
+    sample_pts_on_rays writes for the same samples."""
+    M = ray_id.shape[0]
+    pts = torch.empty((M, 3), dtype=torch.float32, device=start.device)
+    with L.device_of(start):
+        L.call('dvgo_march_positions', ptr(start), ptr(dirs), ptr(ray_id), ptr(step_id), _i64(M), L._flt(float(stepdist)), ptr(pts),
+               stream_of(start))
+    return pts

@@ -181,6 +181,12 @@ class TrainStep:
         self.optimizer = optimizer or create_optimizer_or_freeze_model(model, cfg_train, global_step=0)
         self.pg = process_group
         self.world = dist.get_world_size(process_group) if (dist.is_available() and dist.is_initialized()) else 1
+        # a positional-encoding colour head (posbase_pe > 0) reads no k0: only the density grid gets a gradient, so the
+        # paths that take both grids' gradients together (brick scatter with the fused Adam, combined gradient rows) stay off
+        self.k0_idle = bool(getattr(model, 'uses_posenc', False))
+        if self.k0_idle and self.world > 1:
+            raise NotImplementedError('data-parallel training of a posbase_pe model (positional-encoding colour head) is not '
+                                      'built: train it on one GPU')
         self.decay_factor = 0.1 ** (1 / (cfg_train['lrate_decay'] * 1000))
         self._small = [p for n, p in model.named_parameters() if n not in ('density', 'k0') and p.requires_grad]
 
@@ -377,7 +383,7 @@ class TrainStep:
         cfg, model = self.cfg, self.model
         density, k0 = getattr(model, 'density', None), getattr(model, 'k0', None)
         tv = (cfg['weight_tv_density'] > 0 or cfg['weight_tv_k0'] > 0) and cfg['tv_before'] > cfg['tv_after']
-        return bool(self.world == 1 and self.fused_loss and self.rows_adam and not tv
+        return bool(self.world == 1 and self.fused_loss and self.rows_adam and not tv and not self.k0_idle
                     and isinstance(self.optimizer, MaskedAdam) and isinstance(density, nn.Parameter) and density.is_cuda
                     and hasattr(model, 'can_keep_count_on_device') and model.can_keep_count_on_device()
                     and self.optimizer.can_fuse_grid_step(density, k0) and self.optimizer.per_lr is None)
@@ -456,7 +462,7 @@ class TrainStep:
         density, k0 = getattr(model, 'density', None), getattr(model, 'k0', None)
         # may the march's brick scatter apply the grid update itself?  One GPU: from its own tiles.  Data parallel: from the
         # all-reduced tiles of the bricks any rank touched (fused.brick_union) while that union stays small.
-        own = (self.rows_adam and not tv_now and isinstance(self.optimizer, MaskedAdam)
+        own = (self.rows_adam and not tv_now and not self.k0_idle and isinstance(self.optimizer, MaskedAdam)
                and isinstance(density, nn.Parameter) and isinstance(k0, nn.Parameter) and density.is_cuda)
         fuse_adam = own and self.optimizer.can_fuse_grid_step(density, k0)
         dp_bricks = bool(fuse_adam and self.world > 1 and self.brick_sparse and getattr(model, 'fused', False))

@@ -38,7 +38,8 @@ extern "C" {
 #define DVGO_EINVAL (-1)   /* invalid argument (null pointer, negative size, bad stride) */
 #define DVGO_ERANGE (-2)   /* size exceeds what the kernel's 32-bit indexing supports    */
 
-/* version of this ABI; bumped on any signature change */
+/* version of this ABI; bumped on any signature change (6: the positional-encoding colour head) */
+#define DVGO_ABI_VERSION 6
 int dvgo_abi_version(void);
 
 /* Kernel-variant selection for A/B measurements (process-global; defaults are the fastest
@@ -443,6 +444,35 @@ int dvgo_shade_bwd(const float* g_rgb, const float* rgb, const uint64_t* masks, 
 int dvgo_shade_wgrad(const float* G1, const float* gz, const uint64_t* masks, const float* W3,
                      const float* H1, const float* H2, const float* feat, int C, const float* emb, int E, const int64_t* ray_id, int64_t M,
                      const int64_t* m_dev, int width, int diffuse, int n_parts, float* part, float* total, void* stream);
+
+/* ---------------------------------------------------------------------------------
+ * Positional-encoding colour head (posbase_pe = P > 0, lib/dvgo.py:528-534), csrc/shade_pe.hip:
+ *   X   = cat([pts, sin(pts (x) freq), cos(pts (x) freq), emb[ray_id]])    d_in = 3 + 6P + E columns, never stored
+ *   rgb = sigmoid(W3 relu(W2 relu(W1 X + b1) + b2) + b3)                     no diffuse term; the feature grid is unused
+ * Built for width 128 and d_in <= 96 (P <= 10 with the view embedding of viewbase_pe = 4); DVGO_ERANGE otherwise: fall
+ * back.  freq [P] is the model's posfreq buffer (2^j), emb [n_rays, E] the output of dvgo_viewdir_embed.
+ * dvgo_march_positions: pts [M,3] = start + dir * stepdist * step_id of the fused march's kept samples (the expression
+ *   of dvgo_sample_pts_on_rays, so the positions equal its ray_pts bit for bit).
+ * dvgo_shade_pe_fwd: rgb [M,3]; H1, H2 [M,width] and masks [M,4] (ReLU sign bits, as dvgo_shade_fwd) all NULL, or all
+ *   given (training).
+ * dvgo_shade_pe_bwd: gz [M,3] = g_rgb * sigmoid', G1 [M,width] = relu'(H1) * (W2^T (relu'(H2) * (W3^T gz))).
+ *   Positions and view directions carry no gradient: there is no input gradient.
+ * dvgo_shade_pe_wgrad: n_parts workgroups write partial records (part: n_parts * dvgo_shade_pe_record_size floats) and a
+ *   second launch sums them into `total`, the compact record of dvgo_shade_wgrad
+ *   { dW2 [width][width], dW1 [width][d_in], dW3 [3][width], db1 [width], db2 [width], db3 [3] }; X is rebuilt from
+ *   pts, freq, emb and ray_id exactly as in the forward. */
+int dvgo_march_positions(const float* rays_start, const float* rays_dir, const int64_t* ray_id, const int64_t* step_id,
+                         int64_t M, float stepdist, float* pts, void* stream);
+int dvgo_shade_pe_fwd(const float* pts, const float* freq, int P, const float* emb, int E, const int64_t* ray_id, int64_t M,
+                      const float* W1, const float* b1, const float* W2, const float* b2, const float* W3, const float* b3,
+                      int width, int d_in, float* rgb, float* H1, float* H2, uint64_t* masks, void* stream);
+int dvgo_shade_pe_bwd(const float* g_rgb, const float* rgb, const uint64_t* masks, int64_t M, const float* W2,
+                      const float* W3, int width, float* G1, float* gz, void* stream);
+int64_t dvgo_shade_pe_record_size(int width, int d_in);
+int dvgo_shade_pe_wgrad(const float* G1, const float* gz, const uint64_t* masks, const float* W3, const float* H1,
+                        const float* H2, const float* pts, const float* freq, int P, const float* emb, int E,
+                        const int64_t* ray_id, int64_t M, int width, int d_in, int n_parts, float* part, float* total,
+                        void* stream);
 
 /* ---------------------------------------------------------------------------------
  * "next" rows N1/N2: optimizer and regulariser kernels.
