@@ -1,0 +1,257 @@
+"""DirectContractedVoxGO: a voxel grid over a contracted space, for unbounded (360-degree, real-background) scenes.
+
+Formulas from DVGO v2 (Sun et al., "Improved Direct Voxel Grid Optimization for Radiance Fields Reconstruction",
+arXiv:2206.05085), which borrows the scene contraction and the distortion loss of Mip-NeRF 360 (Barron et al., CVPR
+2022).  The reference code base has no such model; the contract is the sampler stated in `contracted_sample` and
+restated in float32 by tests/unbounded_oracle.py, which the HIP sampler matches bit for bit.
+
+Geometry.  `xyz_min` / `xyz_max` are the FOREGROUND box.  Per axis, c = (min + max) / 2 and r = (max - min) / 2 map it
+to [-1, 1]^3; everything beyond is contracted into the shell 1 < |q| <= 1 + b (b = `bg_len`, norm `contracted_norm`:
+'inf' for the max norm, 'l2').  The grids live on a cubic W^3 lattice over [-(1+b), 1+b]^3 (the `xyz_min` / `xyz_max`
+buffers hold these contracted bounds; `get_kwargs` returns the foreground box).
+
+Forward, in the order of DirectVoxGO.forward: contracted sampling with the occupancy lookup (csrc/contract.hip) ->
+density trilinear -> Raw2Alpha -> alpha filter -> Alphas2Weights -> weight filter -> k0 trilinear and colour (the HIP
+colour head where its shapes allow) -> composite with render_kwargs['bg'].  `near` and `far` are accepted and ignored:
+the sample distances are a fixed table (`contracted_t_table`) in normalised units, from the ray origin to infinity.
+The result carries, besides DirectVoxGO's keys, `step_id`, `t`, `s = 1 - 1/(1+t)` (per kept sample) and `n_max`;
+`depth` (render_depth) is sum_i w_i t_i in normalised units (the foreground box has half-size 1 on every axis).
+NDC rays, posbase_pe, voxel_count_views / maskout_near_cam_vox and mesh extraction are not supported.
+"""
+import numpy as np
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+
+from . import _lib as L
+from ._lib import _flt, _i64, _int, check_f32, check_input, ptr, stream_of
+from .dvgo import DirectVoxGO, _as_f32, make_rgbnet
+from .fused import composite
+from .ops import Alphas2Weights, MaskCache
+
+
+def contracted_t_table(world, stepsize, bg_len):
+    """-> (t float32 [n_max], N_in, n_max): N_in midpoints of a uniform split of [0, 2] and N_in of a split of [2, 256]
+    uniform in 1/t; built in float64, rounded once to float32."""
+    n_in = int(np.floor(2 / (2 + 2 * bg_len) * world / stepsize)) + 1
+    b_in = np.linspace(0, 2, n_in + 1)
+    b_out = 2 / np.linspace(1, 1 / 128, n_in + 1)
+    mid = lambda b: (b[1:] + b[:-1]) / 2       # noqa: E731
+    t = np.concatenate([mid(b_in), mid(b_out)]).astype(np.float32)
+    return t, n_in, 2 * n_in
+
+
+def thinning_threshold(world, stepsize, bg_len):
+    """Contracted-space distance between two kept samples outside the unit box: 0.95 of a step of the lattice."""
+    return float(np.float32((2 + 2 * bg_len) / world * stepsize * 0.95))
+
+
+def contracted_sample(rays_o, rays_d, center, radius, t_tab, bg_len, contracted_norm, thres, mask_cache=None):
+    """The contracted sampler (csrc/contract.hip), per ray in float32:
+
+        o' = (o - c) / r;  u = d / r;  d' = u / ||u||_2;  p_k = o' + d' * t_k  (k < n_max = len(t_tab))
+        n_k = max|p_k| ('inf') or ||p_k||_2 ('l2');  q_k = p_k if n_k <= 1 else p_k / n_k * ((1 + b) - b / n_k)
+        kept: (n_k <= 1 or over_k) and mask_cache(q_k);  over_0 = False,
+              k >= 1: acc += ||q_k - q_{k-1}||_2;  over_k = acc > thres;  acc = 0 when over_k
+
+    -> (q [M,3], ray_id [M], step_id [M] int64, t [M]) of the kept samples, ray-major and step-ascending.  One host
+    synchronisation (the total count).  rays_d must have no zero-length row."""
+    check_input(rays_o, 'rays_o'); check_f32(rays_o, 'rays_o')
+    check_input(rays_d, 'rays_d'); check_f32(rays_d, 'rays_d')
+    for x, n in ((center, 'center'), (radius, 'radius'), (t_tab, 't_tab')):
+        check_input(x, n); check_f32(x, n)
+    if contracted_norm not in ('inf', 'l2'):
+        raise ValueError(f"contracted_norm must be 'inf' or 'l2', got {contracted_norm!r}")
+    N, n_max, dev = rays_o.shape[0], t_tab.shape[0], rays_o.device
+    l2 = _int(1 if contracted_norm == 'l2' else 0)
+    if mask_cache is not None:
+        mask = mask_cache.mask.contiguous()
+        if mask.dtype != torch.bool:
+            raise RuntimeError('mask must be bool')
+        mi, mj, mk = (int(v) for v in mask.shape)
+        mext = (ptr(mask), _int(mi), _int(mj), _int(mk), ptr(mask_cache.xyz2ijk_scale.contiguous()),
+                ptr(mask_cache.xyz2ijk_shift.contiguous()))
+    else:
+        mext = (ptr(None), _int(0), _int(0), _int(0), ptr(None), ptr(None))
+    head = (ptr(rays_o), ptr(rays_d), _i64(N), ptr(center), ptr(radius), ptr(t_tab), _int(n_max), _flt(float(bg_len)), l2,
+            _flt(float(thres))) + mext
+    counts = torch.empty(N, dtype=torch.int32, device=dev)
+    offsets = torch.empty(N + 1, dtype=torch.int64, device=dev)
+    with L.device_of(rays_o):
+        st = stream_of(rays_o)
+        L.call('dvgo_contract_count', *head, ptr(counts), st)
+        L.call('dvgo_exclusive_scan_i32', ptr(counts), _i64(N), ptr(offsets), st)
+        M = int(offsets[N])                                                  # the one host synchronisation
+        q = torch.empty((M, 3), dtype=torch.float32, device=dev)
+        ray_id = torch.empty(M, dtype=torch.int64, device=dev)
+        step_id = torch.empty(M, dtype=torch.int64, device=dev)
+        t = torch.empty(M, dtype=torch.float32, device=dev)
+        if M:
+            L.call('dvgo_contract_emit', *head, ptr(offsets), ptr(q), ptr(ray_id), ptr(step_id), ptr(t), st)
+    return q, ray_id, step_id, t
+
+
+class DirectContractedVoxGO(nn.Module):
+    """Voxel grids over the contracted space of an unbounded scene (see the module docstring)."""
+
+    def __init__(self, xyz_min, xyz_max, num_voxels=0, num_voxels_base=0, alpha_init=None,
+                 mask_cache_world_size=None, fast_color_thres=0, bg_len=0.2, contracted_norm='inf',
+                 rgbnet_dim=0, rgbnet_direct=True, rgbnet_depth=3, rgbnet_width=128, viewbase_pe=4, fused=True,
+                 posbase_pe=0):
+        super().__init__()
+        if posbase_pe:
+            raise NotImplementedError('posbase_pe is not supported by DirectContractedVoxGO')
+        if contracted_norm not in ('inf', 'l2'):
+            raise ValueError(f"contracted_norm must be 'inf' or 'l2', got {contracted_norm!r}")
+        self.fused = bool(fused)
+        self.fused_shade = True
+        self.channels_last = True
+        self.posbase_pe = 0
+        fg_min, fg_max = _as_f32(xyz_min), _as_f32(xyz_max)
+        self._fg_min_cpu, self._fg_max_cpu = fg_min.clone(), fg_max.clone()
+        self.register_buffer('scene_center', (fg_min + fg_max) * 0.5)
+        self.register_buffer('scene_radius', (fg_max - fg_min) * 0.5)
+        self.bg_len = float(bg_len)
+        self.contracted_norm = contracted_norm
+        lim = 1 + self.bg_len
+        cmin, cmax = torch.full((3,), -lim, dtype=torch.float32), torch.full((3,), lim, dtype=torch.float32)
+        self.register_buffer('xyz_min', cmin.clone())
+        self.register_buffer('xyz_max', cmax.clone())
+        self._xyz_min_cpu, self._xyz_max_cpu = cmin, cmax
+        self.fast_color_thres = fast_color_thres
+
+        self.num_voxels_base = num_voxels_base
+        self.voxel_size_base = ((self._xyz_max_cpu - self._xyz_min_cpu).prod() / self.num_voxels_base).pow(1 / 3)
+        self.alpha_init = alpha_init
+        self.act_shift = np.log(1 / (1 - alpha_init) - 1)
+        self._set_grid_resolution(num_voxels)
+
+        ws = [int(v) for v in self.world_size]
+        self.density = nn.Parameter(torch.zeros([1, 1, *ws]))
+        self.rgbnet_kwargs = {'rgbnet_dim': rgbnet_dim, 'rgbnet_direct': rgbnet_direct, 'rgbnet_depth': rgbnet_depth,
+                              'rgbnet_width': rgbnet_width, 'viewbase_pe': viewbase_pe}
+        if rgbnet_dim <= 0:
+            self.k0_dim = 3
+            self.rgbnet = None
+        else:
+            self.k0_dim = rgbnet_dim
+            self.rgbnet_direct = rgbnet_direct
+            self.register_buffer('viewfreq', torch.FloatTensor([(2 ** i) for i in range(viewbase_pe)]))
+            dim0 = (3 + 3 * viewbase_pe * 2) + (self.k0_dim if rgbnet_direct else self.k0_dim - 3)
+            self.rgbnet = make_rgbnet(dim0, rgbnet_width, rgbnet_depth)
+        self.k0 = nn.Parameter(self._alloc_k0(ws))
+
+        self.mask_cache_world_size = None if mask_cache_world_size is None else [int(v) for v in mask_cache_world_size]
+        mws = self.mask_cache_world_size or ws
+        self.mask_cache = MaskCache(path=None, mask=torch.ones(mws, dtype=torch.bool), xyz_min=self._xyz_min_cpu,
+                                    xyz_max=self._xyz_max_cpu)
+        self._tab_cache = {}
+
+    # shared with DirectVoxGO: the same grids, activation, TV and colour head
+    _alloc_k0 = DirectVoxGO._alloc_k0
+    activate_density = DirectVoxGO.activate_density
+    grid_sampler = DirectVoxGO.grid_sampler
+    density_total_variation_add_grad = DirectVoxGO.density_total_variation_add_grad
+    k0_total_variation_add_grad = DirectVoxGO.k0_total_variation_add_grad
+    _shade = DirectVoxGO._shade
+    uses_posenc = False
+
+    def can_keep_count_on_device(self):
+        """The capacity mode of the fused march does not exist for this model."""
+        return False
+
+    def _set_grid_resolution(self, num_voxels):
+        """DirectVoxGO._set_grid_resolution on the contracted cube: the lattice is W^3."""
+        self.num_voxels = num_voxels
+        ext = self._xyz_max_cpu - self._xyz_min_cpu
+        self.voxel_size = (ext.prod() / num_voxels).pow(1 / 3)
+        self.world_size = (ext / self.voxel_size).long()
+        self.voxel_size_ratio = self.voxel_size / self.voxel_size_base
+        self._tab_cache = {}
+
+    @property
+    def world(self):
+        return int(self.world_size[0])
+
+    def get_kwargs(self):
+        return {
+            'xyz_min': self._fg_min_cpu.numpy(), 'xyz_max': self._fg_max_cpu.numpy(),
+            'num_voxels': self.num_voxels, 'num_voxels_base': self.num_voxels_base,
+            'alpha_init': self.alpha_init, 'act_shift': self.act_shift, 'voxel_size_ratio': self.voxel_size_ratio,
+            'mask_cache_world_size': self.mask_cache_world_size, 'fast_color_thres': self.fast_color_thres,
+            'bg_len': self.bg_len, 'contracted_norm': self.contracted_norm,
+            **self.rgbnet_kwargs,
+        }
+
+    @torch.no_grad()
+    def scale_volume_grid(self, num_voxels):
+        """Trilinear resize of both grids to the new cubic lattice; the occupancy mask is rebuilt from the max-pooled
+        activated density (at mask_cache_world_size when that is set)."""
+        self._set_grid_resolution(num_voxels)
+        ws = tuple(int(v) for v in self.world_size)
+        self.density = nn.Parameter(F.interpolate(self.density.data, size=ws, mode='trilinear', align_corners=True))
+        k0 = F.interpolate(self.k0.data.contiguous(), size=ws, mode='trilinear', align_corners=True)
+        self.k0 = nn.Parameter(k0.contiguous(memory_format=torch.channels_last_3d) if self.k0_dim > 1 else k0)
+        self_alpha = F.max_pool3d(self.activate_density(self.density), kernel_size=3, padding=1, stride=1)
+        if self.mask_cache_world_size is not None and list(self.mask_cache_world_size) != list(ws):
+            self_alpha = F.interpolate(self_alpha, size=tuple(self.mask_cache_world_size), mode='trilinear',
+                                       align_corners=True)
+        mask = self_alpha[0, 0] > self.fast_color_thres
+        self.mask_cache = MaskCache(path=None, mask=mask.cpu(), xyz_min=self._xyz_min_cpu,
+                                    xyz_max=self._xyz_max_cpu).to(self.density.device)
+
+    def maskout_near_cam_vox(self, cam_o, near):
+        raise NotImplementedError('maskout_near_cam_vox is not built for contracted space')
+
+    def voxel_count_views(self, *args, **kwargs):
+        raise NotImplementedError('voxel_count_views (pervoxel_lr) is not built for contracted space')
+
+    def _table(self, stepsize, device):
+        key = (float(stepsize), str(device))
+        tab = self._tab_cache.get(key)
+        if tab is None:
+            t, _, n_max = contracted_t_table(self.world, stepsize, self.bg_len)
+            tab = (torch.from_numpy(t).to(device), n_max, thinning_threshold(self.world, stepsize, self.bg_len))
+            self._tab_cache[key] = tab
+        return tab
+
+    def sample_ray(self, rays_o, rays_d, stepsize, **render_kwargs):
+        """-> (q [M,3] contracted points, ray_id, step_id, t, n_max) of the kept samples (occupancy applied)."""
+        t_tab, n_max, thres = self._table(stepsize, rays_o.device)
+        q, ray_id, step_id, t = contracted_sample(rays_o.contiguous(), rays_d.contiguous(), self.scene_center,
+                                                  self.scene_radius, t_tab, self.bg_len, self.contracted_norm, thres,
+                                                  self.mask_cache)
+        return q, ray_id, step_id, t, n_max
+
+    def forward(self, rays_o, rays_d, viewdirs, global_step=None, **render_kwargs):
+        """Volume rendering in contracted space; see the module docstring for the order and the extra keys.
+        `near` / `far` in render_kwargs are ignored; `ndc` rays are not supported."""
+        assert len(rays_o.shape) == 2 and rays_o.shape[-1] == 3, 'Only suuport point queries in [N, 3] format'
+        N = len(rays_o)
+        dev = rays_o.device
+        stepsize = render_kwargs['stepsize']
+        q, ray_id, step_id, t, n_max = self.sample_ray(rays_o, rays_d, stepsize)
+        interval = stepsize * self.voxel_size_ratio
+        density = self.grid_sampler(q, self.density)
+        alpha = self.activate_density(density, interval)
+        if self.fast_color_thres > 0:
+            mask = alpha > self.fast_color_thres
+            q, ray_id, step_id, t, alpha = q[mask], ray_id[mask], step_id[mask], t[mask], alpha[mask]
+        weights, alphainv_last = Alphas2Weights.apply(alpha, ray_id, N)
+        if self.fast_color_thres > 0:
+            mask = weights > self.fast_color_thres
+            weights, alpha = weights[mask], alpha[mask]
+            q, ray_id, step_id, t = q[mask], ray_id[mask], step_id[mask], t[mask]
+        k0 = self.grid_sampler(q, self.k0)
+        rgb = self._shade(k0, viewdirs, ray_id)
+        # per-ray sums in fixed order (the march's composite over the ray offsets): bitwise repeatable renders
+        off = torch.searchsorted(ray_id, torch.arange(N + 1, dtype=torch.int64, device=dev))
+        rgb_marched = composite(weights, rgb, alphainv_last, ray_id, off, render_kwargs['bg'])
+        ret = {'alphainv_last': alphainv_last, 'weights': weights, 'rgb_marched': rgb_marched,
+               'raw_alpha': alpha, 'raw_rgb': rgb, 'ray_id': ray_id, 'step_id': step_id, 't': t,
+               's': 1 - 1 / (1 + t), 'n_max': n_max}
+        if render_kwargs.get('render_depth', False):
+            with torch.no_grad():
+                t3 = t.unsqueeze(-1).expand(-1, 3).contiguous()
+                ret['depth'] = composite(weights.detach(), t3, torch.zeros(N, device=dev), ray_id, off, 0.0)[:, 0]
+        return ret

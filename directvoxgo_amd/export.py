@@ -154,8 +154,12 @@ def mesh_field(model, alpha_thres=0.5, resolution=None, bbox=None):
 
 
 def _check_model(model):
+    from .dcvgo import DirectContractedVoxGO
     from .dmpigo import DirectMPIGO
     from .dvgo import DirectVoxGO
+    if isinstance(model, DirectContractedVoxGO):
+        raise NotImplementedError('extract_mesh: DirectContractedVoxGO grids live in contracted space (a non-linear warp '
+                                  'of the unbounded scene); only DirectVoxGO is supported')
     if isinstance(model, DirectMPIGO):
         raise NotImplementedError('extract_mesh: DirectMPIGO scenes live in NDC space (a warped frustum, not a '
                                   'world-space box); only DirectVoxGO is supported')

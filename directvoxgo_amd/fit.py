@@ -41,6 +41,10 @@ def fit_stage(model, rays_o, rays_d, viewdirs, target, cfg_train, render_kwargs,
     `pg_scale` step (run.py:243-245 builds the model at num_voxels_final / 2^len(pg_scale); a model handed over at
     another resolution is resized to that first).  Returns the per-step PSNR list (python floats; PSNR of the main MSE
     term as logged by run.py:378, read back once at the end)."""
+    from .dcvgo import DirectContractedVoxGO
+    if cfg_train.get('pervoxel_lr', False) and isinstance(model, DirectContractedVoxGO):
+        raise ValueError("cfg_train['pervoxel_lr']: voxel_count_views is not built for the contracted space of "
+                         'DirectContractedVoxGO; train it with pervoxel_lr=False')
     n_iters = n_iters or cfg_train['N_iters']
     n_rand = cfg_train['N_rand']
     pg_scale = list(cfg_train.get('pg_scale', []))
@@ -97,6 +101,27 @@ def compute_bbox_by_cam_frustrm(HW, Ks, poses, near, far, ndc=False, inverse_y=F
             lo = torch.minimum(lo, pts.amin(0))
             hi = torch.maximum(hi, pts.amax(0))
     return lo, hi
+
+
+@torch.no_grad()
+def compute_bbox_by_cam_frustrm_unbounded(HW, Ks, poses, near_clip, inner_r=1.0, inverse_y=False, flip_x=False,
+                                          flip_y=False):
+    """Foreground box of an unbounded scene (DVGO v2, arXiv:2206.05085): the tightest box around every training ray's
+    point at `near_clip` (rays_o + rays_d * near_clip, rays from the ray-generation kernel), turned into the cube of
+    half-side max(center - min) * inner_r around its centre.  -> (xyz_min, xyz_max) float32 CPU tensors."""
+    from .render import rays_of_view
+    lo = torch.full((3,), float('inf'), dtype=torch.float64)
+    hi = -lo
+    dev = torch.device('cuda', torch.cuda.current_device())
+    for (H, W), K, c2w in zip(HW, Ks, poses):
+        H, W = int(H), int(W)
+        rays_o, rays_d, _ = rays_of_view(H, W, K, c2w, False, inverse_y, flip_x, flip_y, p0=0, n=H * W, device=dev)
+        pts = (rays_o + rays_d * near_clip).reshape(-1, 3)
+        lo = torch.minimum(lo, pts.amin(0).double().cpu())
+        hi = torch.maximum(hi, pts.amax(0).double().cpu())
+    center = (lo + hi) * 0.5
+    radius = (center - lo).max() * inner_r
+    return (center - radius).float(), (center + radius).float()
 
 
 @torch.no_grad()

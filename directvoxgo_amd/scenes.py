@@ -135,3 +135,86 @@ def roofline_scene(world=160, n_rays=8192, n_samples=256, seed=777, device='cpu'
     sc = {k: v.to(device) for k, v in sc.items()}
     sc.update(near=0.0, far=far, stepsize=stepsize, world=world, n_samples=n_samples, occupancy=1.0)
     return sc
+
+
+def look_at(eye, target, up=(0.0, 0.0, 1.0)):
+    """camera-to-world [4,4] of a camera at `eye` looking at `target` (camera looks down its -z axis)."""
+    eye, target, up = (torch.as_tensor(v, dtype=torch.float32) for v in (eye, target, up))
+    back = eye - target
+    back = back / back.norm()
+    right = torch.linalg.cross(up, back)
+    if float(right.norm()) < 1e-6:
+        right = torch.linalg.cross(torch.tensor([0.0, 1.0, 0.0]), back)
+    right = right / right.norm()
+    upv = torch.linalg.cross(back, right)
+    c2w = torch.eye(4)
+    c2w[:3, 0], c2w[:3, 1], c2w[:3, 2], c2w[:3, 3] = right, upv, back, eye
+    return c2w
+
+
+def unbounded_grids(world, bg_len, gen, blob_r=0.35, shell=(1.06, 1.14)):
+    """Ground-truth grids of an unbounded scene in contracted space [-(1+b), 1+b]^3 (max norm): a blob of radius
+    `blob_r` around the origin inside the unit box, and an opaque textured background shell at contracted radius
+    `shell` (normalised distance 1 / ((1+b) - radius) * b: about 1.4 to 2.5 for b = 0.2).  -> density [1,1,W,W,W] and
+    a colour grid k0 [1,3,W,W,W] (pre-sigmoid)."""
+    lim = 1 + bg_len
+    ax = torch.linspace(-lim, lim, world)
+    x, y, z = torch.meshgrid(ax, ax, ax, indexing='ij')
+    n = torch.maximum(torch.maximum(x.abs(), y.abs()), z.abs())
+    r = torch.sqrt(x ** 2 + y ** 2 + z ** 2)
+    noise = F.avg_pool3d(torch.randn((1, 1, world, world, world), generator=gen), 3, 1, 1)[0, 0]
+    density = 24 * torch.exp(-(r / blob_r) ** 4) - 12 + noise
+    in_shell = (n > shell[0]) & (n < shell[1])
+    density = torch.where(in_shell, torch.full_like(density, 12.0), density)
+    k0 = torch.stack([
+        torch.where(in_shell, 2.5 * torch.sin(9 * x) * torch.cos(7 * y), 3 * x),
+        torch.where(in_shell, 2.5 * torch.sin(8 * y + 1) * torch.cos(6 * z), -1 + 2 * z),
+        torch.where(in_shell, 2.5 * torch.cos(7 * z + 2) * torch.sin(5 * x), 1 - 3 * y)])
+    return density[None, None].contiguous(), k0[None].contiguous()
+
+
+def unbounded_cameras(n_views, gen, radius=(0.55, 0.85)):
+    """Cameras inside the unit foreground box: each at a random direction and distance `radius` from the origin,
+    looking inward (at the origin, through the blob to the background behind it) or outward (straight at the
+    background), alternately."""
+    poses = []
+    for v in range(n_views):
+        d = torch.randn(3, generator=gen)
+        d = d / d.norm()
+        rr = radius[0] + (radius[1] - radius[0]) * float(torch.rand(1, generator=gen))
+        eye = d * rr
+        jitter = torch.randn(3, generator=gen) * 0.1
+        target = jitter if v % 2 == 0 else eye + d + jitter
+        poses.append(look_at(eye, target))
+    return torch.stack(poses)
+
+
+@torch.no_grad()
+def unbounded_scene(world=64, bg_len=0.2, n_train=24, n_test=4, H=32, W=32, focal=24.0, seed=777, stepsize=0.5,
+                    bg=0.5, device='cuda'):
+    """An unbounded test scene: ground-truth grids (`unbounded_grids`), cameras inside the foreground box [-1, 1]^3
+    looking inward and outward (`unbounded_cameras`), and targets rendered from the ground truth by
+    DirectContractedVoxGO itself (its forward is pinned against tests/unbounded_oracle.py).  Returns the ground-truth
+    model, flat training rays / targets, and the held-out views as (poses, HW, Ks, images) for evaluate_viewpoints."""
+    from .dcvgo import DirectContractedVoxGO
+    gen = torch.Generator().manual_seed(seed)
+    density, k0 = unbounded_grids(world, bg_len, gen)
+    gt = DirectContractedVoxGO([-1, -1, -1], [1, 1, 1], num_voxels=world ** 3, num_voxels_base=world ** 3, alpha_init=1e-2,
+                               bg_len=bg_len).to(device)
+    gt.density.data.copy_(density)
+    gt.k0.data.copy_(k0)
+    render_kwargs = dict(near=0.0, far=1e4, stepsize=stepsize, bg=bg)
+    poses = unbounded_cameras(n_train + n_test, gen)
+    K = [[focal, 0, 0.5 * W], [0, focal, 0.5 * H], [0, 0, 1]]
+    rays = []
+    for c2w in poses:
+        o, d, v = camera_rays(H, W, focal, c2w)
+        o, d, v = o.to(device), d.to(device), v.to(device)
+        rgb = torch.cat([gt(o[i:i + 8192], d[i:i + 8192], v[i:i + 8192], **render_kwargs)['rgb_marched']
+                         for i in range(0, o.shape[0], 8192)])
+        rays.append((o, d, v, rgb))
+    cat = lambda k: torch.cat([rays[i][k] for i in range(n_train)]).contiguous()     # noqa: E731
+    return dict(gt=gt, rays_o=cat(0), rays_d=cat(1), viewdirs=cat(2), target=cat(3), render_kwargs=render_kwargs,
+                test_poses=poses[n_train:].numpy(), test_HW=np.array([[H, W]] * n_test), test_Ks=np.array([K] * n_test, np.float32),
+                test_images=[rays[n_train + i][3].reshape(H, W, 3).cpu().numpy() for i in range(n_test)],
+                train_poses=poses[:n_train].numpy(), bg_len=bg_len, world=world, H=H, W=W, focal=focal)

@@ -80,7 +80,19 @@ def render_loss(render_result, target, n_rays_global, cfg_train):
     if cfg_train['weight_rgbper'] > 0:
         rgbper = (render_result['raw_rgb'] - target[render_result['ray_id']]).pow(2).sum(-1)
         loss = loss + cfg_train['weight_rgbper'] * ((rgbper * render_result['weights'].detach()).sum() / n_rays_global)
-    return loss
+    dist_loss = distortion_term(render_result, n_rays_global, cfg_train)
+    return loss if dist_loss is None else loss + dist_loss
+
+
+def distortion_term(render_result, n_rays_global, cfg_train):
+    """weight_distortion * distortion_loss (distortion.py) for a result that carries the per-sample `s` (the contracted
+    model, dcvgo.py); None otherwise, and for configs without `weight_distortion`."""
+    w = cfg_train.get('weight_distortion', 0)
+    if not (w > 0 and 's' in render_result):
+        return None
+    from .distortion import distortion_loss
+    return w * distortion_loss(render_result['weights'], render_result['s'], render_result['n_max'],
+                               render_result['ray_id'], n_rays_global)
 
 
 class _FusedLoss(torch.autograd.Function):
@@ -187,6 +199,12 @@ class TrainStep:
         if self.k0_idle and self.world > 1:
             raise NotImplementedError('data-parallel training of a posbase_pe model (positional-encoding colour head) is not '
                                       'built: train it on one GPU')
+        # the contracted model of unbounded scenes (dcvgo.py) has no fused march: dense grid gradients from the
+        # grid_sample backward, then MaskedAdam; no graph capture, no data parallelism
+        from .dcvgo import DirectContractedVoxGO
+        self.contracted = isinstance(model, DirectContractedVoxGO)
+        if self.contracted and self.world > 1:
+            raise NotImplementedError('data-parallel training of DirectContractedVoxGO is not built: train it on one GPU')
         self.decay_factor = 0.1 ** (1 / (cfg_train['lrate_decay'] * 1000))
         self._small = [p for n, p in model.named_parameters() if n not in ('density', 'k0') and p.requires_grad]
 
@@ -383,7 +401,7 @@ class TrainStep:
         cfg, model = self.cfg, self.model
         density, k0 = getattr(model, 'density', None), getattr(model, 'k0', None)
         tv = (cfg['weight_tv_density'] > 0 or cfg['weight_tv_k0'] > 0) and cfg['tv_before'] > cfg['tv_after']
-        return bool(self.world == 1 and self.fused_loss and self.rows_adam and not tv and not self.k0_idle
+        return bool(self.world == 1 and self.fused_loss and self.rows_adam and not tv and not self.k0_idle and not self.contracted
                     and isinstance(self.optimizer, MaskedAdam) and isinstance(density, nn.Parameter) and density.is_cuda
                     and hasattr(model, 'can_keep_count_on_device') and model.can_keep_count_on_device()
                     and self.optimizer.can_fuse_grid_step(density, k0) and self.optimizer.per_lr is None)
@@ -462,7 +480,7 @@ class TrainStep:
         density, k0 = getattr(model, 'density', None), getattr(model, 'k0', None)
         # may the march's brick scatter apply the grid update itself?  One GPU: from its own tiles.  Data parallel: from the
         # all-reduced tiles of the bricks any rank touched (fused.brick_union) while that union stays small.
-        own = (self.rows_adam and not tv_now and not self.k0_idle and isinstance(self.optimizer, MaskedAdam)
+        own = (self.rows_adam and not tv_now and not self.k0_idle and not self.contracted and isinstance(self.optimizer, MaskedAdam)
                and isinstance(density, nn.Parameter) and isinstance(k0, nn.Parameter) and density.is_cuda)
         fuse_adam = own and self.optimizer.can_fuse_grid_step(density, k0)
         dp_bricks = bool(fuse_adam and self.world > 1 and self.brick_sparse and getattr(model, 'fused', False))
@@ -473,6 +491,9 @@ class TrainStep:
             self.optimizer.zero_grad(set_to_none=True)
             loss_fn = fused_render_loss if (self.fused_loss and res['rgb_marched'].is_cuda) else render_loss
             loss = loss_fn(res, target, n_global, cfg)
+            dist_loss = distortion_term(res, n_global, cfg) if loss_fn is fused_render_loss else None
+            if dist_loss is not None:
+                loss = loss + dist_loss
             if self.track_mse:
                 self.last_mse = cfg['weight_main'] * (res['rgb_marched'].detach() - target).pow(2).sum() / (3 * n_global)
             tiles = bool(dp_bricks and bu.sparse)      # identical on every rank: decided from the all-reduced brick counts

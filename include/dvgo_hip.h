@@ -38,8 +38,9 @@ extern "C" {
 #define DVGO_EINVAL (-1)   /* invalid argument (null pointer, negative size, bad stride) */
 #define DVGO_ERANGE (-2)   /* size exceeds what the kernel's 32-bit indexing supports    */
 
-/* version of this ABI; bumped on any signature change (6: the positional-encoding colour head) */
-#define DVGO_ABI_VERSION 6
+/* version of this ABI; bumped on any signature change (6: the positional-encoding colour head; 7: the contracted
+ * sampler and the distortion loss of unbounded scenes) */
+#define DVGO_ABI_VERSION 7
 int dvgo_abi_version(void);
 
 /* Kernel-variant selection for A/B measurements (process-global; defaults are the fastest
@@ -586,6 +587,34 @@ int dvgo_mesh_count(const float* field, int Px, int Py, int Pz, float iso, uint8
 int dvgo_mesh_emit(const float* field, const uint8_t* edge_mask, const uint32_t* bases, int Px, int Py, int Pz,
                    float iso, const float* box_min, const float* spacing, int64_t n_verts, int64_t n_faces,
                    float* verts, float* normals, int32_t* faces, void* stream);
+
+/* ---------------------------------------------------------------------------------
+ * Unbounded scenes (csrc/contract.hip).  Per ray, in float32:
+ *   o' = (o - center) / radius, u = d / radius, d' = u / ||u||_2, p_k = o' + d' * t_tab[k] (k < n_max),
+ *   n_k = max|p_k| (l2 == 0) or ||p_k||_2 (l2 != 0), q_k = p_k if n_k <= 1 else p_k / n_k * ((1 + b) - b / n_k),
+ *   kept when (n_k <= 1 or acc > thres after acc += ||q_k - q_{k-1}||_2, acc reset to 0 on keep) and the
+ *   occupancy mask [mi, mj, mk] (NULL: all occupied) holds at q_k (maskcache_lookup's rounding).
+ * dvgo_contract_count: counts [n_rays] int32 = kept samples per ray.
+ * dvgo_contract_emit:  offsets [n_rays + 1] = dvgo_exclusive_scan_i32(counts); writes the kept samples ray-major,
+ *   step-ascending: q [M, 3], ray_id [M], step_id [M] (= k), t [M] (= t_tab[k]).
+ * center, radius: device float[3].  thres = (2 + 2b) / W * stepsize * 0.95.
+ * dvgo_distortion_fwd_bwd: w, s [m] of ray-sorted samples (ray_id [m] in [0, n_rays)), delta = 1 / n_max,
+ *   loss = (1/n_norm) sum_rays [2 sum_i w_i (s_i W_<i - S_<i) + delta/3 sum_i w_i^2], grad [m] = dloss/dw.
+ *   partials: double [ceil(n_rays / 256)] scratch; ticket: one uint32 that must be 0 on entry.
+ *   Deterministic: fixed-order reductions, no float atomics.
+ * --------------------------------------------------------------------------------- */
+int dvgo_contract_count(const float* rays_o, const float* rays_d, int64_t n_rays, const float* center,
+                        const float* radius, const float* t_tab, int n_max, float bg_len, int l2, float thres,
+                        const uint8_t* mask, int mi, int mj, int mk, const float* mask_scale,
+                        const float* mask_shift, int32_t* counts, void* stream);
+int dvgo_contract_emit(const float* rays_o, const float* rays_d, int64_t n_rays, const float* center,
+                       const float* radius, const float* t_tab, int n_max, float bg_len, int l2, float thres,
+                       const uint8_t* mask, int mi, int mj, int mk, const float* mask_scale, const float* mask_shift,
+                       const int64_t* offsets, float* q, int64_t* ray_id, int64_t* step_id, float* t,
+                       void* stream);
+int dvgo_distortion_fwd_bwd(const float* w, const float* s, const int64_t* ray_id, int64_t m, int64_t n_rays,
+                            int64_t n_norm, int n_max, float* grad, double* partials, unsigned int* ticket,
+                            float* loss, void* stream);
 
 #ifdef __cplusplus
 }
