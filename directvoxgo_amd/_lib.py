@@ -6,6 +6,7 @@ with the reference's own error text (lib/cuda/render_utils.cpp:40-42).
 """
 import ctypes
 import os
+import re
 
 import torch
 
@@ -13,36 +14,97 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # DVGO_HIP_SO: another build of the same library (kernel A/B runs, tools/)
 SO_PATH = os.environ.get('DVGO_HIP_SO') or os.path.join(_HERE, 'csrc', 'libdvgo_hip.so')
 ABI_VERSION = 7
+# the declarations the boundary is typed from (checkout layout: include/ beside the package)
+HEADER_PATH = os.path.join(os.path.dirname(_HERE), 'include', 'dvgo_hip.h')
 
 _lib = None
+_nargs = {}          # entry point -> declared parameter count (`call` compares before anything reaches the device)
 
 
 class _Rec2(ctypes.Structure):
     _fields_ = [('step', ctypes.c_int32), ('exp_d', ctypes.c_float), ('alpha', ctypes.c_float), ('T', ctypes.c_float)]
 
 
+_vp = ctypes.c_void_p
+_i64 = ctypes.c_int64
+_int = ctypes.c_int
+_flt = ctypes.c_float
+
+
+class _Pointer(ctypes.c_void_p):
+    """The parameter type of every pointer of the header.  A tensor is converted to its address inside the foreign call,
+    while the argument tuple keeps it alive: call sites pass tensors, never addresses formed earlier."""
+
+    @staticmethod
+    def from_param(x):
+        if x is None or type(x) is _vp:                  # NULL; a hand-made pointer or a raw stream handle
+            return x
+        if isinstance(x, torch.Tensor):
+            return _vp(x.data_ptr())
+        if isinstance(x, (ctypes.Array, _vp)):           # host arrays: `f3`, the pointer tables of dvgo_copy_multi
+            return x
+        raise TypeError(f'expected a tensor, a ctypes array, a c_void_p or None, got {type(x).__name__}')
+
+
+_SCALARS = {'int': ctypes.c_int, 'int32_t': ctypes.c_int32, 'int64_t': ctypes.c_int64, 'float': ctypes.c_float,
+            'double': ctypes.c_double}
+
+
+def declarations(text):
+    """{name: (restype, [argtypes])} of every function a header declares.  Strict: after comments, preprocessor lines,
+    the record typedefs and the extern "C" braces are gone, every statement must be `int|int64_t dvgo_name(params)` and
+    every parameter a pointer or one of `_SCALARS`; anything else is an error, not a guess."""
+    text = re.sub(r'/\*.*?\*/', ' ', text, flags=re.S)
+    text = re.sub(r'^\s*#.*$', ' ', text, flags=re.M)
+    text = re.sub(r'typedef\s+struct\s*\{[^{}]*\}\s*\w+\s*;', ' ', text)
+    text = re.sub(r'extern\s+"C"\s*\{|^\s*\}\s*$', ' ', text, flags=re.M)
+    decls = {}
+    for stmt in filter(None, (' '.join(s.split()) for s in text.split(';'))):
+        m = re.fullmatch(r'(int|int64_t) (dvgo_\w+) ?\((.*)\)', stmt)
+        if m is None or m.group(2) in decls:
+            raise RuntimeError(f'dvgo_hip.h: cannot read the declaration `{stmt}`')
+        argtypes = []
+        for param in ([] if m.group(3).strip() == 'void' else m.group(3).split(',')):
+            if re.fullmatch(r'\s*(const )?(unsigned )?\w+ ?\*( ?const ?\*)? ?\w+\s*', param):
+                argtypes.append(_Pointer)
+                continue
+            words = param.split()
+            if len(words) != 2 or words[0] not in _SCALARS or not words[1].isidentifier():
+                raise RuntimeError(f'dvgo_hip.h: {m.group(2)}: cannot read the parameter `{param.strip()}`')
+            argtypes.append(_SCALARS[words[0]])
+        decls[m.group(2)] = (_SCALARS[m.group(1)], argtypes)
+    return decls
+
+
 def lib():
-    """The loaded library; raises (loudly) when it has not been built."""
+    """The loaded library, every entry point typed from its declaration in include/dvgo_hip.h; raises (loudly) when it
+    has not been built."""
     global _lib
     if _lib is None:
         if not os.path.exists(SO_PATH):
             raise RuntimeError(
                 f'{SO_PATH} is missing: build it with `python -m directvoxgo_amd.build` '
                 '(hipcc --offload-arch=gfx950).  directvoxgo_amd has no CPU fallback.')
-        _lib = ctypes.CDLL(SO_PATH)
-        _lib.dvgo_abi_version.restype = ctypes.c_int
-        v = _lib.dvgo_abi_version()
+        if not os.path.exists(HEADER_PATH):
+            raise RuntimeError(f'{HEADER_PATH} is missing: the calls into libdvgo_hip.so are typed from it '
+                               '(run from a checkout: include/ beside directvoxgo_amd/)')
+        handle = ctypes.CDLL(SO_PATH)
+        handle.dvgo_abi_version.restype = ctypes.c_int
+        v = handle.dvgo_abi_version()
         if v != ABI_VERSION:
             raise RuntimeError(f'libdvgo_hip.so ABI {v} != expected {ABI_VERSION}: rebuild')
+        with open(HEADER_PATH) as f:
+            decls = declarations(f.read())
+        for name, (restype, argtypes) in decls.items():
+            fn = getattr(handle, name, None)
+            if fn is None:
+                raise RuntimeError(f'{SO_PATH} does not export {name}, which include/dvgo_hip.h declares: rebuild')
+            fn.restype, fn.argtypes = restype, argtypes
+            _nargs[name] = len(argtypes)
         if os.environ.get('DVGO_SHADE_VARIANT'):          # A/B runs (tools/): colour-head kernel variant bits
-            _lib.dvgo_shade_variant(int(os.environ['DVGO_SHADE_VARIANT']))
+            handle.dvgo_shade_variant(int(os.environ['DVGO_SHADE_VARIANT']))
+        _lib = handle
     return _lib
-
-
-_vp = ctypes.c_void_p
-_i64 = ctypes.c_int64
-_int = ctypes.c_int
-_flt = ctypes.c_float
 
 
 def check_input(x, name):
@@ -110,7 +172,10 @@ def profile_stop():
 
 
 def call(name, *args):
-    fn = getattr(lib(), name)
+    handle = lib()
+    if len(args) != _nargs.get(name):                    # (ctypes itself lets surplus arguments through)
+        raise TypeError(f'{name}: {len(args)} arguments given, include/dvgo_hip.h declares {_nargs.get(name, "no such function")}')
+    fn = getattr(handle, name)
     if _profile is not None and name in _profile:
         a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         a.record()

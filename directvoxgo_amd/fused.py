@@ -13,13 +13,12 @@ Two autograd Functions wrap the kernels of csrc/march.hip:
 One host sync per forward (the survivor count M3, needed to size the outputs); the reference
 needs five.
 """
-import ctypes
 import math
 
 import torch
 
 from . import _lib as L
-from ._lib import _flt, _i64, _int, check_f32, check_input, f3, ptr, stream_of
+from ._lib import check_f32, check_input, f3, stream_of
 from .ops import _grid_geom
 
 # scratch budget for fixed-stride records (16 B per potential sample)
@@ -91,7 +90,7 @@ COMBINED_MIN_RATIO = 6          # use it when kept samples * ratio >= voxels (te
 class grid_rows_capture:
     """Context manager for a training step that owns the optimizer: inside it the march backward does NOT produce
     `k0.grad` / `density.grad` (those two stay `None`).  Either
-      * `adam` is given (a callable returning the argument tail of dvgo_brick_accumulate, see
+      * `adam` is given (a callable returning the Adam argument group of dvgo_brick_accumulate, see
         `MaskedAdam.grid_step_args`) and the brick scatter applies the masked Adam update of both grids in place, from
         the brick's gradient tile in LDS -- the gradient never exists in memory (`.stepped` is set); or
       * the atomic scatter into combined gradient rows hands them over (`.G`: [n_vox, 16] = 12 feature channels, the
@@ -145,8 +144,75 @@ def split_grid_rows(G, density, k0):
     gk = torch.empty_like(k0, memory_format=torch.preserve_format)
     gd = torch.empty_like(density)
     with L.device_of(G):
-        L.call('dvgo_grid_grad_split', ptr(G), _i64(density.numel()), _int(16), _int(k0.shape[1]), ptr(gk), ptr(gd), stream_of(G))
+        L.call('dvgo_grid_grad_split', G, density.numel(), 16, k0.shape[1], gk, gd, stream_of(G))
     return gd, gk
+
+
+class _BrickPlan:
+    """The brick tables of one forward (csrc/brick.hip), from the counting in march_density to the backward that consumes
+    them; `ctx.plan` of _FusedMarch.  `n_bricks == 0`: no brick scatter for this forward, every table is None.
+      counts [n_bricks] samples per brick; offsets [n_bricks + 1] list offsets (offsets[-1]: the list total);
+      cursor [n_bricks] fill cursors of march_density_bwd (consumed: one backward per forward);
+      heavy bricks, else None and slice_len == n_extra_max == 0: extra_off [n_bricks + 1] extra work items, active
+      [n_bricks + 1] the non-empty bricks, extra_brick [n_extra_max] the brick of each extra item, arrive = `counts`,
+      which the scan clears into the slices' arrival counters.
+    n_entries: the list total (or its bound) once the forward has learnt it."""
+
+    def __init__(self, want_grads, density, k0, n_rays, cap):
+        C, X, Y, Z, sC, sX, sY, sZ = _grid_geom(k0)
+        self.n_bricks = self.slice_len = self.n_extra_max = self.n_entries = 0
+        self.counts = self.offsets = self.cursor = self.extra_off = self.active = self.extra_brick = self.arrive = None
+        # training: count, per 8^3 brick, the samples the backward will list for it
+        if not (BRICK_SCATTER and want_grads[0] and want_grads[1] and C in BRICK_CHANNELS
+                and tuple(density.shape[2:]) == (X, Y, Z) and (sC, sZ, sY, sX) == (1, C, Z * C, Y * Z * C)
+                and k0.data_ptr() % 16 == 0 and n_rays > 0 and 8 * cap < 1 << 31):       # int32 list offsets
+            return
+        dev = density.device
+        nb = self.n_bricks = L.lib().dvgo_n_bricks(X, Y, Z)
+        self.counts = torch.zeros(nb, dtype=torch.int32, device=dev)
+        tabs = torch.empty((3, nb + 1), dtype=torch.int32, device=dev)    # list offsets, extra items, non-empty bricks
+        self.offsets = tabs[0]
+        self.cursor = torch.empty(nb, dtype=torch.int32, device=dev)
+        # heavy bricks: extra work items <= entries / slice, entries <= 8 per record slot.  The packed scan of
+        # csrc/scan.h has 28 bits for entries and 18 each for extra items and non-empty bricks: beyond that
+        # (render-sized batches, 512^3 grids) every brick runs as one workgroup (ADVICE r2)
+        sl = BRICK_SLICE or L.lib().dvgo_brick_slice()
+        if 8 * cap < 1 << 28 and nb < 1 << 18 and 8 * max(cap, 1) // sl < 1 << 18:
+            self.slice_len = sl
+            self.n_extra_max = 8 * max(cap, 1) // sl
+            self.extra_off, self.active, self.arrive = tabs[1], tabs[2], self.counts
+            self.extra_brick = torch.empty(max(self.n_extra_max, 1), dtype=torch.int32, device=dev)
+
+
+def _scans(plan, n3, N, off3, tail, union, list_total, st):
+    """Every scan between march_density and march_gather: n3 -> off3 (per-ray offsets), the plan's counts -> its tables and,
+    data parallel (`union` = the all-reduce of the counts, in flight), the union's counts -> the table of the bricks any
+    rank touched, which is returned.  `list_total`: the host is about to read off3[N + 1], the plan's list total."""
+    nb = plan.n_bricks
+    if tail:
+        pass                        # the last workgroup of march_density has written off3 and the brick tables
+    elif N <= 16384:                # both scans in one launch (one workgroup each)
+        L.call('dvgo_march_scans', n3, N, off3, plan.counts, nb, plan.offsets, plan.cursor, plan.extra_off, plan.active,
+               plan.extra_brick, plan.n_extra_max, plan.slice_len, st)
+    else:                           # render-sized batches: the multi-workgroup scan
+        L.call('dvgo_exclusive_scan_i32', n3, N, off3, st)
+        if nb:
+            L.call('dvgo_brick_scan', plan.counts, nb, plan.offsets, plan.cursor, plan.extra_off, plan.active,
+                   plan.extra_brick, plan.n_extra_max, plan.slice_len, st)
+    union_active = None
+    if union is not None:
+        union_cnt, work = union
+        work.wait()
+        tabs = torch.empty((4, nb + 1), dtype=torch.int32, device=n3.device)     # off, cursor, extra, active
+        L.call('dvgo_brick_scan', union_cnt, nb, tabs[0], tabs[1], tabs[2], tabs[3], tabs[1], 0, 1 << 30, st)
+        union_active = tabs[3]
+    if list_total and nb and N > 16384:         # (the multi-workgroup scan path does not write the list total)
+        off3[N + 1] = plan.offsets[-1]
+    return union_active
+
+
+# the Adam group of dvgo_brick_accumulate (p_k0 .. step_sizes_dev) when the launch applies no update
+_NO_ADAM = (None, None, None, 0.0, 0, None, None, None, 0.0, 0, 0.0, 0.0, 0.0, None)
 
 
 class _FusedMarch(torch.autograd.Function):
@@ -185,92 +251,42 @@ class _FusedMarch(torch.autograd.Function):
             if not ndc and not setup_in_march:
                 t_min = torch.empty(N, dtype=torch.float32, device=dev)
                 t_max = torch.empty_like(t_min)
-                L.call('dvgo_sample_pts_prepare', ptr(rays_o), ptr(rays_d), ptr(cfg.xyz_min_t), ptr(cfg.xyz_max_t),
-                       _flt(cfg.near), _flt(cfg.far), _flt(cfg.stepdist), _i64(N), ptr(t_min), ptr(t_max),
-                       ptr(n_steps), ptr(cum), ptr(start), ptr(dirs), st)
+                L.call('dvgo_sample_pts_prepare', rays_o, rays_d, cfg.xyz_min_t, cfg.xyz_max_t, cfg.near, cfg.far,
+                       cfg.stepdist, N, t_min, t_max, n_steps, cum, start, dirs, st)
             if stride == 0:
                 cap = int(cum[-1].item()) if N > 0 else 0     # exact layout: one extra host read
             else:
                 cap = stride * N
             rec2 = torch.empty((max(cap, 1), 4), dtype=torch.float32, device=dev)
-            # training: count, per 8^3 brick, the samples the backward will list for it (csrc/brick.hip)
-            bricks = (BRICK_SCATTER and ctx.needs_input_grad[0] and ctx.needs_input_grad[1] and C in BRICK_CHANNELS
-                      and tuple(density.shape[2:]) == (X, Y, Z) and (sC, sZ, sY, sX) == (1, C, Z * C, Y * Z * C)
-                      and k0.data_ptr() % 16 == 0 and N > 0 and 8 * cap < 1 << 31)       # int32 list offsets
-            brick_cnt = brick_off = brick_cur = extra_brick = None
-            n_extra_max = slice_len = 0
-            if bricks:
-                nb = L.lib().dvgo_n_bricks(X, Y, Z)
-                brick_cnt = torch.zeros(nb, dtype=torch.int32, device=dev)
-                brick_off = torch.empty((3, nb + 1), dtype=torch.int32, device=dev)    # list offsets, extra items, non-empty bricks
-                brick_cur = torch.empty(nb, dtype=torch.int32, device=dev)
-                # heavy bricks: extra work items <= entries / slice, entries <= 8 per record slot.  The packed scan of
-                # csrc/scan.h has 28 bits for entries and 18 each for extra items and non-empty bricks: beyond that
-                # (render-sized batches, 512^3 grids) every brick runs as one workgroup
-                sl = BRICK_SLICE or L.lib().dvgo_brick_slice()
-                if 8 * cap < 1 << 28 and nb < 1 << 18 and 8 * max(cap, 1) // sl < 1 << 18:
-                    slice_len = sl
-                    n_extra_max = 8 * max(cap, 1) // slice_len
-                    extra_brick = torch.empty(max(n_extra_max, 1), dtype=torch.int32, device=dev)
+            plan = _BrickPlan(ctx.needs_input_grad, density, k0, N, cap)
             mask = cfg.mask
             mshape = mask.shape if mask is not None else (0, 0, 0)
             tail = TAIL_SCANS and 0 < N <= 16384          # the scans ride on march_density's last workgroup
-            L.call('dvgo_march_density', ptr(start), ptr(dirs), ptr(n_steps), ptr(cum), _i64(stride), _i64(N),
-                   cfg.xyz_min_h, cfg.xyz_max_h, _flt(cfg.stepdist), ptr(mask), _int(mshape[0]), _int(mshape[1]),
-                   _int(mshape[2]), cfg.scale_h, cfg.shift_h, ptr(density), _int(X), _int(Y), _int(Z),
-                   _flt(cfg.act_shift), _flt(cfg.interval), _flt(cfg.thres), ptr(rec2), ptr(n2), ptr(n3),
-                   ptr(last), ptr(brick_cnt), ptr(rays_o if setup_in_march else None), ptr(rays_d if setup_in_march else None),
-                   _flt(cfg.near), _flt(cfg.far), ptr(_tail_ticket(dev, st) if tail else None), ptr(off3),
-                   _int(nb if bricks else 0), ptr(brick_off[0] if bricks else None), ptr(brick_cur),
-                   ptr(brick_off[1] if extra_brick is not None else None),
-                   ptr(brick_off[2] if extra_brick is not None else None), ptr(extra_brick), _int(n_extra_max),
-                   _int(slice_len), st)
-            bu = brick_union._active if (bricks and extra_brick is not None and ctx.needs_input_grad[0]) else None
-            union_cnt = union_work = None
+            L.call('dvgo_march_density', start, dirs, n_steps, cum, stride, N, cfg.xyz_min_h, cfg.xyz_max_h, cfg.stepdist,
+                   mask, mshape[0], mshape[1], mshape[2], cfg.scale_h, cfg.shift_h, density, X, Y, Z, cfg.act_shift,
+                   cfg.interval, cfg.thres, rec2, n2, n3, last, plan.counts, rays_o if setup_in_march else None,
+                   rays_d if setup_in_march else None, cfg.near, cfg.far, _tail_ticket(dev, st) if tail else None, off3,
+                   plan.n_bricks, plan.offsets, plan.cursor, plan.extra_off, plan.active, plan.extra_brick,
+                   plan.n_extra_max, plan.slice_len, st)
+            bu = brick_union._active if (plan.extra_brick is not None and ctx.needs_input_grad[0]) else None
+            union = None
             if bu is not None:
                 import torch.distributed as dist
-                union_cnt = brick_cnt.clone()                       # (the local scan below clears the counters)
-                union_work = dist.all_reduce(union_cnt, op=dist.ReduceOp.SUM, group=bu.group, async_op=True)
-            n_entries = 0
-            if tail:
-                pass                    # the last workgroup of march_density has written off3 and the brick tables
-            elif N <= 16384:            # both scans in one launch (one workgroup each)
-                L.call('dvgo_march_scans', ptr(n3), _i64(N), ptr(off3), ptr(brick_cnt), _int(nb if bricks else 0),
-                       ptr(brick_off[0] if bricks else None), ptr(brick_cur),
-                       ptr(brick_off[1] if extra_brick is not None else None),
-                       ptr(brick_off[2] if extra_brick is not None else None), ptr(extra_brick), _int(n_extra_max),
-                       _int(slice_len), st)
-            else:                       # render-sized batches: the multi-workgroup scan
-                L.call('dvgo_exclusive_scan_i32', ptr(n3), _i64(N), ptr(off3), st)
-                if bricks:
-                    L.call('dvgo_brick_scan', ptr(brick_cnt), _int(nb), ptr(brick_off[0]), ptr(brick_cur),
-                           ptr(brick_off[1] if extra_brick is not None else None),
-                           ptr(brick_off[2] if extra_brick is not None else None), ptr(extra_brick), _int(n_extra_max),
-                           _int(slice_len), st)
-            union_tabs = None
-            if bu is not None:
-                union_work.wait()
-                union_tabs = torch.empty((4, nb + 1), dtype=torch.int32, device=dev)     # off, cursor, extra, active
-                L.call('dvgo_brick_scan', ptr(union_cnt), _int(nb), ptr(union_tabs[0]), ptr(union_tabs[1]), ptr(union_tabs[2]),
-                       ptr(union_tabs[3]), ptr(union_tabs[1]), _int(0), _int(1 << 30), st)
-            if capacity and stride > 0 and bricks:
-                # training step (train.py): the surviving-sample count stays on the device.  The outputs are sized by
-                # their upper bound -- every step of every ray -- and every consumer is handed off3[N] as a device
-                # pointer (`m_dev`): no host synchronisation in the forward at all.  Rows past the count are garbage.
+                union_cnt = plan.counts.clone()                     # (the local scan below clears the counters)
+                union = (union_cnt, dist.all_reduce(union_cnt, op=dist.ReduceOp.SUM, group=bu.group, async_op=True))
+            # training step (train.py): the surviving-sample count stays on the device.  The outputs are sized by
+            # their upper bound -- every step of every ray -- and every consumer is handed off3[N] as a device
+            # pointer (`m_dev`): no host synchronisation in the forward at all.  Rows past the count are garbage.
+            padded = bool(capacity and stride > 0 and plan.n_bricks)
+            union_active = _scans(plan, n3, N, off3, tail, union, not padded, st)
+            if padded:
                 M3 = stride * N
-                n_entries = 8 * M3                              # a sample touches at most 2 x 2 x 2 bricks
-            elif bricks and bu is not None:
-                if N > 16384:
-                    off3[N + 1] = brick_off[0, -1]
-                off3 = torch.cat((off3, union_tabs[3, -1:].long()))           # (data parallel: the union size rides along)
-                M3, n_entries, n_union = off3[N:N + 3].tolist()
-                off3 = off3[:N + 2]
-                bu.n_union, bu.n_bricks = n_union, nb
-                bu.sparse = n_union <= bu.max_frac * nb
-            elif bricks:
-                if N > 16384:                                   # (the multi-workgroup scan path does not write the list total)
-                    off3[N + 1] = brick_off[0, -1]
-                M3, n_entries = off3[N:N + 2].tolist()          # the one host sync: 16 contiguous bytes, no gather launch
+                plan.n_entries = 8 * M3                         # a sample touches at most 2 x 2 x 2 bricks
+            elif bu is not None:                                # (data parallel: the union size rides along)
+                M3, plan.n_entries, n_union = torch.cat((off3, union_active[-1:].long()))[N:N + 3].tolist()
+                bu.n_union, bu.n_bricks, bu.sparse = n_union, plan.n_bricks, n_union <= bu.max_frac * plan.n_bricks
+            elif plan.n_bricks:
+                M3, plan.n_entries = off3[N:N + 2].tolist()     # the one host sync: 16 contiguous bytes, no gather launch
             else:
                 M3 = int(off3[N].item())                       # the one host sync of the fused forward
             ray_id = torch.empty(M3, dtype=torch.int64, device=dev)
@@ -278,18 +294,16 @@ class _FusedMarch(torch.autograd.Function):
             weights = torch.empty(M3, dtype=torch.float32, device=dev)
             alpha = torch.empty(M3, dtype=torch.float32, device=dev)
             feat = torch.empty((M3, C), dtype=torch.float32, device=dev)
-            L.call('dvgo_march_gather', ptr(rec2), ptr(n2), ptr(n_steps), ptr(cum), _i64(stride), ptr(off3), _i64(N), _i64(M3),
-                   ptr(start), ptr(dirs), _flt(cfg.stepdist), cfg.xyz_min_h, cfg.xyz_max_h, ptr(k0), _int(C),
-                   _int(X), _int(Y), _int(Z), _i64(sC), _i64(sX), _i64(sY), _i64(sZ), ptr(ray_id), ptr(step_id),
-                   ptr(weights), ptr(alpha), ptr(feat), st)
+            L.call('dvgo_march_gather', rec2, n2, n_steps, cum, stride, off3, N, M3, start, dirs, cfg.stepdist, cfg.xyz_min_h,
+                   cfg.xyz_max_h, k0, C, X, Y, Z, sC, sX, sY, sZ, ray_id, step_id, weights, alpha, feat, st)
             if positions:              # the kept samples' positions in place of the (zero-channel) features
                 from .shade import march_positions
                 feat = march_positions(start, dirs, ray_id, step_id, cfg.stepdist)
         ctx.cfg = cfg
         ctx.geom = (X, Y, Z, C, sC, sX, sY, sZ, stride, N)
-        ctx.bricks = (brick_off, brick_cur, brick_cnt, extra_brick, slice_len, n_entries) if bricks else None
-        ctx.union = (bu, union_tabs[3], bu.n_union) if (bu is not None and bu.sparse) else None
-        ctx.padded = bool(capacity and stride > 0 and bricks)
+        ctx.plan = plan if plan.n_bricks else None
+        ctx.union = (bu, union_active, bu.n_union) if (bu is not None and bu.sparse) else None
+        ctx.padded = padded
         ctx.density_meta, ctx.k0_meta = density, k0
         ctx.save_for_backward(rec2, n2, n_steps, cum if cum is not None else n_steps, off3, start, dirs, last,
                               ray_id, step_id)
@@ -304,7 +318,6 @@ class _FusedMarch(torch.autograd.Function):
         rec2, n2, n_steps, cum, off3, start, dirs, last, ray_id, step_id = ctx.saved_tensors
         X, Y, Z, C, sC, sX, sY, sZ, stride, N = ctx.geom
         cfg = ctx.cfg
-        cum_p = ptr(cum) if stride == 0 else ptr(None)
         M3 = ray_id.shape[0]
         st = stream_of(start)
         grad_density = grad_k0 = None
@@ -318,68 +331,16 @@ class _FusedMarch(torch.autograd.Function):
                 gl = g_last.contiguous() if g_last is not None else None
 
             def density_bwd(dst, dst_stride, kept, cursor=None, recs=None):
-                L.call('dvgo_march_density_bwd', ptr(rec2), ptr(n2), ptr(n_steps), cum_p, _i64(stride), ptr(off3),
-                       _i64(N), ptr(start), ptr(dirs), _flt(cfg.stepdist), cfg.xyz_min_h, cfg.xyz_max_h, ptr(last),
-                       _flt(cfg.interval), ptr(gw), ptr(gl), _int(X), _int(Y), _int(Z), ptr(dst), _i64(dst_stride),
-                       ptr(kept), ptr(cursor), ptr(recs), st)
+                L.call('dvgo_march_density_bwd', rec2, n2, n_steps, cum if stride == 0 else None, stride, off3, N, start, dirs,
+                       cfg.stepdist, cfg.xyz_min_h, cfg.xyz_max_h, last, cfg.interval, gw, gl, X, Y, Z, dst, dst_stride, kept,
+                       cursor, recs, st)
 
-            if ctx.padded and not (ctx.bricks is not None and want_k0 and want_d and BRICK_SCATTER):
+            plan = ctx.plan if (want_k0 and want_d and BRICK_SCATTER) else None
+            if ctx.padded and plan is None:
                 raise RuntimeError('capacity-mode forward (device-side sample count) needs the brick scatter backward for both grids')
-            if ctx.bricks is not None and want_k0 and want_d and BRICK_SCATTER:
-                # owner-computes scatter: list every sample per brick, then one workgroup sums each brick
-                brick_off, brick_cur, arrive, extra_brick, slice_len, E = ctx.bricks
-                ctx.bricks = None                               # the fill cursors are consumed: one backward per forward
-                recs = torch.empty((max(E, 1), 4), dtype=torch.int32, device=dev)
-                density_bwd(None, 1, None, brick_cur, recs)
-                g_feat = g_feat.contiguous()
-                # heavy bricks run as several work items (slices of the list) that meet in scratch tiles
-                if extra_brick is not None:
-                    n_extra_max = min(extra_brick.shape[0], E // slice_len)
-                    tiles = torch.empty((2 * n_extra_max + 1, 512 * ((C + 4) // 4 * 4)), dtype=torch.float32, device=dev)
-                    items = (ptr(brick_off[0]), ptr(brick_off[1]), ptr(brick_off[2]), ptr(extra_brick), ptr(arrive),
-                             ptr(tiles), _i64(n_extra_max), _int(slice_len))
-                else:
-                    items = (ptr(brick_off[0]), ptr(None), ptr(None), ptr(None), ptr(None), ptr(None), _i64(0), _int(0))
-                cap = grid_rows_capture._active
-                fuse = (cap is not None and cap.adam is not None and not cap.stepped and cap.density is ctx.density_meta
-                        and cap.k0 is ctx.k0_meta)
-                if fuse and ctx.union is not None:
-                    # data parallel, sparse scene: tiles of the bricks any rank touched -> one all-reduce -> the same masked
-                    # Adam update from the summed tiles on every rank
-                    import torch.distributed as dist
-                    bu, active_u, n_union = ctx.union
-                    TS = (C + 4) // 4 * 4
-                    tiles = torch.empty((max(n_union, 1), 512 * TS), dtype=torch.float32, device=dev)
-                    items_u = (items[0], items[1], ptr(active_u)) + items[3:]
-                    nulls = (ptr(None), ptr(None), ptr(None), _flt(0), _int(0), ptr(None), ptr(None), ptr(None), _flt(0), _int(0),
-                             _flt(0), _flt(0), _flt(0), ptr(None))
-                    L.call('dvgo_brick_accumulate', *items_u, ptr(recs), ptr(start), ptr(dirs), _flt(cfg.stepdist),
-                           cfg.xyz_min_h, cfg.xyz_max_h, ptr(g_feat), _int(C), _int(X), _int(Y), _int(Z), ptr(None), ptr(None),
-                           *nulls, ptr(tiles), _int(2), st)
-                    if n_union > 0:
-                        dist.all_reduce(tiles[:n_union], op=dist.ReduceOp.SUM, group=bu.group)
-                    bu.bytes_on_wire = n_union * 512 * TS * 4
-                    tail = cap.adam()
-                    L.call('dvgo_brick_accumulate', *items_u, ptr(None), ptr(None), ptr(None), _flt(cfg.stepdist),
-                           cfg.xyz_min_h, cfg.xyz_max_h, ptr(None), _int(C), _int(X), _int(Y), _int(Z), ptr(None), ptr(None),
-                           *tail, ptr(tiles), _int(3), st)
-                    cap.stepped = True
-                    return None, None, None, None, None, None, None
-                if fuse and brick_union._active is None:
-                    tail = cap.adam()
-                    L.call('dvgo_brick_accumulate', *items, ptr(recs), ptr(start), ptr(dirs), _flt(cfg.stepdist),
-                           cfg.xyz_min_h, cfg.xyz_max_h, ptr(g_feat), _int(C), _int(X), _int(Y), _int(Z), ptr(None), ptr(None),
-                           *tail, ptr(None), _int(0), st)
-                    cap.stepped = True
-                    return None, None, None, None, None, None, None
-                grad_k0 = torch.empty_like(ctx.k0_meta, memory_format=torch.preserve_format)
-                grad_density = torch.empty_like(ctx.density_meta)
-                assert grad_k0.stride() == ctx.k0_meta.stride() and grad_density.is_contiguous()
-                L.call('dvgo_brick_accumulate', *items, ptr(recs), ptr(start), ptr(dirs), _flt(cfg.stepdist),
-                       cfg.xyz_min_h, cfg.xyz_max_h, ptr(g_feat), _int(C), _int(X), _int(Y), _int(Z), ptr(grad_k0),
-                       ptr(grad_density), ptr(None), ptr(None), ptr(None), _flt(0), _int(0),
-                       ptr(None), ptr(None), ptr(None), _flt(0), _int(0), _flt(0), _flt(0), _flt(0), ptr(None), ptr(None), _int(0), st)
-                return grad_density, grad_k0, None, None, None, None, None
+            if plan is not None:
+                ctx.plan = None                                 # the fill cursors are consumed: one backward per forward
+                return _brick_backward(ctx, plan, density_bwd, g_feat, start, dirs, st) + (None,) * 5
 
             # worth its two extra full-grid passes (zero 64 B, split 116 B per voxel) from ~1 kept sample per 6 voxels
             combined = (COMBINED_GRID_GRAD and want_k0 and want_d and C == 12 and M3 * COMBINED_MIN_RATIO >= X * Y * Z and tuple(ctx.density_meta.shape[2:]) == (X, Y, Z)
@@ -390,9 +351,8 @@ class _FusedMarch(torch.autograd.Function):
                 G = torch.zeros((X * Y * Z, 16), dtype=torch.float32, device=dev)
                 kept = torch.empty(M3, dtype=torch.float32, device=dev)
                 density_bwd(G[:, 12:], 16, kept)
-                L.call('dvgo_march_feat_bwd', ptr(g_feat.contiguous()), ptr(kept), ptr(ray_id), ptr(step_id), _i64(M3),
-                       ptr(start), ptr(dirs), _flt(cfg.stepdist), cfg.xyz_min_h, cfg.xyz_max_h, _int(C), _int(X),
-                       _int(Y), _int(Z), _i64(1), _i64(Y * Z * 16), _i64(Z * 16), _i64(16), ptr(G), st)
+                L.call('dvgo_march_feat_bwd', g_feat.contiguous(), kept, ray_id, step_id, M3, start, dirs, cfg.stepdist,
+                       cfg.xyz_min_h, cfg.xyz_max_h, C, X, Y, Z, 1, Y * Z * 16, Z * 16, 16, G, st)
                 cap = grid_rows_capture._active
                 if cap is not None and cap.G is None and cap.density is ctx.density_meta and cap.k0 is ctx.k0_meta:
                     cap.G = G                  # the optimizer consumes the rows; no dense gradients are produced
@@ -400,19 +360,66 @@ class _FusedMarch(torch.autograd.Function):
                 grad_k0 = torch.empty_like(ctx.k0_meta, memory_format=torch.preserve_format)
                 grad_density = torch.empty_like(ctx.density_meta)
                 assert grad_k0.stride() == ctx.k0_meta.stride() and grad_density.is_contiguous()
-                L.call('dvgo_grid_grad_split', ptr(G), _i64(X * Y * Z), _int(16), _int(C), ptr(grad_k0),
-                       ptr(grad_density), st)
+                L.call('dvgo_grid_grad_split', G, X * Y * Z, 16, C, grad_k0, grad_density, st)
             else:
                 if want_k0:
                     grad_k0 = torch.zeros_like(ctx.k0_meta, memory_format=torch.preserve_format)
                     assert grad_k0.stride() == ctx.k0_meta.stride()
-                    L.call('dvgo_march_feat_bwd', ptr(g_feat.contiguous()), ptr(None), ptr(ray_id), ptr(step_id),
-                           _i64(M3), ptr(start), ptr(dirs), _flt(cfg.stepdist), cfg.xyz_min_h, cfg.xyz_max_h, _int(C),
-                           _int(X), _int(Y), _int(Z), _i64(sC), _i64(sX), _i64(sY), _i64(sZ), ptr(grad_k0), st)
+                    L.call('dvgo_march_feat_bwd', g_feat.contiguous(), None, ray_id, step_id, M3, start, dirs, cfg.stepdist,
+                           cfg.xyz_min_h, cfg.xyz_max_h, C, X, Y, Z, sC, sX, sY, sZ, grad_k0, st)
                 if want_d:
                     grad_density = torch.zeros_like(ctx.density_meta)
                     density_bwd(grad_density, 1, None)
         return grad_density, grad_k0, None, None, None, None, None
+
+
+def _brick_backward(ctx, plan, density_bwd, g_feat, start, dirs, st):
+    """Owner-computes scatter: list every sample per brick, then one workgroup sums each brick.  -> (density.grad, k0.grad),
+    both None when the scatter applied the optimizer's update itself (grid_rows_capture.adam)."""
+    X, Y, Z, C = ctx.geom[:4]
+    dev = start.device
+    recs = torch.empty((max(plan.n_entries, 1), 4), dtype=torch.int32, device=dev)
+    density_bwd(None, 1, None, plan.cursor, recs)
+    lists = (recs, start, dirs, g_feat.contiguous())
+    scratch, n_extra, cfg = None, 0, ctx.cfg
+    if plan.extra_brick is not None:        # heavy bricks run as several work items (slices of the list) that meet in scratch tiles
+        n_extra = min(plan.extra_brick.shape[0], plan.n_entries // plan.slice_len)
+        scratch = torch.empty((2 * n_extra + 1, 512 * ((C + 4) // 4 * 4)), dtype=torch.float32, device=dev)
+
+    def accumulate(lists, active=None, grad_k0=None, grad_density=None, adam=_NO_ADAM, tiles=None, mode=0):
+        """The one issuer of dvgo_brick_accumulate; the four modes are the calls below.  `lists`: None when the launch
+        reads tiles instead; `active`: the union's brick table in place of the plan's own; `adam`: grid_step_args."""
+        assert len(adam) == len(_NO_ADAM)
+        recs, start, dirs, g_feat = lists or (None, None, None, None)
+        L.call('dvgo_brick_accumulate', plan.offsets, plan.extra_off, active if active is not None else plan.active,
+               plan.extra_brick, plan.arrive, scratch, n_extra, plan.slice_len, recs, start, dirs, cfg.stepdist, cfg.xyz_min_h,
+               cfg.xyz_max_h, g_feat, C, X, Y, Z, grad_k0, grad_density, *adam, tiles, mode, st)
+
+    cap = grid_rows_capture._active
+    fuse = (cap is not None and cap.adam is not None and not cap.stepped and cap.density is ctx.density_meta
+            and cap.k0 is ctx.k0_meta)
+    if fuse and ctx.union is not None:
+        # data parallel, sparse scene: tiles of the bricks any rank touched -> one all-reduce -> the same masked
+        # Adam update from the summed tiles on every rank
+        import torch.distributed as dist
+        bu, union_active, n_union = ctx.union
+        TS = (C + 4) // 4 * 4
+        tiles = torch.empty((max(n_union, 1), 512 * TS), dtype=torch.float32, device=dev)
+        accumulate(lists, active=union_active, tiles=tiles, mode=2)
+        if n_union > 0:
+            dist.all_reduce(tiles[:n_union], op=dist.ReduceOp.SUM, group=bu.group)
+        bu.bytes_on_wire = n_union * 512 * TS * 4
+        accumulate(None, active=union_active, adam=cap.adam(), tiles=tiles, mode=3)
+    elif fuse and brick_union._active is None:
+        accumulate(lists, adam=cap.adam())
+    else:
+        grad_k0 = torch.empty_like(ctx.k0_meta, memory_format=torch.preserve_format)
+        grad_density = torch.empty_like(ctx.density_meta)
+        assert grad_k0.stride() == ctx.k0_meta.stride() and grad_density.is_contiguous()
+        accumulate(lists, grad_k0=grad_k0, grad_density=grad_density)
+        return grad_density, grad_k0
+    cap.stepped = True
+    return None, None
 
 
 @torch.no_grad()
@@ -432,12 +439,10 @@ def fused_hit(rays_o, rays_d, cfg):
     mask = cfg.mask
     with L.device_of(rays_o):
         st = stream_of(rays_o)
-        L.call('dvgo_sample_pts_prepare', ptr(rays_o), ptr(rays_d), ptr(cfg.xyz_min_t), ptr(cfg.xyz_max_t), _flt(cfg.near),
-               _flt(cfg.far), _flt(cfg.stepdist), _i64(N), ptr(t_min), ptr(t_max), ptr(n_steps), ptr(None), ptr(start),
-               ptr(dirs), st)
-        L.call('dvgo_march_hit', ptr(start), ptr(dirs), ptr(n_steps), _i64(N), cfg.xyz_min_h, cfg.xyz_max_h,
-               _flt(cfg.stepdist), ptr(mask), _int(mask.shape[0]), _int(mask.shape[1]), _int(mask.shape[2]), cfg.scale_h,
-               cfg.shift_h, ptr(hit), st)
+        L.call('dvgo_sample_pts_prepare', rays_o, rays_d, cfg.xyz_min_t, cfg.xyz_max_t, cfg.near, cfg.far, cfg.stepdist, N,
+               t_min, t_max, n_steps, None, start, dirs, st)
+        L.call('dvgo_march_hit', start, dirs, n_steps, N, cfg.xyz_min_h, cfg.xyz_max_h, cfg.stepdist, mask, mask.shape[0],
+               mask.shape[1], mask.shape[2], cfg.scale_h, cfg.shift_h, hit, st)
     return hit
 
 
@@ -460,15 +465,14 @@ class _Composite(torch.autograd.Function):
         last = alphainv_last.contiguous()
         out = torch.empty((N, 3), dtype=torch.float32, device=weights.device)
         with L.device_of(weights):
-            L.call('dvgo_march_composite', ptr(weights), ptr(rgb), ptr(None), ptr(off3), _i64(N),
-                   ptr(last), _flt(float(bg)), ptr(out), ptr(None), stream_of(weights))
+            L.call('dvgo_march_composite', weights, rgb, None, off3, N, last, float(bg), out, None, stream_of(weights))
         ctx.save_for_backward(weights, rgb, ray_id)
         ctx.bg = float(bg)
         ctx.N = N
         ctx.m_dev = m_dev
         # A loss that also consumes `rgb` / `alphainv_last` (run.py:381-385: rgbper, entropy) may leave its gradient of
         # them in `ctx.extra` instead of returning it to autograd (train._FusedLoss does, after checking these two
-        # pointers): the backward below then adds to it in place -- one gradient per tensor, no summation launches.
+        # addresses): the backward below then adds to it in place -- one gradient per tensor, no summation launches.
         ctx.rgb_ptr, ctx.last_ptr = rgb.data_ptr(), last.data_ptr()
         ctx.extra = None
         return out
@@ -478,31 +482,26 @@ class _Composite(torch.autograd.Function):
     def backward(ctx, g):
         weights, rgb, ray_id = ctx.saved_tensors
         g = g.contiguous()
-        M3 = weights.shape[0]
+        want_rgb, want_last = ctx.needs_input_grad[1], ctx.needs_input_grad[2]
+
+        def bwd(gw, grgb, glast, accumulate):
+            with L.device_of(weights):
+                L.call('dvgo_march_composite_bwd', g, weights, rgb, ray_id, weights.shape[0], ctx.m_dev, ctx.N, ctx.bg, gw,
+                       grgb, glast, accumulate, stream_of(weights))
+
         gw = torch.empty_like(weights) if ctx.needs_input_grad[0] else None
-        extra, ctx.extra = ctx.extra, None
-        if extra is not None:
-            grgb, glast = extra                      # the loss's gradients of rgb / alphainv_last (either may be None)
-            acc = 1
-            if (grgb is None and ctx.needs_input_grad[1]) or (glast is None and ctx.needs_input_grad[2]):
-                # only one of the two was handed over: finish the other the plain way, then add
-                g2 = torch.empty_like(rgb) if grgb is None and ctx.needs_input_grad[1] else None
-                l2 = torch.empty(ctx.N, dtype=torch.float32, device=g.device) if glast is None and ctx.needs_input_grad[2] else None
-                with L.device_of(weights):
-                    L.call('dvgo_march_composite_bwd', ptr(g), ptr(weights), ptr(rgb), ptr(ray_id), _i64(M3), ptr(ctx.m_dev),
-                           _i64(ctx.N), _flt(ctx.bg), ptr(None), ptr(g2), ptr(l2), _int(0), stream_of(weights))
-                with L.device_of(weights):
-                    L.call('dvgo_march_composite_bwd', ptr(g), ptr(weights), ptr(rgb), ptr(ray_id), _i64(M3), ptr(ctx.m_dev),
-                           _i64(ctx.N), _flt(ctx.bg), ptr(gw), ptr(grgb), ptr(glast), _int(1), stream_of(weights))
-                return gw, (grgb if grgb is not None else g2), (glast if glast is not None else l2), None, None, None, None
+        # the loss's gradients of rgb / alphainv_last (either may be None), to be added to; else fresh ones
+        (grgb, glast), accumulate = (ctx.extra, 1) if ctx.extra is not None else ((None, None), 0)
+        ctx.extra = None
+        g2 = torch.empty_like(rgb) if grgb is None and want_rgb else None
+        l2 = torch.empty(ctx.N, dtype=torch.float32, device=g.device) if glast is None and want_last else None
+        if not accumulate:
+            bwd(gw, g2, l2, 0)
         else:
-            grgb = torch.empty_like(rgb) if ctx.needs_input_grad[1] else None
-            glast = torch.empty(ctx.N, dtype=torch.float32, device=g.device) if ctx.needs_input_grad[2] else None
-            acc = 0
-        with L.device_of(weights):
-            L.call('dvgo_march_composite_bwd', ptr(g), ptr(weights), ptr(rgb), ptr(ray_id), _i64(M3), ptr(ctx.m_dev), _i64(ctx.N),
-                   _flt(ctx.bg), ptr(gw), ptr(grgb), ptr(glast), _int(acc), stream_of(weights))
-        return gw, grgb, glast, None, None, None, None
+            if g2 is not None or l2 is not None:    # only one of the two was handed over: finish the other the plain way
+                bwd(None, g2, l2, 0)
+            bwd(gw, grgb, glast, 1)
+        return gw, (grgb if grgb is not None else g2), (glast if glast is not None else l2), None, None, None, None
 
 
 def composite(weights, rgb, alphainv_last, ray_id, off3, bg, m_dev=None):
@@ -519,6 +518,6 @@ def composite_depth(weights, step_id, off3, n_rays):
     out = torch.empty((n_rays, 3), dtype=torch.float32, device=dev)
     depth = torch.empty(n_rays, dtype=torch.float32, device=dev)
     with L.device_of(weights):
-        L.call('dvgo_march_composite', ptr(weights.contiguous()), ptr(dummy_rgb), ptr(step_id), ptr(off3),
-               _i64(n_rays), ptr(zeros), _flt(0.0), ptr(out), ptr(depth), stream_of(weights))
+        L.call('dvgo_march_composite', weights.contiguous(), dummy_rgb, step_id, off3, n_rays, zeros, 0.0, out, depth,
+               stream_of(weights))
     return depth

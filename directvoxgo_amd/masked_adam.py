@@ -6,11 +6,13 @@ eps=1e-8) with (a) optional per-voxel learning rate for the parameter whose shap
 Dispatch order per-lr -> masked -> plain as at :60-71.  The bias-corrected step size is
 computed on the host in float32 exactly as lib/cuda/adam_upd_kernel.cu:72 does.
 """
+import ctypes
+
 import numpy as np
 import torch
 
 from . import _lib as L
-from ._lib import _flt, _i64, _int, ptr, stream_of
+from ._lib import stream_of
 
 
 def _dense_same_layout(*ts):
@@ -35,26 +37,24 @@ def adam_upd(param, grad, exp_avg, exp_avg_sq, step, beta1, beta2, lr, eps, mode
         raise RuntimeError('param, grad and optimizer state must share one memory layout')
     n = param.numel()
     with L.device_of(param):
-        L.call('dvgo_adam_upd', ptr(param), ptr(grad), ptr(exp_avg), ptr(exp_avg_sq), ptr(perlr if mode == 2 else None),
-               _i64(n), _flt(adam_step_size(lr, beta1, beta2, step)), _flt(beta1), _flt(beta2), _flt(eps), _int(mode),
-               stream_of(param))
+        L.call('dvgo_adam_upd', param, grad, exp_avg, exp_avg_sq, perlr if mode == 2 else None, n,
+               adam_step_size(lr, beta1, beta2, step), beta1, beta2, eps, mode, stream_of(param))
 
 
 def adam_upd_multi(items, step, beta1, beta2, lr, eps, step_size_dev=None):
     """Plain Adam over up to 16 small (param, state) pairs in one launch (csrc/loss.hip).  `step_size_dev`: a 1-element
     device float tensor holding the step size (captured steps), read instead of the host value."""
-    import ctypes
     n = len(items)
-    PT = ctypes.c_void_p * n
-    ps = PT(*[p.data_ptr() for p, _ in items])
-    gs = PT(*[p.grad.data_ptr() for p, _ in items])
-    ms = PT(*[st['exp_avg'].data_ptr() for _, st in items])
-    vs = PT(*[st['exp_avg_sq'].data_ptr() for _, st in items])
-    ne = (ctypes.c_int64 * n)(*[p.numel() for p, _ in items])
+
+    def table(tensors):          # host array of device addresses, formed in the call (`items` keeps the tensors alive)
+        return (ctypes.c_void_p * n)(*[t.data_ptr() for t in tensors])
+
     p0 = items[0][0]
     with L.device_of(p0):
-        L.call('dvgo_adam_upd_multi', ps, gs, ms, vs, ne, _int(n), _flt(adam_step_size(lr, beta1, beta2, step)), _flt(beta1),
-               _flt(beta2), _flt(eps), ptr(step_size_dev), stream_of(p0))
+        L.call('dvgo_adam_upd_multi', table(p for p, _ in items), table(p.grad for p, _ in items),
+               table(st['exp_avg'] for _, st in items), table(st['exp_avg_sq'] for _, st in items),
+               (ctypes.c_int64 * n)(*[p.numel() for p, _ in items]), n, adam_step_size(lr, beta1, beta2, step), beta1, beta2,
+               eps, step_size_dev, stream_of(p0))
 
 
 class MaskedAdam(torch.optim.Optimizer):
@@ -176,18 +176,19 @@ class MaskedAdam(torch.optim.Optimizer):
         self._hyper_fresh = True
 
     def grid_step_args(self, density, k0):
-        """Counts one step for both grids and returns the Adam argument tail of dvgo_brick_accumulate
-        (csrc/brick.hip): the update `step()` would make, applied by the scatter kernel from its LDS tile."""
+        """Counts one step for both grids and returns the Adam argument group of dvgo_brick_accumulate (p_k0 ..
+        step_sizes_dev: tensors and Python numbers, for `fused._brick_accumulate`): the update `step()` would make,
+        applied by the scatter kernel from its LDS tile (csrc/brick.hip)."""
         gd, gk = self._group_of(density), self._group_of(k0)
         sd, sk = self._state_of(density), self._state_of(k0)
         sd['step'] += 1
         sk['step'] += 1
         b1, b2 = gk['betas']
-        return (ptr(k0), ptr(sk['exp_avg']), ptr(sk['exp_avg_sq']), _flt(adam_step_size(gk['lr'], b1, b2, sk['step'])),
-                _int(1 if gk.get('skip_zero_grad', False) else 0),
-                ptr(density), ptr(sd['exp_avg']), ptr(sd['exp_avg_sq']), _flt(adam_step_size(gd['lr'], b1, b2, sd['step'])),
-                _int(1 if gd.get('skip_zero_grad', False) else 0), _flt(b1), _flt(b2), _flt(gk['eps']),
-                ptr(self.hyper_dev[0:2]) if (self.hyper_dev is not None and self._hyper_fresh) else ptr(None))
+        return (k0, sk['exp_avg'], sk['exp_avg_sq'], adam_step_size(gk['lr'], b1, b2, sk['step']),
+                1 if gk.get('skip_zero_grad', False) else 0,
+                density, sd['exp_avg'], sd['exp_avg_sq'], adam_step_size(gd['lr'], b1, b2, sd['step']),
+                1 if gd.get('skip_zero_grad', False) else 0, b1, b2, gk['eps'],
+                self.hyper_dev[0:2] if (self.hyper_dev is not None and self._hyper_fresh) else None)
 
     @torch.no_grad()
     def step_grid_rows(self, density, k0, G):
@@ -201,11 +202,11 @@ class MaskedAdam(torch.optim.Optimizer):
         n_vox = density.numel()
         assert G.shape == (n_vox, 16) and G.is_contiguous()
         with L.device_of(k0):
-            L.call('dvgo_adam_rows', ptr(G), _i64(n_vox), _int(16), _int(12), ptr(k0), ptr(sk['exp_avg']), ptr(sk['exp_avg_sq']),
-                   _flt(adam_step_size(gk['lr'], b1, b2, sk['step'])), _int(1 if gk.get('skip_zero_grad', False) else 0),
-                   ptr(density), ptr(sd['exp_avg']), ptr(sd['exp_avg_sq']),
-                   _flt(adam_step_size(gd['lr'], b1, b2, sd['step'])), _int(1 if gd.get('skip_zero_grad', False) else 0),
-                   _flt(b1), _flt(b2), _flt(gk['eps']), stream_of(k0))
+            L.call('dvgo_adam_rows', G, n_vox, 16, 12, k0, sk['exp_avg'], sk['exp_avg_sq'],
+                   adam_step_size(gk['lr'], b1, b2, sk['step']), 1 if gk.get('skip_zero_grad', False) else 0,
+                   density, sd['exp_avg'], sd['exp_avg_sq'],
+                   adam_step_size(gd['lr'], b1, b2, sd['step']), 1 if gd.get('skip_zero_grad', False) else 0,
+                   b1, b2, gk['eps'], stream_of(k0))
 
     @torch.no_grad()
     def step_shard(self, p, flat_p, flat_g, lo, hi):

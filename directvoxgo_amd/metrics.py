@@ -77,7 +77,6 @@ def image_metrics(img0, img1, max_val=1.0, filter_size=11, filter_sigma=1.5, k1=
     sse = torch.empty(n, dtype=torch.float64, device=a.device)
     smap = torch.empty((n, H - fs + 1, W - fs + 1, 3), dtype=torch.float32, device=a.device) if return_map else None
     lib = L.lib()
-    lib.dvgo_image_metrics_workspace_bytes.restype = ctypes.c_int64
     nbytes = lib.dvgo_image_metrics_workspace_bytes(_i64(n), _int(H), _int(W), _int(fs))
     if nbytes < 0:
         raise RuntimeError(f'dvgo_image_metrics_workspace_bytes failed: {L._ERR.get(nbytes, nbytes)}')

@@ -5,7 +5,6 @@
 kernel.  It applies to the reference's default head, Sequential(Linear, ReLU, Sequential(Linear, ReLU),
 Linear) with width 128 or 64; other shapes return None and the caller keeps the torch modules.
 """
-import ctypes
 
 import torch
 import torch.nn as nn
@@ -92,7 +91,6 @@ def _scratch(width, device):
     """Device scratch for the bf16-split kernels' weight image (csrc/shade_x3.hip): a fresh block per call from torch's
     caching allocator, so that calls on different streams never share one."""
     lib = L.lib()
-    lib.dvgo_shade_scratch_bytes.restype = ctypes.c_int64
     n = int(lib.dvgo_shade_scratch_bytes(int(width)))
     return torch.empty(n, dtype=torch.uint8, device=device) if n > 0 else None
 
@@ -252,7 +250,6 @@ class _ShadePosenc(torch.autograd.Function):
 
         def wgrad():
             lib = L.lib()
-            lib.dvgo_shade_pe_record_size.restype = ctypes.c_int64
             rec = int(lib.dvgo_shade_pe_record_size(width, d_in))
             n_parts = max(1, min(N_PARTS, (M + 31) // 32))
             part = torch.empty((n_parts, rec), dtype=torch.float32, device=pts.device)

@@ -15,11 +15,13 @@ reduction because both branch on ``grad != 0`` (total_variation_kernel.cu:21,
 adam_upd_kernel.cu:35) and must see the reduced gradient.
 """
 import contextlib
+import ctypes
 
 import torch
 import torch.distributed as dist
 import torch.nn as nn
 
+from . import _lib as L
 from .masked_adam import MaskedAdam
 from .fused import brick_union, grid_rows_capture, split_grid_rows
 from .shade import defer_wgrad
@@ -101,8 +103,6 @@ class _FusedLoss(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, rgb_marched, alphainv_last, raw_rgb, weights, ray_id, target, n_global, w_main, w_ent, w_per, m_dev=None):
-        from . import _lib as L
-        from ._lib import _flt, _i64, ptr, stream_of
         N, M = rgb_marched.shape[0], raw_rgb.shape[0]
         dev = rgb_marched.device
         rgb_marched, alphainv_last, raw_rgb = rgb_marched.contiguous(), alphainv_last.contiguous(), raw_rgb.contiguous()
@@ -111,9 +111,8 @@ class _FusedLoss(torch.autograd.Function):
         g_raw = torch.empty_like(raw_rgb) if w_per > 0 else None
         loss = torch.empty((), dtype=torch.float32, device=dev)
         with L.device_of(rgb_marched):
-            L.call('dvgo_loss_fwd_bwd', ptr(rgb_marched), ptr(alphainv_last), ptr(target.contiguous()), _i64(N), ptr(raw_rgb),
-                   ptr(weights.contiguous()), ptr(ray_id), _i64(M), ptr(m_dev), _i64(int(n_global)), _flt(w_main), _flt(w_ent),
-                   _flt(w_per), ptr(g_marched), ptr(g_last), ptr(g_raw), ptr(loss), stream_of(rgb_marched))
+            L.call('dvgo_loss_fwd_bwd', rgb_marched, alphainv_last, target.contiguous(), N, raw_rgb, weights.contiguous(), ray_id,
+                   M, m_dev, int(n_global), w_main, w_ent, w_per, g_marched, g_last, g_raw, loss, L.stream_of(rgb_marched))
         ctx.save_for_backward(g_marched, g_last, g_raw if g_raw is not None else g_last)
         ctx.has_raw = g_raw is not None
         # rgb_marched = composite(weights, raw_rgb, alphainv_last): the same two tensors reach the loss directly (rgbper,
@@ -444,13 +443,11 @@ class TrainStep:
     def _replay(self, rays_o, rays_d, viewdirs, target):
         srcs = (rays_o, rays_d, viewdirs, target)
         if all(t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.shape == d.shape for t, d in zip(srcs, self._static)):
-            import ctypes
-            from . import _lib as L
             n = len(srcs)                                   # the four inputs in one launch (csrc/loss.hip copy_multi)
             with L.device_of(rays_o):
                 L.call('dvgo_copy_multi', (ctypes.c_void_p * n)(*[d.data_ptr() for d in self._static]),
                        (ctypes.c_void_p * n)(*[t.data_ptr() for t in srcs]), (ctypes.c_int64 * n)(*[t.numel() for t in srcs]),
-                       ctypes.c_int(n), L.stream_of(rays_o))
+                       n, L.stream_of(rays_o))
         else:
             for dst, src in zip(self._static, srcs):
                 dst.copy_(src, non_blocking=True)

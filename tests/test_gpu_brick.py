@@ -162,9 +162,8 @@ def test_brick_lists_cover_every_sample_corner_exactly_once():
     sc, m = _model(23, 500)
     cfg = m._march_cfg(sc['near'], sc['far'], sc['stepsize'])
     w, alpha, last, feat, ray_id, step_id, off3 = F.fused_march(m.density, m.k0, sc['rays_o'], sc['rays_d'], cfg)
-    node = feat.grad_fn
-    brick_off, _, _, _, _, E = node.bricks
-    off = brick_off[0].cpu().numpy()
+    plan = feat.grad_fn.plan
+    off, E = plan.offsets.cpu().numpy(), plan.n_entries
     assert off[0] == 0 and off[-1] == E and np.all(np.diff(off) >= 0)
     assert E >= w.numel()                         # every kept sample is listed at least once (plus alpha-only ones)
 
@@ -192,7 +191,8 @@ def test_heavy_bricks_are_split_into_slices_that_meet_in_scratch_tiles(monkeypat
     # the lists really were sliced
     cfg = m._march_cfg(sc['near'], sc['far'], sc['stepsize'])
     w, alpha, last, feat, ray_id, step_id, off3 = F.fused_march(m.density, m.k0, sc['rays_o'], sc['rays_d'], cfg)
-    tables = feat.grad_fn.bricks[0].cpu().numpy()
+    plan = feat.grad_fn.plan
+    tables = [t.cpu().numpy() for t in (plan.offsets, plan.extra_off, plan.active)]
     counts = np.diff(tables[0])
     assert counts.max() > 2 * slice_len
     assert tables[1][-1] >= 2                                              # extra work items in use

@@ -41,7 +41,7 @@ def run(tag, brick, rows_adam):
         import numpy as np
         cfg = m._march_cfg(sc['near'], sc['far'], 0.5)
         out = F.fused_march(m.density, m.k0, sc['rays_o'], sc['rays_d'], cfg)
-        c = np.diff(out[3].grad_fn.bricks[0][0].cpu().numpy())
+        c = np.diff(out[3].grad_fn.plan.offsets.cpu().numpy())
         nz = c[c > 0]
         print('bricks', len(c), 'non-empty', len(nz), 'entries', int(c.sum()), 'percentiles 50/90/99/max',
               [int(np.percentile(nz, q)) for q in (50, 90, 99, 100)])
