@@ -156,16 +156,79 @@ def test_adam_fused_into_the_brick_kernel_equals_dense_gradients_plus_masked_ada
 
 
 def test_brick_lists_cover_every_sample_corner_exactly_once():
-    """Structure of the lists themselves: the number of entries equals the number of (sample, brick) incidences
-    computed independently on the host, for a lattice with partial bricks."""
-    from directvoxgo_amd import fused as F
-    sc, m = _model(23, 500)
-    cfg = m._march_cfg(sc['near'], sc['far'], sc['stepsize'])
-    w, alpha, last, feat, ray_id, step_id, off3 = F.fused_march(m.density, m.k0, sc['rays_o'], sc['rays_d'], cfg)
-    plan = feat.grad_fn.plan
-    off, E = plan.offsets.cpu().numpy(), plan.n_entries
-    assert off[0] == 0 and off[-1] == E and np.all(np.diff(off) >= 0)
-    assert E >= w.numel()                         # every kept sample is listed at least once (plus alpha-only ones)
+    """Structure of the lists themselves, for a lattice with partial bricks and for samples that mostly straddle brick
+    faces: for EVERY brick the multiset of (kept index, ray, step) in its list equals the (sample, brick) incidences
+    computed independently on the host (tests/brick_oracle.py `incidences`, pinned on hand-built cases by the host
+    test) -- each kept sample of the forward listed once by every brick that owns one of its in-range corners and by no
+    other.  Samples that passed the alpha filter only (kept index -1) are known to the host only through the lists: each
+    must be a sample no kept one is, and be listed by exactly its bricks.  The density gradient riding in the records
+    equals, bit for bit, what dvgo_march_density_bwd hands to `grad_kept` on the atomic path for the same forward."""
+    for world, stepsize in ((23, None), (64, 3.7)):
+        try:
+            _check_brick_lists(world, stepsize)
+        except AssertionError as e:
+            raise AssertionError(f'scene {world}^3, stepsize {stepsize or 0.5}: {e}') from e
+
+
+def _check_brick_lists(world, stepsize):
+    import brick_oracle as B
+    from directvoxgo_amd import _lib as L, fused as F
+    sc, m = _model(world, 500 if world == 23 else 4096, stepsize=stepsize or 0.5)
+    cfg = m._march_cfg(sc['near'], sc['far'], stepsize or sc['stepsize'])
+    X, Y, Z = m.k0.shape[2:]
+
+    def run(variant):
+        F.BRICK_SCATTER = variant == 'brick'
+        F.COMBINED_GRID_GRAD, F.COMBINED_MIN_RATIO = True, (6 if variant == 'brick' else 1e9)
+        seen, call = {}, L.call
+        def tap(name, *args):
+            call(name, *args)
+            if name == 'dvgo_march_density_bwd':
+                torch.cuda.synchronize()
+                kept = args[B.param_index('dvgo_march_density_bwd')['grad_kept']]        # by the header's name
+                seen['kept'] = None if kept is None else kept.detach().cpu().numpy().copy()
+        L.call = tap
+        try:
+            m.zero_grad(set_to_none=True)
+            w, alpha, last, feat, ray_id, step_id, off3 = F.fused_march(m.density, m.k0, sc['rays_o'], sc['rays_d'], cfg)
+            plan = feat.grad_fn.plan
+            gen = torch.Generator(device='cuda').manual_seed(2)
+            with B.LaunchSpy(check=False) as spy:
+                torch.autograd.backward([w, last, feat], [torch.randn(t.shape, device='cuda', generator=gen) for t in (w, last, feat)])
+            return plan, spy, seen, ray_id.cpu().numpy(), step_id.cpu().numpy()
+        finally:
+            L.call = call
+            F.BRICK_SCATTER, F.COMBINED_GRID_GRAD, F.COMBINED_MIN_RATIO = True, True, 6
+
+    plan, spy, _, ray_id, step_id = run('brick')
+    ins = spy.launches[0].inputs
+    off, recs = ins['off'].astype(np.int64), ins['recs']
+    E = plan.n_entries
+    assert off[0] == 0 and off[-1] == E == recs.shape[0] and np.all(np.diff(off) >= 0)
+    nb = off.shape[0] - 1
+    brick = np.repeat(np.arange(nb), np.diff(off))
+    # the samples: the forward's kept ones, and the alpha-only ones as the lists name them
+    M = ray_id.shape[0]
+    only = np.unique(recs[recs[:, 0] < 0][:, 1:3], axis=0)
+    kept_keys = set(zip(ray_id.tolist(), step_id.tolist()))
+    assert len(kept_keys) == M and not any((r, s) in kept_keys for r, s in only.tolist())
+    samples = np.zeros((M + only.shape[0], 4), np.int32)
+    samples[:M, 0], samples[:M, 1], samples[:M, 2] = np.arange(M), ray_id, step_id
+    samples[M:, 0], samples[M:, 1:3] = -1, only
+    pos = B.positions(samples, ins['rays_start'], ins['rays_dir'], ins['stepdist'])
+    ijk0, _, inb, _ = B.tri_setup(pos, ins['xyz_min'], ins['xyz_max'], X, Y, Z)
+    assert inb[:M].any(1).all()
+    smp, brk = B.incidences(ijk0, X, Y, Z)
+    want = np.concatenate([brk[:, None], samples[smp, :3].astype(np.int64)], 1)
+    got = np.concatenate([brick[:, None], recs[:, :3].astype(np.int64)], 1)
+    order = lambda a: a[np.lexsort(a.T[::-1])]
+    assert want.shape == got.shape and np.array_equal(order(want), order(got))       # equality of multisets, brick by brick
+    assert E >= M
+    # the density gradient in the records == grad_kept of the atomic path
+    _, _, seen, ray_id2, step_id2 = run('rows')
+    assert np.array_equal(ray_id2, ray_id) and np.array_equal(step_id2, step_id) and seen['kept'] is not None
+    k = recs[:, 0] >= 0
+    assert np.array_equal(recs[k, 3], seen['kept'].view(np.int32)[recs[k, 0]])
 
 
 def test_heavy_bricks_are_split_into_slices_that_meet_in_scratch_tiles(monkeypatch):

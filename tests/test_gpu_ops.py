@@ -470,6 +470,32 @@ def test_loss_gradients_handed_to_the_composite_backward_equal_autograd_sums():
             np.testing.assert_allclose(a.cpu().numpy(), b.cpu().numpy(), rtol=2e-5, atol=1e-9)
 
 
+def test_composite_backward_with_only_the_rgb_gradient_handed_over_equals_autograd_sums():
+    """`ctx.extra` holding the loss's gradient of rgb and none of alphainv_last: the backward adds its share of rgb's
+    gradient in place and finishes alphainv_last the plain way (fused.py, `_Composite.backward`) -- elementwise the sum
+    autograd would form, to one float32 addition."""
+    from directvoxgo_amd.fused import composite
+    torch.manual_seed(5)
+    N, M = 257, 9001
+    rid = torch.sort(torch.randint(N, (M,), device='cuda'))[0]
+    off3 = torch.zeros(N + 1, dtype=torch.int64, device='cuda')
+    off3[1:] = torch.cumsum(torch.bincount(rid, minlength=N), 0)
+    w = (torch.rand(M, device='cuda') * 0.05).requires_grad_()
+    rgb = torch.rand(M, 3, device='cuda').requires_grad_()
+    last = torch.rand(N, device='cuda').requires_grad_()
+    g = torch.randn(N, 3, device='cuda')
+    plain = torch.autograd.grad(composite(w, rgb, last, rid, off3, 1.0), [w, rgb, last], g)
+    extra = torch.randn(M, 3, device='cuda')
+    handed = extra.clone()
+    out = composite(w, rgb, last, rid, off3, 1.0)
+    out.grad_fn.extra = (handed, None)
+    got = torch.autograd.grad(out, [w, rgb, last], g)
+    assert got[1].data_ptr() == handed.data_ptr() and out.grad_fn.extra is None       # added to in place, consumed
+    assert torch.equal(got[0], plain[0]) and torch.equal(got[2], plain[2])
+    want = plain[1].double() + extra.double()
+    assert bool(((got[1].double() - want).abs() <= 2.0 ** -23 * (plain[1].abs() + extra.abs()).double()).all())
+
+
 def test_viewdir_embed_matches_torch_expression():
     from directvoxgo_amd.shade import viewdir_embed
     v = torch.nn.functional.normalize(torch.randn(1000, 3, device='cuda'), dim=-1)
