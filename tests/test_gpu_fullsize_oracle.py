@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 import torch
 
+import march_oracle as MO
 import render_oracle as R
 
 pytestmark = pytest.mark.gpu
@@ -83,13 +84,18 @@ def _check_gradients(m, sc, ref, target, n_rays, rk):
             k0.register_hook(lambda g: seen.append(g.detach().clone()))
         return shade(k0, *a, **kw)
     m._shade = tap
-    try:
-        res = m(ro, rd, vd, **rk)
-    finally:
-        m._shade = shade
-    loss = fused_render_loss(res, target, n_rays, dict(FINE_TRAIN))
-    loss.backward()
-    torch.cuda.synchronize()
+    # beside the grid-wide `_within` below: every record of every ray against tests/march_oracle.py, on the launches' own arguments
+    with MO.MarchSpy() as spy:
+        try:
+            res = m(ro, rd, vd, **rk)
+        finally:
+            m._shade = shade
+        loss = fused_render_loss(res, target, n_rays, dict(FINE_TRAIN))
+        loss.backward()
+        torch.cuda.synchronize()
+    summ = spy.summary()
+    assert summ['march_density'][0] == 1 and summ['march_density_bwd'][0] == 1 and summ['march_density_bwd'][1] == summ['march_density'][1]
+    print('march per sample (launches, elements, worst err / bound)', summ)
     ref_loss, g = R.loss_and_grads(sc, ref, _np(target), w_main=FINE_TRAIN['weight_main'],
                                    w_ent=FINE_TRAIN['weight_entropy_last'], w_per=FINE_TRAIN['weight_rgbper'])
     np.testing.assert_allclose(float(loss.detach()), ref_loss, rtol=1e-5)
