@@ -223,7 +223,7 @@ class MaskedAdam(torch.optim.Optimizer):
         if use_perlr:
             self.per_lr = self._like(p, self.per_lr)
         mode = 2 if use_perlr else (1 if group.get('skip_zero_grad', False) else 0)
-        from .train import flat_view
+        from .dp import flat_view
         m, v = flat_view(st['exp_avg']), flat_view(st['exp_avg_sq'])
         pl = flat_view(self.per_lr)[lo:hi] if use_perlr else None
         adam_upd(flat_p[lo:hi], flat_g[lo:hi], m[lo:hi], v[lo:hi], st['step'], b1, b2, group['lr'], group['eps'], mode=mode,

@@ -16,26 +16,17 @@ adam_upd_kernel.cu:35) and must see the reduced gradient.
 """
 import contextlib
 import ctypes
+from typing import NamedTuple
 
 import torch
 import torch.distributed as dist
 import torch.nn as nn
 
 from . import _lib as L
+from .dp import GridReducer, flat_view  # noqa: F401  (flat_view: part of this module's surface)
 from .masked_adam import MaskedAdam
 from .fused import brick_union, grid_rows_capture, split_grid_rows
 from .shade import defer_wgrad
-
-def flat_view(t):
-    """1-D view of a dense tensor's memory (no copy): collectives want plain contiguous buffers, and the
-    feature grid / its gradient are stored channels-last."""
-    if t.is_contiguous():
-        return t.view(-1)
-    if t.dim() == 5 and t.is_contiguous(memory_format=torch.channels_last_3d):
-        v = t.permute(0, 2, 3, 4, 1).reshape(-1)
-        assert v.data_ptr() == t.data_ptr()
-        return v
-    return None
 
 
 COARSE_TRAIN = dict(
@@ -149,8 +140,17 @@ def fused_render_loss(render_result, target, n_rays_global, cfg_train):
                             float(cfg_train['weight_rgbper']), render_result.get('n_samples'))
 
 
+class _Plan(NamedTuple):
+    """What one step will do, decided once before the forward."""
+    path: str            # 'fused' (Adam in the brick kernel) / 'tiles' (the same from all-reduced tiles, if bu.sparse) / 'rows' / 'dense'
+    tv: bool             # total variation is added this step
+    keep_count: bool     # the sample count stays on the device (model.forward(_capacity=True))
+
+
 class TrainStep:
     """One optimisation step on one batch of rays; ``world_size > 1`` shards the batch by rank."""
+
+    OVERLAP_MIN_SAMPLES = 600000
 
     def __init__(self, model, cfg_train, render_kwargs, optimizer=None, process_group=None, fused_loss=True,
                  overlap_wgrad=True, touched_reduce=True, rows_adam=True, track_mse=False, shard_grids=True, sync_free=False):
@@ -162,9 +162,6 @@ class TrainStep:
         self.sync_free = sync_free
         self._m3_seen = None                 # last sample count read back (asynchronously, a step or two late)
         self._m3_pin, self._m3_event = None, None
-        # data parallel, dense scenes: reduce-scatter the grid gradients, update only the owned slab, all-gather the
-        # parameters (see _sharded_*); False = plain all-reduce + full update on every rank
-        self.shard_grids = shard_grids
         # weight_main * mse of the step, the quantity run.py:378 turns into the logged PSNR (before the entropy and
         # per-point terms are added); kept on the device, no sync
         self.track_mse = track_mse
@@ -172,25 +169,21 @@ class TrainStep:
         # one GPU, no TV this step: Adam reads the combined gradient rows of the fused backward directly
         # (fused.grid_rows_capture / MaskedAdam.step_grid_rows); density.grad / k0.grad then stay None
         self.rows_adam = rows_adam
-        # data parallel, sparse scenes: all-reduce only the voxels some rank touched (see _reduce_touched)
+        # data parallel, sparse scenes: all-reduce only the voxels some rank touched (see dp.GridReducer._reduce_touched)
         self.touched_reduce = touched_reduce
-        self._touched_frac = None            # fraction of voxels in the last union; None: not probed yet
-        self._steps_since_probe = 0
         self.overlap_wgrad = overlap_wgrad    # colour-head weight gradients on a second stream (shade.defer_wgrad)
         # data parallel, fused HIP model: the grid gradient travels as the tiles of the bricks any rank touched and every
-        # rank applies the same fused Adam update (fused.brick_union); used while that union is at most BRICK_SPARSE_MAX of
-        # the bricks, decided per step from the all-reduced brick counts
+        # rank applies the same fused Adam update (fused.brick_union); used while that union is at most
+        # dp.GridReducer.BRICK_SPARSE_MAX (set it on `self.dp`) of the bricks, decided per step from the all-reduced brick counts
         self.brick_sparse = True
         self.last_mode = None                 # 'bricks' / 'sharded' / 'allreduce' / 'touched' / 'single': what the last step used
         self.last_wire_bytes = 0
-        # the sharded update leaves every rank with the moments of its own X-slab only: before any step that updates the
-        # whole grid on every rank (tiles, touched voxels, all-reduce fallback) the slabs are gathered once
-        self._moments_sharded = False
+        self.last_fused_adam = False          # (bench.py: which bytes the scatter launch is credited with)
+        self._graph, self._capturing, self._static, self._static_loss = None, False, None, None    # see capture()
         self.fused_loss = fused_loss
         self.cfg = cfg_train
         self.render_kwargs = render_kwargs
         self.optimizer = optimizer or create_optimizer_or_freeze_model(model, cfg_train, global_step=0)
-        self.pg = process_group
         self.world = dist.get_world_size(process_group) if (dist.is_available() and dist.is_initialized()) else 1
         # a positional-encoding colour head (posbase_pe > 0) reads no k0: only the density grid gets a gradient, so the
         # paths that take both grids' gradients together (brick scatter with the fused Adam, combined gradient rows) stay off
@@ -205,186 +198,32 @@ class TrainStep:
         if self.contracted and self.world > 1:
             raise NotImplementedError('data-parallel training of DirectContractedVoxGO is not built: train it on one GPU')
         self.decay_factor = 0.1 ** (1 / (cfg_train['lrate_decay'] * 1000))
-        self._small = [p for n, p in model.named_parameters() if n not in ('density', 'k0') and p.requires_grad]
+        # every collective of the step outside fused.brick_union; None on one GPU
+        self.dp = None if self.world == 1 else GridReducer(
+            model, self.optimizer, process_group, shard_grids,
+            small=[p for n, p in model.named_parameters() if n not in ('density', 'k0') and p.requires_grad])
 
-    def reduce_grids_async(self):
-        """Sparse scenes: start the compacted touched-voxel reduction (see _reduce_touched); returns its handle, or []
-        when the dense path (sharded reduce-scatter / all-reduce) has to take the step."""
-        works = []
-        if self.world == 1:
-            return works
-        if self.touched_reduce:
-            self._steps_since_probe += 1
-            probe = self._touched_frac is None or self._steps_since_probe >= self.PROBE_EVERY
-            if probe or self._touched_frac <= self.TOUCHED_MAX:
-                rd = self._rows()
-                pending = self._reduce_touched(*rd) if rd is not None else None
-                if pending is not None:
-                    return [pending]
-        return works
-
-    def _all_reduce_grids(self):
-        """Plain sum of the full grid gradients on every rank (the fallback when the grids cannot be sharded)."""
-        works = []
-        for p in (self.model.density, self.model.k0):
-            if p.grad is not None:
-                flat = flat_view(p.grad)
-                if flat is not None:
-                    works.append(dist.all_reduce(flat, op=dist.ReduceOp.SUM, group=self.pg, async_op=True))
-                else:                                 # exotic strides: staged through a contiguous copy
-                    tmp = p.grad.contiguous()
-                    dist.all_reduce(tmp, op=dist.ReduceOp.SUM, group=self.pg)
-                    p.grad.copy_(tmp)
-        return works
-
-    # A batch of rays touches the voxels along those rays only: on a trained scene a few per cent of the grid, while
-    # the dense all-reduce always moves all of it (213 MB at 160^3 -- more than a whole step of compute on such
-    # scenes).  The touched set differs per rank, so: OR-reduce a byte mask (4 MB), compact the union's rows
-    # [n, C + 1] (features + density), all-reduce that, write back.  Untouched voxels stay exactly zero on every
-    # rank, which is what the masked Adam and the sparse TV branch on.  Used while the union stays below
-    # TOUCHED_MAX of the grid (decided from the previous union, identical on all ranks; re-probed every
-    # PROBE_EVERY steps while the dense path is in use).
-    TOUCHED_MAX = 0.35
-    BRICK_SPARSE_MAX = 0.5
-    PROBE_EVERY = 64
-    OVERLAP_MIN_SAMPLES = 600000
-
-    def _rows(self):
-        """(k0.grad as [n_vox, C] rows, density.grad as [n_vox]) when both share the lattice and are row-addressable."""
-        d, k = self.model.density.grad, self.model.k0.grad
-        if d is None or k is None or d.dim() != 5 or k.dim() != 5 or d.shape[2:] != k.shape[2:] or not d.is_contiguous():
-            return None
-        flat = flat_view(k) if k.is_contiguous(memory_format=torch.channels_last_3d) else None
-        if flat is None:
-            return None
-        return flat.view(-1, k.shape[1]), d.view(-1)
-
-    def _reduce_touched(self, rows, dflat):
-        mask = (rows != 0).any(1) | (dflat != 0)
-        m8 = mask.to(torch.uint8)
-        dist.all_reduce(m8, op=dist.ReduceOp.MAX, group=self.pg)
-        idx = m8.nonzero().flatten()                       # the union, identical on every rank (one host read)
-        self._touched_frac = idx.numel() / max(m8.numel(), 1)
-        self._steps_since_probe = 0
-        if self._touched_frac > self.TOUCHED_MAX:
-            return None                                     # dense scene: the caller falls back to the plain all-reduce
-        C = rows.shape[1]
-        compact = torch.empty((idx.numel(), C + 1), dtype=rows.dtype, device=rows.device)
-        if idx.numel():
-            compact[:, :C] = rows[idx]
-            compact[:, C] = dflat[idx]
-        work = dist.all_reduce(compact, op=dist.ReduceOp.SUM, group=self.pg, async_op=True)
-
-        class _Pending:
-            def wait(_self):
-                work.wait()
-                if idx.numel():
-                    rows[idx] = compact[:, :C]
-                    dflat[idx] = compact[:, C]
-        return _Pending()
-
-    # ------------------------------------------------------------------------------------------------------------
-    # Dense scenes (every voxel has a gradient: the roofline case): a plain all-reduce moves 2 (P-1)/P x 213 MB per rank
-    # AND leaves every rank sweeping all 53 M elements through Adam.  Instead (ZeRO-1 style, SURVEY.md section 5):
-    #   reduce_scatter   rank r receives the SUM of the gradient of the X-planes [r X/P, (r+1) X/P) -- in place, the slab
-    #                    is a contiguous range of the gradient's memory (channels-last / C == 1: X is the outermost axis)
-    #   TV + Adam        on that slab only (1/P of the optimizer's traffic; the TV stencil reads the replicated params)
-    #   all_gather       the updated parameter slabs, in place in the parameters
-    # Same bytes on the wire as the all-reduce ((P-1)/P x 213 MB out and in per rank and phase, spread over all xGMI
-    # links by RCCL), 1/P of the optimizer work, and the parameters -- not the gradients -- are what ends up replicated.
-    # ------------------------------------------------------------------------------------------------------------
-    def _grid_shards(self):
-        """[(param, flat param, flat grad, lo, hi, (x_lo, x_hi))] for the grids when the sharded update applies."""
-        if not (self.shard_grids and self.world > 1 and hasattr(self.optimizer, 'step_shard')):
-            return None
-        rank = dist.get_rank(self.pg)
-        out = []
-        for p in (getattr(self.model, 'density', None), getattr(self.model, 'k0', None)):
-            if not isinstance(p, nn.Parameter) or p.grad is None or p.dim() != 5:
-                return None
-            x_outermost = p.shape[1] == 1 and p.is_contiguous() or p.is_contiguous(memory_format=torch.channels_last_3d)
-            fp, fg = flat_view(p.data), flat_view(p.grad)
-            X = p.shape[2]
-            if not x_outermost or fp is None or fg is None or p.grad.stride() != p.stride() or X % self.world != 0:
-                return None
-            n = fp.numel() // self.world
-            out.append((p, fp, fg, rank * n, (rank + 1) * n, (rank * (X // self.world), (rank + 1) * (X // self.world))))
-        return out
-
-    def _sharded_reduce_start(self, shards):
-        return [dist.reduce_scatter_tensor(fg[lo:hi], fg, op=dist.ReduceOp.SUM, group=self.pg, async_op=True)
-                for _, _, fg, lo, hi, _ in shards]
-
-    def _sharded_update(self, shards):
-        """Adam on the owned slabs, then the parameters travel.  Returns the all-gather handles."""
-        works = []
-        self._moments_sharded = True
-        self.optimizer._dvgo_sharded_by = self          # (checkpoint.save_checkpoint gathers the slabs before it writes)
-        for p, fp, fg, lo, hi, _ in shards:
-            self.optimizer.step_shard(p, fp, fg, lo, hi)
-            p.grad = None                      # consumed: optimizer.step() below skips the grids
-            works.append(dist.all_gather_into_tensor(fp, fp[lo:hi], group=self.pg, async_op=True))
-        return works
-
-    @torch.no_grad()
     def gather_optimizer_state(self):
-        """Data-parallel runs with the sharded update: every rank has only ever updated the moments of the X-slab it
-        owns.  Before `checkpoint.save_checkpoint` (or any other reader of `optimizer.state_dict()`), all-gather the slabs
-        in place so that every rank holds the complete `exp_avg` / `exp_avg_sq` of both grids -- the state a single
-        process would have written (run.py:420-437).  No-op on one rank or when the grids are not sharded."""
-        if not (self.shard_grids and self.world > 1 and hasattr(self.optimizer, 'step_shard')):
-            return False
-        rank = dist.get_rank(self.pg)
-        done = False
-        for p in (getattr(self.model, 'density', None), getattr(self.model, 'k0', None)):
-            st = self.optimizer.state.get(p) if isinstance(p, nn.Parameter) else None
-            if not st or p.dim() != 5 or p.shape[2] % self.world != 0:
-                continue
-            for key in ('exp_avg', 'exp_avg_sq'):
-                flat = flat_view(st[key])
-                if flat is None or st[key].stride() != p.stride():
-                    raise RuntimeError(f'gather_optimizer_state: {key} is not laid out like its parameter')
-                n = flat.numel() // self.world
-                dist.all_gather_into_tensor(flat, flat[rank * n:(rank + 1) * n].clone(), group=self.pg)
-            done = True
-        self._moments_sharded = False
-        return done
-
-    def _whole_grid_update_ahead(self):
-        """Call (on every rank: it is a collective when it does anything) before a step in which every rank updates the
-        WHOLE grid: after sharded steps each rank only holds current moments for its own slab."""
-        if self._moments_sharded:
-            self.gather_optimizer_state()
+        """See dp.GridReducer.gather_optimizer_state; no-op (False) on one GPU."""
+        return self.dp.gather_optimizer_state() if self.dp is not None else False
 
     def _sample_count(self, res):
         """Number of surviving samples of the step, without waiting for it: exact when the forward read it back anyway,
-        else the last value that has arrived from the device (copied asynchronously into pinned memory every step)."""
+        else the last value that has arrived from the device (copied asynchronously into pinned memory every step; no
+        host read at all while a graph is being captured)."""
         n_dev = res.get('n_samples')
-        if n_dev is None:
+        if n_dev is None and not self._capturing:
             return res['weights'].shape[0]
-        if self._m3_event is not None and self._m3_event.query():
-            self._m3_seen = int(self._m3_pin[0])
-        if self._m3_pin is None:
-            self._m3_pin = torch.empty(1, dtype=torch.int64).pin_memory()
-            self._m3_event = torch.cuda.Event()
-        if self._m3_event.query():                 # the previous copy has landed: start the next one
-            self._m3_pin.copy_(n_dev, non_blocking=True)
-            self._m3_event.record()
+        if not self._capturing:
+            if self._m3_event is not None and self._m3_event.query():
+                self._m3_seen = int(self._m3_pin[0])
+            if self._m3_pin is None:
+                self._m3_pin = torch.empty(1, dtype=torch.int64).pin_memory()
+                self._m3_event = torch.cuda.Event()
+            if self._m3_event.query():                 # the previous copy has landed: start the next one
+                self._m3_pin.copy_(n_dev, non_blocking=True)
+                self._m3_event.record()
         return self._m3_seen if self._m3_seen is not None else res['weights'].shape[0]
-
-    def reduce_small(self):
-        """One flat bucket for the handful of MLP gradients."""
-        if self.world == 1:
-            return
-        small = [p for p in self._small if p.grad is not None]
-        if small:
-            flat = torch.cat([p.grad.reshape(-1) for p in small])
-            dist.all_reduce(flat, op=dist.ReduceOp.SUM, group=self.pg)
-            off = 0
-            for p in small:
-                n = p.grad.numel()
-                p.grad.copy_(flat[off:off + n].view_as(p.grad))
-                off += n
 
     # ------------------------------------------------------------------------------------------------------------
     # HIP-graph replay of the step.  A sparse-scene step is ~45 short kernels (0.55 ms of GPU work at 8192 rays on a
@@ -400,7 +239,7 @@ class TrainStep:
         cfg, model = self.cfg, self.model
         density, k0 = getattr(model, 'density', None), getattr(model, 'k0', None)
         tv = (cfg['weight_tv_density'] > 0 or cfg['weight_tv_k0'] > 0) and cfg['tv_before'] > cfg['tv_after']
-        return bool(self.world == 1 and self.fused_loss and self.rows_adam and not tv and not self.k0_idle and not self.contracted
+        return bool(self.dp is None and self.fused_loss and self.rows_adam and not tv and not self.k0_idle and not self.contracted
                     and isinstance(self.optimizer, MaskedAdam) and isinstance(density, nn.Parameter) and density.is_cuda
                     and hasattr(model, 'can_keep_count_on_device') and model.can_keep_count_on_device()
                     and self.optimizer.can_fuse_grid_step(density, k0) and self.optimizer.per_lr is None)
@@ -453,39 +292,48 @@ class TrainStep:
                 dst.copy_(src, non_blocking=True)
         self.optimizer.hyper_begin(self.model.density, self.model.k0, advance=True)    # this step's Adam step sizes
         self._graph.replay()
-        for group in self.optimizer.param_groups:                                                  # run.py:401-406
-            group['lr'] = group['lr'] * self.decay_factor
+        self._decay_lr()
         return self._static_loss
 
     def __call__(self, rays_o, rays_d, viewdirs, target, global_step):
         """rays are this rank's shard; returns the (local share of the) loss as a 0-dim tensor (after `capture()`: a
         tensor that the next call overwrites)."""
-        if getattr(self, '_graph', None) is not None and rays_o.shape == self._static[0].shape:
+        if self._graph is not None and rays_o.shape == self._static[0].shape:
             return self._replay(rays_o, rays_d, viewdirs, target)
         return self._eager(rays_o, rays_d, viewdirs, target, global_step)
 
-    def _eager(self, rays_o, rays_d, viewdirs, target, global_step):
-        cfg, model = self.cfg, self.model
-        if isinstance(self.optimizer, MaskedAdam) and self.optimizer.hyper_dev is not None and not getattr(self, '_capturing', False):
-            self.optimizer.hyper_begin(model.density, model.k0)   # device-side step sizes of this step (see capture())
-        n_global = rays_o.shape[0] * self.world
-        keep_on_device = (self.sync_free and self.fused_loss and rays_o.is_cuda and hasattr(model, 'can_keep_count_on_device')
-                          and model.can_keep_count_on_device())
-        extra = {'_capacity': True} if keep_on_device else {}
-        tv_now = (cfg['tv_after'] < global_step < cfg['tv_before'] and global_step % cfg['tv_every'] == 0 and
-                  (cfg['weight_tv_density'] > 0 or cfg['weight_tv_k0'] > 0))
+    def _plan(self, rays_o, global_step):
+        cfg, model, opt = self.cfg, self.model, self.optimizer
+        tv = (cfg['tv_after'] < global_step < cfg['tv_before'] and global_step % cfg['tv_every'] == 0 and
+              (cfg['weight_tv_density'] > 0 or cfg['weight_tv_k0'] > 0))
         density, k0 = getattr(model, 'density', None), getattr(model, 'k0', None)
         # may the march's brick scatter apply the grid update itself?  One GPU: from its own tiles.  Data parallel: from the
         # all-reduced tiles of the bricks any rank touched (fused.brick_union) while that union stays small.
-        own = (self.rows_adam and not tv_now and not self.k0_idle and not self.contracted and isinstance(self.optimizer, MaskedAdam)
+        own = (self.rows_adam and not tv and not self.k0_idle and not self.contracted and isinstance(opt, MaskedAdam)
                and isinstance(density, nn.Parameter) and isinstance(k0, nn.Parameter) and density.is_cuda)
-        fuse_adam = own and self.optimizer.can_fuse_grid_step(density, k0)
-        dp_bricks = bool(fuse_adam and self.world > 1 and self.brick_sparse and getattr(model, 'fused', False))
-        if self.world > 1:
-            own = fuse_adam = False                    # (dense gradients unless the tile path takes the step)
-        with (brick_union(self.pg, self.BRICK_SPARSE_MAX) if dp_bricks else contextlib.nullcontext()) as bu:
+        fuse_adam = own and opt.can_fuse_grid_step(density, k0)
+        if self.dp is not None:                        # (dense gradients unless the tile path takes the step)
+            path = 'tiles' if (fuse_adam and self.brick_sparse and getattr(model, 'fused', False)) else 'dense'
+        else:
+            path = 'fused' if fuse_adam else 'rows' if (own and opt.can_step_grid_rows(density, k0)) else 'dense'
+        return _Plan(path, tv, bool(self.sync_free and self.fused_loss and rays_o.is_cuda
+                                    and hasattr(model, 'can_keep_count_on_device') and model.can_keep_count_on_device()))
+
+    def _decay_lr(self):
+        for group in self.optimizer.param_groups:                                                  # run.py:401-406
+            group['lr'] = group['lr'] * self.decay_factor
+
+    def _eager(self, rays_o, rays_d, viewdirs, target, global_step):
+        cfg, model, opt, dp = self.cfg, self.model, self.optimizer, self.dp
+        if isinstance(opt, MaskedAdam) and opt.hyper_dev is not None and not self._capturing:
+            opt.hyper_begin(model.density, model.k0)   # device-side step sizes of this step (see capture())
+        plan = self._plan(rays_o, global_step)
+        n_global = rays_o.shape[0] * self.world
+        density, k0 = getattr(model, 'density', None), getattr(model, 'k0', None)
+        extra = {'_capacity': True} if plan.keep_count else {}
+        with (brick_union(dp.pg, dp.BRICK_SPARSE_MAX) if plan.path == 'tiles' else contextlib.nullcontext()) as bu:
             res = model(rays_o, rays_d, viewdirs, global_step=global_step, **self.render_kwargs, **extra)
-            self.optimizer.zero_grad(set_to_none=True)
+            opt.zero_grad(set_to_none=True)
             loss_fn = fused_render_loss if (self.fused_loss and res['rgb_marched'].is_cuda) else render_loss
             loss = loss_fn(res, target, n_global, cfg)
             dist_loss = distortion_term(res, n_global, cfg) if loss_fn is fused_render_loss else None
@@ -493,80 +341,65 @@ class TrainStep:
                 loss = loss + dist_loss
             if self.track_mse:
                 self.last_mse = cfg['weight_main'] * (res['rgb_marched'].detach() - target).pow(2).sum() / (3 * n_global)
-            tiles = bool(dp_bricks and bu.sparse)      # identical on every rank: decided from the all-reduced brick counts
-            if tiles:
-                self._whole_grid_update_ahead()
+            # who updates the grids, now that the tile path knows (identical on every rank: decided from the all-reduced
+            # brick counts); 'tiles' that stay: every rank is about to update the whole grid inside the backward
+            path = 'dense' if (plan.path == 'tiles' and not bu.sparse) else plan.path
+            if path == 'tiles':
+                dp.whole_grid_update_ahead()
+            self.last_fused_adam = path in ('fused', 'tiles')
             # backward order: ... colour-head data gradient -> grid scatters.  One GPU: the colour head's weight-gradient
             # kernel runs on a second stream beside the scatters.  Data parallel: it is postponed until the grid
             # all-reduce has been STARTED -- its persistent workgroups fill every CU, and RCCL's kernels, arriving
             # second, would sit behind them; arriving first they keep their CUs and the two overlap
-            use_rows = fuse_adam or tiles or (own and self.optimizer.can_step_grid_rows(density, k0))
-            self.last_fused_adam = bool(fuse_adam or tiles)       # (bench.py: which bytes the scatter launch is credited with)
-            opt = self.optimizer
-            rows = (grid_rows_capture(density, k0, adam=(lambda: opt.grid_step_args(density, k0)) if (fuse_adam or tiles) else None)
-                    if use_rows else contextlib.nullcontext())
+            rows = (grid_rows_capture(density, k0, adam=(lambda: opt.grid_step_args(density, k0)) if self.last_fused_adam else None)
+                    if path != 'dense' else contextlib.nullcontext())
             # the second stream pays on kernel-bound steps (the weight-gradient kernel beside the grid scatter: -0.3 ms at
             # 2 M samples) and costs on launch-bound ones (stream switches and event records on the host: +0.1 ms at 0.2 M)
-            if getattr(self, '_capturing', False):       # no host reads while a graph is being captured: the last count seen
-                n_samples = self._m3_seen if self._m3_seen is not None else res['weights'].shape[0]
-            else:
-                n_samples = self._sample_count(res)
-            side = self.overlap_wgrad and self.world == 1 and n_samples >= self.OVERLAP_MIN_SAMPLES
+            n_samples = self._sample_count(res)
+            side = self.overlap_wgrad and dp is None and n_samples >= self.OVERLAP_MIN_SAMPLES
             with defer_wgrad(side_stream=side) as deferred, rows as cap:
                 _FusedLoss.unit_grad = True
                 try:
                     loss.backward()
                 finally:
                     _FusedLoss.unit_grad = False
-        self.last_mode = 'single' if self.world == 1 else None
-        self.last_wire_bytes = 0
-        if use_rows and cap.stepped:
-            assert density.grad is None and k0.grad is None    # both grids were updated inside the backward (csrc/brick.hip)
-            if tiles:
-                self.last_mode, self.last_wire_bytes = 'bricks', bu.bytes_on_wire
-        elif use_rows and cap.G is not None:
+        # what the backward left: 'stepped' (both grids were updated inside it, csrc/brick.hip), gradient 'rows', or 'dense' .grad
+        outcome = 'dense' if cap is None else 'stepped' if cap.stepped else 'rows' if cap.G is not None else 'dense'
+        if outcome == 'stepped':
+            assert density.grad is None and k0.grad is None
+        elif outcome == 'rows':
             if density.grad is None and k0.grad is None:
-                self.optimizer.step_grid_rows(density, k0, cap.G)  # (.grad of the two grids is None: step() below skips them)
+                opt.step_grid_rows(density, k0, cap.G)            # (.grad of the two grids is None: step() below skips them)
             else:                                                 # more than one march in the graph: fold the rows back
                 gd, gk = split_grid_rows(cap.G, density, k0)
                 density.grad = gd if density.grad is None else density.grad + gd
                 k0.grad = gk if k0.grad is None else k0.grad + gk
             cap.G = None
-        if self.world > 1 and not (use_rows and cap.stepped):
-            # every rank must enter the same collectives: a rank whose shard produced no gradient for a grid brings zeros
-            for p in (density, k0):
-                if isinstance(p, nn.Parameter) and p.requires_grad and p.grad is None:
-                    p.grad = torch.zeros_like(p, memory_format=torch.preserve_format)
-        # (dp_bricks: the all-reduced brick counts have just said that the scene is dense -- no touched-voxel probe)
-        works = [] if ((use_rows and cap.stepped) or dp_bricks) else self.reduce_grids_async()
-        shards = None
-        if self.world > 1 and not works and not (use_rows and cap.stepped):   # (else the compacted reduction took the step)
-            shards = self._grid_shards()
-            if shards:
-                works = self._sharded_reduce_start(shards)
-                self.last_mode = 'sharded'
-            else:
-                self._whole_grid_update_ahead()
-                works = self._all_reduce_grids()
-                self.last_mode = 'allreduce'
-        elif works:
-            self._whole_grid_update_ahead()
-            self.last_mode = 'touched'
-        deferred.flush()
-        self.reduce_small()
-        for wk in works:
-            wk.wait()
-        if cfg['tv_after'] < global_step < cfg['tv_before'] and global_step % cfg['tv_every'] == 0:   # run.py:389-395
-            dense = global_step < cfg['tv_dense_before']
-            xr = {'x_range': shards[0][5]} if shards else {}      # a rank that owns a slab adds the TV gradient of that slab
-            if cfg['weight_tv_density'] > 0:
-                model.density_total_variation_add_grad(cfg['weight_tv_density'] / n_global, dense, **xr)
-            if cfg['weight_tv_k0'] > 0:
-                model.k0_total_variation_add_grad(cfg['weight_tv_k0'] / n_global, dense, **xr)
-        gathers = self._sharded_update(shards) if shards else []
-        self.optimizer.step()
-        for wk in gathers:
-            wk.wait()
-        for group in self.optimizer.param_groups:                                                  # run.py:401-406
-            group['lr'] = group['lr'] * self.decay_factor
+        if dp is None:
+            deferred.flush()
+            self.last_mode = 'single'
+            if plan.tv:
+                self._tv_add_grad(global_step, n_global)
+            opt.step()
+        else:
+            # (tiles that said "dense": the all-reduced brick counts have settled it, no touched-voxel probe)
+            dp.start(bu.bytes_on_wire if outcome == 'stepped' else None, probe=self.touched_reduce and bu is None)
+            deferred.flush()
+            slab = dp.wait()
+            if plan.tv:
+                self._tv_add_grad(global_step, n_global, **slab)
+            gathers = dp.finish()
+            opt.step()
+            for wk in gathers:
+                wk.wait()
+            self.last_mode, self.last_wire_bytes = dp.last_mode, dp.last_wire_bytes
+        self._decay_lr()
         return loss.detach()
+
+    def _tv_add_grad(self, global_step, n_global, **x_range):
+        """run.py:389-395, after the grid gradients have been reduced (data parallel: on the owned slab when sharded)."""
+        cfg, dense = self.cfg, global_step < self.cfg['tv_dense_before']
+        if cfg['weight_tv_density'] > 0:
+            self.model.density_total_variation_add_grad(cfg['weight_tv_density'] / n_global, dense, **x_range)
+        if cfg['weight_tv_k0'] > 0:
+            self.model.k0_total_variation_add_grad(cfg['weight_tv_k0'] / n_global, dense, **x_range)

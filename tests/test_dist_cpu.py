@@ -6,6 +6,7 @@ normalised by the global ray count, grid gradients summed with all-reduce, MLP g
 bucket, optimizer step after the reduction.  Two ranks on half the batch each must end at exactly the
 parameters one process reaches on the whole batch.
 """
+import contextlib
 import os
 import socket
 
@@ -96,7 +97,29 @@ class TorchMaskedAdam(torch.optim.Optimizer):
                   g['lr'], mode=1 if g.get('skip_zero_grad') else 0)
 
 
-def run_steps(model, batch, rank, world, n_steps=3, mode='dense', out=None):
+@contextlib.contextmanager
+def record_collectives(log):
+    """Append (name, reduce op, dtype, numel of the whole buffer) to `log` for every collective issued inside."""
+    whole = {'all_reduce': 0, 'reduce_scatter_tensor': 1, 'all_gather_into_tensor': 0}     # (output, input) argument order
+    saved = {name: getattr(dist, name) for name in whole}
+
+    def wrap(name):
+        def call(*args, **kw):
+            op = kw.get('op', None if name == 'all_gather_into_tensor' else dist.ReduceOp.SUM)
+            t = args[whole[name]]
+            log.append((name, None if op is None else str(op).split('.')[-1], str(t.dtype).split('.')[-1], t.numel()))
+            return saved[name](*args, **kw)
+        return call
+    for name in whole:
+        setattr(dist, name, wrap(name))
+    try:
+        yield
+    finally:
+        for name, fn in saved.items():
+            setattr(dist, name, fn)
+
+
+def run_steps(model, batch, rank, world, n_steps=3, mode='dense', out=None, schedule=None):
     cfg = dict(FINE_TRAIN, weight_entropy_last=0.01, weight_rgbper=0.05)
     if mode in ('sharded', 'sharded_off', 'flip'):
         # Adam with the masked rule on the grids, the sharded update on (reduce-scatter -> slab Adam -> all-gather)
@@ -105,19 +128,14 @@ def run_steps(model, batch, rank, world, n_steps=3, mode='dense', out=None):
                                {'params': [model.k0], 'lr': 0.1, 'skip_zero_grad': True},
                                {'params': list(model.rgbnet.parameters()), 'lr': 1e-2}])
         step = TrainStep(model, cfg, dict(bg=1), optimizer=opt, touched_reduce=False, shard_grids=(mode != 'sharded_off'))
-        step.sharded_steps = 0
-        orig = step._sharded_update
-        def counted(shards):
-            step.sharded_steps += 1
-            return orig(shards)
-        step._sharded_update = counted
     else:
         opt = torch.optim.SGD(model.parameters(), lr=0.5)
         step = TrainStep(model, cfg, dict(bg=1), optimizer=opt, touched_reduce=(mode != 'dense'))
+    reducer = step.dp                     # dp.GridReducer: the thresholds live there; None in the one-process reference
     if mode == 'touched':
-        step.TOUCHED_MAX = 2.0            # always take the compact (touched-voxel) reduction
+        reducer.TOUCHED_MAX = 2.0         # always take the compact (touched-voxel) reduction
     elif mode == 'adaptive':
-        step.TOUCHED_MAX = 0.0            # probe, find the union too large, fall back to the dense all-reduce
+        reducer.TOUCHED_MAX = 0.0         # probe, find the union too large, fall back to the dense all-reduce
     n = batch[0].shape[0] // world
     shard = tuple(t[rank * n:(rank + 1) * n] for t in batch)
     losses = []
@@ -127,15 +145,17 @@ def run_steps(model, batch, rank, world, n_steps=3, mode='dense', out=None):
             # the reduction mode changes mid-run -- two sharded steps (each rank updates the moments of its
             # own X-slab only), then the compacted touched-voxel reduction with a full update on every rank
             step.touched_reduce = True
-            step.TOUCHED_MAX = 2.0
-        losses.append(step(*shard, global_step=s))
+            if reducer is not None:
+                reducer.TOUCHED_MAX = 2.0
+        with record_collectives([] if schedule is None else schedule.setdefault(f'step {s}', [])):
+            losses.append(step(*shard, global_step=s))
         modes_seen.append(step.last_mode)
     if mode == 'flip' and world > 1:
         assert modes_seen == ['sharded', 'sharded', 'touched', 'touched'], modes_seen
     if mode == 'sharded' and world > 1:
-        assert step.sharded_steps == n_steps                    # the slab path really ran
+        assert modes_seen == ['sharded'] * n_steps, modes_seen  # the slab path really ran
     if mode == 'sharded_off':
-        assert step.sharded_steps == 0
+        assert 'sharded' not in modes_seen, modes_seen
     if out is not None:
         out['step'] = step
     return torch.stack(losses)
@@ -166,9 +186,9 @@ def _worker(rank, world, port, q, mode='dense'):
         moments = _moments(model, out['step'])
     if mode == 'sharded':             # what a checkpoint of a data-parallel run needs: every rank's slab of the moments:
         from directvoxgo_amd.checkpoint import save_checkpoint        # the save helper gathers them itself
-        assert out['step']._moments_sharded
+        assert out['step'].dp._moments_sharded
         save_checkpoint(None, model, out['step'].optimizer, 3)        # (path None: this rank does not write)
-        assert not out['step']._moments_sharded
+        assert not out['step'].dp._moments_sharded
         moments = _moments(model, out['step'])
     if rank == 0:
         # numpy: pickled by value (torch tensors would travel as shared-memory handles of a process about to exit)
@@ -237,3 +257,61 @@ def test_render_loss_equals_reference_formula_on_one_rank():
     rgbper = (res['raw_rgb'] - tgt[res['ray_id']]).pow(2).sum(-1)
     b = b + cfg['weight_rgbper'] * ((rgbper * res['weights'].detach()).sum() / 16)
     assert torch.allclose(a, b, rtol=1e-6)
+
+
+def _schedule_worker(rank, world, port, q, mode):
+    os.environ['MASTER_ADDR'] = '127.0.0.1'
+    os.environ['MASTER_PORT'] = str(port)
+    dist.init_process_group('gloo', rank=rank, world_size=world)
+    torch.set_num_threads(1)
+    model = ToyModel()
+    out, schedule = {}, {}
+    run_steps(model, make_batch(32), rank, world, mode=mode, out=out, n_steps=4 if mode == 'flip' else 3, schedule=schedule)
+    if mode == 'sharded':
+        from directvoxgo_amd.checkpoint import save_checkpoint
+        with record_collectives(schedule.setdefault('save', [])):
+            save_checkpoint(None, model, out['step'].optimizer, 3)
+    q.put((rank, schedule))
+    dist.barrier()
+    dist.destroy_process_group()
+
+
+# (collective, reduce op, dtype, elements of the whole buffer) as `record_collectives` logs them, for the toy model: density
+# 150 voxels, k0 900 elements, the colour MLP 83 parameters, and a union of 64 touched voxels x (6 channels + density)
+_ALL_REDUCE = [('all_reduce', 'SUM', 'float32', 150), ('all_reduce', 'SUM', 'float32', 900), ('all_reduce', 'SUM', 'float32', 83)]
+_TOUCHED = [('all_reduce', 'MAX', 'uint8', 150), ('all_reduce', 'SUM', 'float32', 448), ('all_reduce', 'SUM', 'float32', 83)]
+_SHARDED = [('reduce_scatter_tensor', 'SUM', 'float32', 150), ('reduce_scatter_tensor', 'SUM', 'float32', 900),
+            ('all_reduce', 'SUM', 'float32', 83),
+            ('all_gather_into_tensor', None, 'float32', 150), ('all_gather_into_tensor', None, 'float32', 900)]
+_GATHER_MOMENTS = [('all_gather_into_tensor', None, 'float32', 150), ('all_gather_into_tensor', None, 'float32', 150),
+                   ('all_gather_into_tensor', None, 'float32', 900), ('all_gather_into_tensor', None, 'float32', 900)]
+SCHEDULE = {
+    'dense': {'step 0': _ALL_REDUCE, 'step 1': _ALL_REDUCE, 'step 2': _ALL_REDUCE},
+    'touched': {'step 0': _TOUCHED, 'step 1': _TOUCHED, 'step 2': _TOUCHED},
+    # the probe of step 0 finds the union too large; no probe again before PROBE_EVERY steps
+    'adaptive': {'step 0': [('all_reduce', 'MAX', 'uint8', 150)] + _ALL_REDUCE, 'step 1': _ALL_REDUCE, 'step 2': _ALL_REDUCE},
+    'sharded': {'step 0': _SHARDED, 'step 1': _SHARDED, 'step 2': _SHARDED, 'save': _GATHER_MOMENTS},
+    'sharded_off': {'step 0': _ALL_REDUCE, 'step 1': _ALL_REDUCE, 'step 2': _ALL_REDUCE},
+    # step 2: the slab moments are gathered once the compacted reduction is under way, before the whole-grid update
+    'flip': {'step 0': _SHARDED, 'step 1': _SHARDED, 'step 2': _TOUCHED[:2] + _GATHER_MOMENTS + _TOUCHED[2:], 'step 3': _TOUCHED},
+}
+
+
+@pytest.mark.timeout(120)
+@pytest.mark.parametrize('mode', ['dense', 'touched', 'adaptive', 'sharded', 'sharded_off', 'flip'])
+def test_collective_schedule(mode):
+    """Which collectives a step issues, in which order, on what: both ranks log the same list, and it is the list the step
+    issued before the reduction moved into dp.GridReducer (recorded with this test on that code).  `save`: the gather of
+    the slab moments inside save_checkpoint."""
+    ctx = mp.get_context('spawn')
+    q = ctx.Queue()
+    port = _free_port()
+    procs = [ctx.Process(target=_schedule_worker, args=(r, 2, port, q, mode)) for r in range(2)]
+    for p in procs:
+        p.start()
+    got = dict(q.get(timeout=100) for _ in procs)
+    for p in procs:
+        p.join(timeout=60)
+        assert p.exitcode == 0
+    assert got[0] == got[1]
+    assert got[0] == SCHEDULE[mode]

@@ -240,6 +240,30 @@ def _assert_same_up_to_adam_noise(x, y, name=''):
     assert float(d.max()) <= 0.35, name                       # 3 steps x lr 0.1 (+ margin)
 
 
+# (collective, reduce op, dtype, elements of the whole buffer) per step, as test_dist_cpu.record_collectives logs them on either
+# rank of the two-rank runs below: 32^3 density voxels, 12 x 32^3 k0 elements, 22019 colour-MLP parameters, 64 brick counts,
+# the tiles of the touched bricks, and a union of touched voxels x (12 channels + density).  Recorded on an MI355X from the
+# step as it was before the reduction moved into dp.GridReducer; every size was the same on both ranks of two runs.
+_F32 = 'float32'
+_DP_SMALL = ('all_reduce', 'SUM', _F32, 22019)
+_DP_SHARDED = [('reduce_scatter_tensor', 'SUM', _F32, 32768), ('reduce_scatter_tensor', 'SUM', _F32, 393216), _DP_SMALL,
+               ('all_gather_into_tensor', None, _F32, 32768), ('all_gather_into_tensor', None, _F32, 393216)]
+_DP_ALL_REDUCE = [('all_reduce', 'SUM', _F32, 32768), ('all_reduce', 'SUM', _F32, 393216), _DP_SMALL]
+_DP_COUNTS = ('all_reduce', 'SUM', 'int32', 64)                      # fused.brick_union: which bricks any rank touched
+_DP_TILES = ('all_reduce', 'SUM', _F32, 262144)
+_DP_GATHER_MOMENTS = [('all_gather_into_tensor', None, _F32, n) for n in (32768, 32768, 393216, 393216)]
+DP_SCHEDULE = {
+    'dense': [_DP_SHARDED] * 3,
+    'allreduce': [_DP_ALL_REDUCE] * 3,
+    'touched': [[('all_reduce', 'MAX', 'uint8', 32768), ('all_reduce', 'SUM', _F32, n), _DP_SMALL] for n in (58539, 58812, 59189)],
+    'sharded_tv': [_DP_SHARDED] * 3,
+    'bricks': [[_DP_COUNTS, _DP_TILES, _DP_SMALL]] * 3,
+    # steps 0-1: the brick counts say "dense" (threshold -1), no probe; step 2: the slab moments are gathered before the backward
+    'sharded_then_bricks': [[_DP_COUNTS] + _DP_SHARDED] * 2 + [[_DP_COUNTS] + _DP_GATHER_MOMENTS + [_DP_TILES, _DP_SMALL],
+                                                               [_DP_COUNTS, _DP_TILES, _DP_SMALL]],
+}
+
+
 def _dp_worker(rank, world, port, q, mode):
     import os
     import torch.distributed as dist
@@ -247,14 +271,20 @@ def _dp_worker(rank, world, port, q, mode):
     os.environ['MASTER_PORT'] = str(port)
     dist.init_process_group('gloo', rank=rank, world_size=world)      # RCCL needs one GPU per rank; gloo moves the same bytes
     torch.cuda.set_device(0)
-    params, losses = _dp_run(rank, world, mode)
+    schedule = []
+    params, losses = _dp_run(rank, world, mode, schedule=schedule)
+    both = [None] * world
+    dist.all_gather_object(both, schedule)
+    assert both[0] == both[1], both                                   # every rank entered the same collectives
+    assert schedule == DP_SCHEDULE[mode], schedule
     if rank == 0:
         q.put(({k: v.cpu().numpy().copy() for k, v in params.items()}, losses))
     dist.barrier()
     dist.destroy_process_group()
 
 
-def _dp_run(rank, world, mode, n_steps=3):
+def _dp_run(rank, world, mode, n_steps=3, schedule=None):
+    from test_dist_cpu import record_collectives
     from directvoxgo_amd.dvgo import DirectVoxGO
     from directvoxgo_amd.scenes import synthetic_scene
     from directvoxgo_amd.train import FINE_TRAIN, TrainStep
@@ -269,31 +299,33 @@ def _dp_run(rank, world, mode, n_steps=3):
         cfg.update(tv_before=1e9, tv_dense_before=0, weight_tv_density=1e-4, weight_tv_k0=1e-4)
     step = TrainStep(m, cfg, dict(near=sc['near'], far=sc['far'], bg=1, stepsize=0.5),
                      touched_reduce=(mode == 'touched'), shard_grids=(mode != 'allreduce'))
-    if mode == 'touched':
-        step.TOUCHED_MAX = 2.0
     step.brick_sparse = mode in ('bricks', 'sharded_then_bricks')
-    step.BRICK_SPARSE_MAX = 2.0 if mode == 'bricks' else -1.0          # the tile path always / (for now) never
-    if world > 1 and mode in ('dense', 'sharded_tv'):
-        assert step._grid_shards is not None
-        ran = []
-        orig = step._sharded_update
-        step._sharded_update = lambda shards: (ran.append(1), orig(shards))[1]
-        step._ran_sharded = ran
+    if world > 1:                          # the thresholds live on the reducer (dp.GridReducer)
+        if mode == 'touched':
+            step.dp.TOUCHED_MAX = 2.0
+        step.dp.BRICK_SPARSE_MAX = 2.0 if mode == 'bricks' else -1.0   # the tile path always / (for now) never
     n = 2048 // world
     shard = tuple(sc[k][rank * n:(rank + 1) * n] for k in ('rays_o', 'rays_d', 'viewdirs', 'target'))
     losses, modes = [], []
     for s in range(n_steps + (1 if mode == 'sharded_then_bricks' else 0)):
         if mode == 'sharded_then_bricks' and s == 2:
-            step.BRICK_SPARSE_MAX = 2.0          # two sharded steps (slab moments), then the tile path (whole-grid update)
-        losses.append(float(step(*shard, global_step=1 + s)))
+            if world > 1:
+                step.dp.BRICK_SPARSE_MAX = 2.0   # two sharded steps (slab moments), then the tile path (whole-grid update)
+        log = []
+        with record_collectives(log):
+            losses.append(float(step(*shard, global_step=1 + s)))
         modes.append(step.last_mode)
+        if schedule is not None:
+            schedule.append(log)
     torch.cuda.synchronize()
     if world > 1 and mode == 'bricks':
         assert modes == ['bricks'] * n_steps and step.last_wire_bytes > 0, modes
     if world > 1 and mode == 'sharded_then_bricks':
         assert modes == ['sharded', 'sharded', 'bricks', 'bricks'], modes
-    if hasattr(step, '_ran_sharded'):
-        assert len(step._ran_sharded) == n_steps        # reduce-scatter -> slab TV + Adam -> all-gather really ran
+    if world > 1 and mode in ('dense', 'sharded_tv'):
+        assert modes == ['sharded'] * n_steps, modes    # reduce-scatter -> slab TV + Adam -> all-gather really ran
+    if mode == 'allreduce':
+        assert 'sharded' not in modes, modes
     return {k: v.detach().clone() for k, v in m.state_dict().items() if v.is_floating_point()}, losses
 
 
@@ -307,7 +339,8 @@ def test_two_ranks_on_one_gpu_equal_one_process(mode):
     touched-voxel reduction; `bricks`: the gradient travels as the tiles of the bricks either rank touched (one all-reduce
     of a compact buffer) and both ranks apply the same fused Adam update from the summed tiles;
     `sharded_then_bricks`: the reduction mode changes mid-run (slab moments are gathered before the first whole-grid
-    update)."""
+    update).  Every rank logs the collectives of each step (test_dist_cpu.record_collectives): both ranks issue the same
+    list, and it is DP_SCHEDULE[mode], what the step issued before the reduction moved into dp.GridReducer."""
     import socket
     import torch.multiprocessing as mp
     ref_params, ref_losses = _dp_run(0, 1, mode)
