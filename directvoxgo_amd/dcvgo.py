@@ -25,9 +25,8 @@ import torch.nn.functional as F
 
 from . import _lib as L
 from ._lib import _flt, _i64, _int, check_f32, check_input, ptr, stream_of
-from .dvgo import DirectVoxGO, _as_f32, make_rgbnet
 from .fused import composite
-from .ops import Alphas2Weights, MaskCache
+from .voxel_model import VoxelModel, _as_f32, _result
 
 
 def contracted_t_table(world, stepsize, bg_len):
@@ -91,7 +90,7 @@ def contracted_sample(rays_o, rays_d, center, radius, t_tab, bg_len, contracted_
     return q, ray_id, step_id, t
 
 
-class DirectContractedVoxGO(nn.Module):
+class DirectContractedVoxGO(VoxelModel):
     """Voxel grids over the contracted space of an unbounded scene (see the module docstring)."""
 
     def __init__(self, xyz_min, xyz_max, num_voxels=0, num_voxels_base=0, alpha_init=None,
@@ -114,10 +113,7 @@ class DirectContractedVoxGO(nn.Module):
         self.bg_len = float(bg_len)
         self.contracted_norm = contracted_norm
         lim = 1 + self.bg_len
-        cmin, cmax = torch.full((3,), -lim, dtype=torch.float32), torch.full((3,), lim, dtype=torch.float32)
-        self.register_buffer('xyz_min', cmin.clone())
-        self.register_buffer('xyz_max', cmax.clone())
-        self._xyz_min_cpu, self._xyz_max_cpu = cmin, cmax
+        self._set_box(torch.full((3,), -lim, dtype=torch.float32), torch.full((3,), lim, dtype=torch.float32))
         self.fast_color_thres = fast_color_thres
 
         self.num_voxels_base = num_voxels_base
@@ -130,35 +126,14 @@ class DirectContractedVoxGO(nn.Module):
         self.density = nn.Parameter(torch.zeros([1, 1, *ws]))
         self.rgbnet_kwargs = {'rgbnet_dim': rgbnet_dim, 'rgbnet_direct': rgbnet_direct, 'rgbnet_depth': rgbnet_depth,
                               'rgbnet_width': rgbnet_width, 'viewbase_pe': viewbase_pe}
-        if rgbnet_dim <= 0:
-            self.k0_dim = 3
-            self.rgbnet = None
-        else:
-            self.k0_dim = rgbnet_dim
+        if rgbnet_dim > 0:
             self.rgbnet_direct = rgbnet_direct
-            self.register_buffer('viewfreq', torch.FloatTensor([(2 ** i) for i in range(viewbase_pe)]))
-            dim0 = (3 + 3 * viewbase_pe * 2) + (self.k0_dim if rgbnet_direct else self.k0_dim - 3)
-            self.rgbnet = make_rgbnet(dim0, rgbnet_width, rgbnet_depth)
-        self.k0 = nn.Parameter(self._alloc_k0(ws))
+        self._init_colour(ws, rgbnet_dim, rgbnet_dim if rgbnet_direct else rgbnet_dim - 3, viewbase_pe, rgbnet_width,
+                          rgbnet_depth)
 
         self.mask_cache_world_size = None if mask_cache_world_size is None else [int(v) for v in mask_cache_world_size]
-        mws = self.mask_cache_world_size or ws
-        self.mask_cache = MaskCache(path=None, mask=torch.ones(mws, dtype=torch.bool), xyz_min=self._xyz_min_cpu,
-                                    xyz_max=self._xyz_max_cpu)
+        self._set_mask_cache(torch.ones(self.mask_cache_world_size or ws, dtype=torch.bool))
         self._tab_cache = {}
-
-    # shared with DirectVoxGO: the same grids, activation, TV and colour head
-    _alloc_k0 = DirectVoxGO._alloc_k0
-    activate_density = DirectVoxGO.activate_density
-    grid_sampler = DirectVoxGO.grid_sampler
-    density_total_variation_add_grad = DirectVoxGO.density_total_variation_add_grad
-    k0_total_variation_add_grad = DirectVoxGO.k0_total_variation_add_grad
-    _shade = DirectVoxGO._shade
-    uses_posenc = False
-
-    def can_keep_count_on_device(self):
-        """The capacity mode of the fused march does not exist for this model."""
-        return False
 
     def _set_grid_resolution(self, num_voxels):
         """DirectVoxGO._set_grid_resolution on the contracted cube: the lattice is W^3."""
@@ -188,17 +163,12 @@ class DirectContractedVoxGO(nn.Module):
         """Trilinear resize of both grids to the new cubic lattice; the occupancy mask is rebuilt from the max-pooled
         activated density (at mask_cache_world_size when that is set)."""
         self._set_grid_resolution(num_voxels)
-        ws = tuple(int(v) for v in self.world_size)
-        self.density = nn.Parameter(F.interpolate(self.density.data, size=ws, mode='trilinear', align_corners=True))
-        k0 = F.interpolate(self.k0.data.contiguous(), size=ws, mode='trilinear', align_corners=True)
-        self.k0 = nn.Parameter(k0.contiguous(memory_format=torch.channels_last_3d) if self.k0_dim > 1 else k0)
-        self_alpha = F.max_pool3d(self.activate_density(self.density), kernel_size=3, padding=1, stride=1)
+        ws = self._resize_grids()
+        self_alpha = self._pooled_alpha()
         if self.mask_cache_world_size is not None and list(self.mask_cache_world_size) != list(ws):
             self_alpha = F.interpolate(self_alpha, size=tuple(self.mask_cache_world_size), mode='trilinear',
                                        align_corners=True)
-        mask = self_alpha[0, 0] > self.fast_color_thres
-        self.mask_cache = MaskCache(path=None, mask=mask.cpu(), xyz_min=self._xyz_min_cpu,
-                                    xyz_max=self._xyz_max_cpu).to(self.density.device)
+        self._set_mask_cache(self_alpha[0, 0] > self.fast_color_thres)
 
     def maskout_near_cam_vox(self, cam_o, near):
         raise NotImplementedError('maskout_near_cam_vox is not built for contracted space')
@@ -227,30 +197,21 @@ class DirectContractedVoxGO(nn.Module):
         """Volume rendering in contracted space; see the module docstring for the order and the extra keys.
         `near` / `far` in render_kwargs are ignored; `ndc` rays are not supported."""
         assert len(rays_o.shape) == 2 and rays_o.shape[-1] == 3, 'Only suuport point queries in [N, 3] format'
-        N = len(rays_o)
-        dev = rays_o.device
         stepsize = render_kwargs['stepsize']
         q, ray_id, step_id, t, n_max = self.sample_ray(rays_o, rays_d, stepsize)
-        interval = stepsize * self.voxel_size_ratio
-        density = self.grid_sampler(q, self.density)
-        alpha = self.activate_density(density, interval)
-        if self.fast_color_thres > 0:
-            mask = alpha > self.fast_color_thres
-            q, ray_id, step_id, t, alpha = q[mask], ray_id[mask], step_id[mask], t[mask], alpha[mask]
-        weights, alphainv_last = Alphas2Weights.apply(alpha, ray_id, N)
-        if self.fast_color_thres > 0:
-            mask = weights > self.fast_color_thres
-            weights, alpha = weights[mask], alpha[mask]
-            q, ray_id, step_id, t = q[mask], ray_id[mask], step_id[mask], t[mask]
-        k0 = self.grid_sampler(q, self.k0)
-        rgb = self._shade(k0, viewdirs, ray_id)
-        # per-ray sums in fixed order (the march's composite over the ray offsets): bitwise repeatable renders
+        ret = self._forward_unfused(len(rays_o), viewdirs, stepsize, render_kwargs['bg'],
+                                    render_kwargs.get('render_depth', False), q, ray_id, step_id, t)
+        ret['n_max'] = n_max
+        return ret
+
+    def _sum_rays(self, N, weights, alpha, alphainv_last, rgb, ray_id, bg, render_depth, step_id, t):
+        """Per-ray sums in fixed order (the march's composite over the ray offsets): bitwise repeatable renders."""
+        dev = weights.device
         off = torch.searchsorted(ray_id, torch.arange(N + 1, dtype=torch.int64, device=dev))
-        rgb_marched = composite(weights, rgb, alphainv_last, ray_id, off, render_kwargs['bg'])
-        ret = {'alphainv_last': alphainv_last, 'weights': weights, 'rgb_marched': rgb_marched,
-               'raw_alpha': alpha, 'raw_rgb': rgb, 'ray_id': ray_id, 'step_id': step_id, 't': t,
-               's': 1 - 1 / (1 + t), 'n_max': n_max}
-        if render_kwargs.get('render_depth', False):
+        rgb_marched = composite(weights, rgb, alphainv_last, ray_id, off, bg)
+        ret = _result(alphainv_last, weights, rgb_marched, alpha, rgb, ray_id)
+        ret.update(step_id=step_id, t=t, s=1 - 1 / (1 + t))
+        if render_depth:
             with torch.no_grad():
                 t3 = t.unsqueeze(-1).expand(-1, 3).contiguous()
                 ret['depth'] = composite(weights.detach(), t3, torch.zeros(N, device=dev), ray_id, off, 0.0)[:, 0]

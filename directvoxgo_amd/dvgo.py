@@ -22,76 +22,16 @@ configs set it, and its branches read an undefined k0 or unpack four values into
 import numpy as np
 import torch
 import torch.nn as nn
-import torch.nn.functional as F
 
 from . import _lib as L
 from . import render_utils as render_utils_hip
 from ._lib import _flt, _i64, _int, f3, ptr, stream_of
-from .fused import MarchConfig, composite, composite_depth, fused_hit, fused_march
-from .ops import Alphas2Weights, MaskCache, Raw2Alpha, grid_sample, segment_coo, total_variation_add_grad
-from .shade import posenc_supported, shade, shade_posenc, viewdir_embed
+from .fused import MarchConfig, fused_hit
+from .shade import head_layers
+from .voxel_model import VoxelModel, _freqs, make_rgbnet, mlp_forward  # noqa: F401 (tests and tools import the last two from here)
 
 
-def _as_f32(x):
-    return torch.as_tensor(np.asarray(x, dtype=np.float32) if not isinstance(x, torch.Tensor) else x.detach().cpu(),
-                           dtype=torch.float32)
-
-
-class _LinearSplitK(torch.autograd.Function):
-    """y = x @ W^T + b for tall-skinny x [M, K] (M ~ 10^6 samples, K, N <= 128).
-
-    Same maths as nn.Linear; only the weight gradient is evaluated differently: dW = g^T x is a
-    reduction over the M samples into a tiny [N, K] output, for which the stock GEMM picks a
-    3-ms single-pass kernel at M = 2 M (profiles/r1).  Here the samples are cut into chunks that are
-    reduced as one batched GEMM (parallel over chunks) and then summed."""
-    CHUNK = 8192
-
-    @staticmethod
-    def forward(ctx, x, weight, bias):
-        ctx.save_for_backward(x, weight)
-        return torch.addmm(bias, x, weight.t())
-
-    @staticmethod
-    def backward(ctx, g):
-        x, weight = ctx.saved_tensors
-        g = g.contiguous()
-        gx = g @ weight if ctx.needs_input_grad[0] else None
-        M, chunk = x.shape[0], _LinearSplitK.CHUNK
-        main = (M // chunk) * chunk
-        gw = None
-        if main:
-            S = main // chunk
-            gw = torch.bmm(g[:main].view(S, chunk, -1).transpose(1, 2), x[:main].view(S, chunk, -1)).sum(0)
-        if main < M:
-            tail = g[main:].t() @ x[main:]
-            gw = tail if gw is None else gw + tail
-        return gx, gw, g.sum(0)
-
-
-def mlp_forward(net, x):
-    """Run an rgbnet (nn.Sequential of Linear / ReLU / nested Sequential) with the split-K linear for
-    large sample counts; identical module tree and parameters."""
-    for mod in net:
-        if isinstance(mod, nn.Sequential):
-            x = mlp_forward(mod, x)
-        elif isinstance(mod, nn.Linear) and x.shape[0] >= 4 * _LinearSplitK.CHUNK and x.requires_grad | mod.weight.requires_grad:
-            x = _LinearSplitK.apply(x.contiguous(), mod.weight, mod.bias)
-        else:
-            x = mod(x)
-    return x
-
-
-def make_rgbnet(dim0, width, depth):
-    """Same module tree (hence state_dict keys) as lib/dvgo.py:123-131."""
-    net = nn.Sequential(
-        nn.Linear(dim0, width), nn.ReLU(inplace=True),
-        *[nn.Sequential(nn.Linear(width, width), nn.ReLU(inplace=True)) for _ in range(depth - 2)],
-        nn.Linear(width, 3))
-    nn.init.constant_(net[-1].bias, 0)
-    return net
-
-
-class DirectVoxGO(nn.Module):
+class DirectVoxGO(VoxelModel):
     def __init__(self, xyz_min, xyz_max, num_voxels=0, num_voxels_base=0, alpha_init=None,
                  mask_cache_path=None, mask_cache_thres=1e-3, fast_color_thres=0,
                  rgbnet_dim=0, rgbnet_direct=False, rgbnet_full_implicit=False,
@@ -109,12 +49,7 @@ class DirectVoxGO(nn.Module):
         self.fused = bool(fused)
         self.fused_shade = True          # fp32-MFMA colour head (csrc/shade.hip) when the rgbnet has the default shape
         self.channels_last = bool(channels_last)
-        xyz_min, xyz_max = _as_f32(xyz_min), _as_f32(xyz_max)
-        self.register_buffer('xyz_min', xyz_min.clone())
-        self.register_buffer('xyz_max', xyz_max.clone())
-        # host copies: sizing maths runs on the CPU in float32 exactly like the reference's
-        # tensor expressions, and never costs a device sync afterwards
-        self._xyz_min_cpu, self._xyz_max_cpu = xyz_min.clone(), xyz_max.clone()
+        self._set_box(xyz_min, xyz_max)
         self.fast_color_thres = fast_color_thres
 
         # lib/dvgo.py:55-62
@@ -136,39 +71,16 @@ class DirectVoxGO(nn.Module):
         self.posbase_pe = int(posbase_pe) if rgbnet_dim > 0 else 0
         if posbase_pe > 0:
             self.rgbnet_kwargs['posbase_pe'] = posbase_pe
-        if rgbnet_dim <= 0:
-            self.k0_dim = 3                 # colour grid, coarse stage (lib/dvgo.py:83-87)
-            self.rgbnet = None
-        else:
-            self.k0_dim = rgbnet_dim        # feature grid + shallow MLP (lib/dvgo.py:88-131)
+        if rgbnet_dim > 0:
             self.rgbnet_direct = rgbnet_direct
-            self.register_buffer('viewfreq', torch.FloatTensor([(2 ** i) for i in range(viewbase_pe)]))
-            if self.posbase_pe > 0:
-                self.register_buffer('posfreq', torch.FloatTensor([(2 ** i) for i in range(self.posbase_pe)]))
-                dim0 = (3 + 3 * viewbase_pe * 2) + (3 + 3 * self.posbase_pe * 2)
-            else:
-                dim0 = (3 + 3 * viewbase_pe * 2) + (self.k0_dim if rgbnet_direct else self.k0_dim - 3)
-            self.rgbnet = make_rgbnet(dim0, rgbnet_width, rgbnet_depth)
-        self.k0 = nn.Parameter(self._alloc_k0(ws))
-
-        # occupancy grid (lib/dvgo.py:135-153)
-        self.mask_cache_path = mask_cache_path
-        self.mask_cache_thres = mask_cache_thres
-        if mask_cache_path:
-            coarse = MaskCache(path=mask_cache_path, mask_cache_thres=mask_cache_thres)
-            mask = self._lookup_on_own_grid(coarse, ws)
-        else:
-            mask = torch.ones(ws, dtype=torch.bool)
-        self.mask_cache = MaskCache(path=None, mask=mask, xyz_min=self._xyz_min_cpu, xyz_max=self._xyz_max_cpu)
-        self._cfg_cache = {}
+        # what the MLP reads before the view embedding: the positions' encoding, or the k0 channels that are not diffuse colour
+        feat_dim = 3 + 3 * self.posbase_pe * 2 if self.posbase_pe > 0 else rgbnet_dim if rgbnet_direct else rgbnet_dim - 3
+        self._init_colour(ws, rgbnet_dim, feat_dim, viewbase_pe, rgbnet_width, rgbnet_depth)
+        if self.posbase_pe > 0:
+            self.register_buffer('posfreq', _freqs(self.posbase_pe))
+        self._init_mask_cache(ws, mask_cache_path, mask_cache_thres)
 
     # ------------------------------------------------------------------ sizing / bookkeeping
-    def _alloc_k0(self, ws, device=None):
-        g = torch.zeros([1, self.k0_dim, *ws], device=device)
-        if self.channels_last and self.k0_dim > 1:
-            g = g.contiguous(memory_format=torch.channels_last_3d)
-        return g
-
     def _set_grid_resolution(self, num_voxels):
         """lib/dvgo.py:155-165 (float32 tensor maths on the host)."""
         self.num_voxels = num_voxels
@@ -192,19 +104,6 @@ class DirectVoxGO(nn.Module):
             **self.rgbnet_kwargs,
         }
 
-    def _grid_xyz(self, ws, device):
-        return torch.stack(torch.meshgrid(
-            torch.linspace(float(self._xyz_min_cpu[0]), float(self._xyz_max_cpu[0]), ws[0], device=device),
-            torch.linspace(float(self._xyz_min_cpu[1]), float(self._xyz_max_cpu[1]), ws[1], device=device),
-            torch.linspace(float(self._xyz_min_cpu[2]), float(self._xyz_max_cpu[2]), ws[2], device=device),
-            indexing='ij'), -1)
-
-    def _lookup_on_own_grid(self, coarse, ws):
-        """Evaluate a coarse MaskCache at this model's voxel centres (lib/dvgo.py:143-148).
-        Needs the GPU (the lookup is a HIP op)."""
-        dev = torch.device('cuda', torch.cuda.current_device())
-        return coarse.to(dev)(self._grid_xyz(ws, dev)).cpu()
-
     # ------------------------------------------------------------------ grid maintenance (N4)
     @torch.no_grad()
     def maskout_near_cam_vox(self, cam_o, near):
@@ -223,23 +122,11 @@ class DirectVoxGO(nn.Module):
     def scale_volume_grid(self, num_voxels):
         """Progressive up-scaling (lib/dvgo.py:228-263)."""
         self._set_grid_resolution(num_voxels)
-        ws = tuple(int(v) for v in self.world_size)
-        self.density = nn.Parameter(F.interpolate(self.density.data, size=ws, mode='trilinear', align_corners=True))
-        if self.k0_dim > 0:
-            k0 = F.interpolate(self.k0.data.contiguous(), size=ws, mode='trilinear', align_corners=True)
-            if self.channels_last and self.k0_dim > 1:
-                k0 = k0.contiguous(memory_format=torch.channels_last_3d)
-            self.k0 = nn.Parameter(k0)
-        else:
-            self.k0 = nn.Parameter(self._alloc_k0(ws, device=self.density.device))
-        self_alpha = F.max_pool3d(self.activate_density(self.density), kernel_size=3, padding=1, stride=1)[0, 0]
-        mask = self_alpha > self.fast_color_thres
+        ws = self._resize_grids()
+        mask = self._alpha_mask()
         if self.mask_cache_path:
-            coarse = MaskCache(path=self.mask_cache_path, mask_cache_thres=self.mask_cache_thres).to(self.density.device)
-            mask = coarse(self._grid_xyz(ws, self.density.device)) & mask
-        self.mask_cache = MaskCache(path=None, mask=mask.cpu(), xyz_min=self._xyz_min_cpu,
-                                    xyz_max=self._xyz_max_cpu).to(self.density.device)
-        self._cfg_cache = {}
+            mask = self._coarse_mask(ws, self.density.device) & mask
+        self._set_mask_cache(mask)
 
     @torch.no_grad()
     def voxel_count_views(self, rays_o_tr, rays_d_tr, imsz, near, far, stepsize, downrate=1, irregular_shape=False):
@@ -266,28 +153,6 @@ class DirectVoxGO(nn.Module):
                 L.call('dvgo_view_count_commit', ptr(acc), ptr(count), _i64(X * Y * Z), st)
         return count
 
-    def density_total_variation_add_grad(self, weight, dense_mode, x_range=None):
-        """lib/dvgo.py:297-300"""
-        w = weight * float(self.world_size.max()) / 128
-        total_variation_add_grad(self.density, self.density.grad, w, w, w, dense_mode, x_range)
-
-    def k0_total_variation_add_grad(self, weight, dense_mode, x_range=None):
-        """lib/dvgo.py:302-305"""
-        w = weight * float(self.world_size.max()) / 128
-        total_variation_add_grad(self.k0, self.k0.grad, w, w, w, dense_mode, x_range)
-
-    # ------------------------------------------------------------------ op wrappers
-    def activate_density(self, density, interval=None):
-        """lib/dvgo.py:307-310"""
-        interval = interval if interval is not None else self.voxel_size_ratio
-        shape = density.shape
-        return Raw2Alpha.apply(density.flatten().contiguous(), self.act_shift, interval).reshape(shape)
-
-    def grid_sampler(self, xyz, *grids, **_unused):
-        """lib/dvgo.py:312-328 (bilinear branch)."""
-        ret = [grid_sample(g, xyz, self.xyz_min, self.xyz_max) for g in grids]
-        return ret[0] if len(ret) == 1 else ret
-
     def hit_coarse_geo(self, rays_o, rays_d, near, far, stepsize, **render_kwargs):
         """Rays with at least one sample in known-occupied space (lib/dvgo.py:412-423)."""
         shape = rays_o.shape[:-1]
@@ -313,50 +178,13 @@ class DirectVoxGO(nn.Module):
         mask_inbbox = ~mask_outbbox
         return ray_pts[mask_inbbox], ray_id[mask_inbbox], step_id[mask_inbbox]
 
-    # ------------------------------------------------------------------ colour head
-    def _shade(self, k0, viewdirs, ray_id, m_dev=None):
-        """lib/dvgo.py:512-541 (bilinear / non-implicit branches)."""
-        if self.rgbnet is None:
-            return torch.sigmoid(k0)
-        if self.rgbnet_direct:
-            k0_view = k0
-        else:
-            k0_view = k0[:, 3:]
-            k0_diffuse = k0[:, :3]
-        if self.fused and self.fused_shade and viewdirs.is_cuda and viewdirs.dim() == 2:
-            rgb = shade(self.rgbnet, k0, viewdir_embed(viewdirs, self.viewfreq), ray_id, diffuse=not self.rgbnet_direct,
-                        m_dev=m_dev)
-            if rgb is not None:
-                return rgb
-        assert m_dev is None, 'capacity mode needs the fused colour head'      # (torch ops would run over undefined rows)
-        viewdirs_emb = (viewdirs.unsqueeze(-1) * self.viewfreq).flatten(-2)
-        viewdirs_emb = torch.cat([viewdirs, viewdirs_emb.sin(), viewdirs_emb.cos()], -1)
-        viewdirs_emb = viewdirs_emb.flatten(0, -2)[ray_id]
-        rgb_logit = mlp_forward(self.rgbnet, torch.cat([k0_view, viewdirs_emb], -1))
-        if self.rgbnet_direct:
-            return torch.sigmoid(rgb_logit)
-        return torch.sigmoid(rgb_logit + k0_diffuse)
-
+    # ------------------------------------------------------------------ colour head and forward (H2)
     @property
     def uses_posenc(self):
         """True when the colour head reads the positional encoding of the sample positions and not k0 (posbase_pe > 0,
         fine stage): k0 then gets no gradient and is never updated."""
         return self.rgbnet is not None and self.posbase_pe > 0
 
-    def _shade_posenc(self, pts, viewdirs, ray_id):
-        """lib/dvgo.py:524-534 (posbase_pe > 0): rgb from the positions' encoding and the view embedding, no diffuse term."""
-        if self.fused and self.fused_shade and viewdirs.is_cuda and viewdirs.dim() == 2:
-            rgb = shade_posenc(self.rgbnet, pts, viewdir_embed(viewdirs, self.viewfreq), ray_id, self.posfreq)
-            if rgb is not None:
-                return rgb
-        viewdirs_emb = (viewdirs.unsqueeze(-1) * self.viewfreq).flatten(-2)
-        viewdirs_emb = torch.cat([viewdirs, viewdirs_emb.sin(), viewdirs_emb.cos()], -1)
-        viewdirs_emb = viewdirs_emb.flatten(0, -2)[ray_id]
-        pos_emb = (pts.unsqueeze(-1) * self.posfreq).flatten(-2)
-        pos_emb = torch.cat([pts, pos_emb.sin(), pos_emb.cos()], -1)
-        return torch.sigmoid(mlp_forward(self.rgbnet, torch.cat([pos_emb, viewdirs_emb], -1)))
-
-    # ------------------------------------------------------------------ forward (H2)
     def _march_cfg(self, near, far, stepsize):
         key = (float(near), float(far), float(stepsize))
         cfg = self._cfg_cache.get(key)
@@ -371,81 +199,7 @@ class DirectVoxGO(nn.Module):
             self._cfg_cache[key] = cfg
         return cfg
 
-    def forward(self, rays_o, rays_d, viewdirs, global_step=None, **render_kwargs):
-        """Volume rendering (lib/dvgo.py:450-577).  Returns the reference's dict:
-        alphainv_last [N], weights [M], rgb_marched [N,3], raw_alpha [M], raw_rgb [M,3], ray_id [M]
-        (+ depth [N] when render_kwargs['render_depth'])."""
-        assert len(rays_o.shape) == 2 and rays_o.shape[-1] == 3, 'Only suuport point queries in [N, 3] format'
-        if self.fused:
-            return self._forward_fused(rays_o, rays_d, viewdirs, **render_kwargs)
-        return self._forward_unfused(rays_o, rays_d, viewdirs, global_step, **render_kwargs)
-
     def can_keep_count_on_device(self):
         """True when `forward(..., _capacity=True)` is available: the fused march with the fused colour head."""
-        from .shade import head_layers
         return bool(self.fused and self.fused_shade and self.rgbnet is not None and not self.uses_posenc
                     and head_layers(self.rgbnet) is not None)
-
-    def _forward_fused(self, rays_o, rays_d, viewdirs, near, far, stepsize, bg, render_depth=False, _capacity=False,
-                       **_unused):
-        """`_capacity` (training step only, train.py): no host synchronisation -- the per-sample outputs are allocated at
-        their upper bound, only their first `ret['n_samples']` rows (a device scalar) are defined, and every kernel
-        downstream reads that count from the device."""
-        N = len(rays_o)
-        cfg = self._march_cfg(near, far, stepsize)
-        _capacity = bool(_capacity) and self.can_keep_count_on_device() and viewdirs.is_cuda and viewdirs.dim() == 2
-        if self.uses_posenc:
-            # the march writes the kept samples' positions where it would write their k0 features; k0 is not read
-            weights, alpha, alphainv_last, pts, ray_id, step_id, off3 = fused_march(
-                self.density, self.k0.detach()[:, :0], rays_o, rays_d, cfg, positions=True)
-            m_dev = None
-            rgb = self._shade_posenc(pts, viewdirs, ray_id)
-        else:
-            weights, alpha, alphainv_last, k0, ray_id, step_id, off3 = fused_march(
-                self.density, self.k0, rays_o, rays_d, cfg, capacity=_capacity)
-            m_dev = off3[N:] if _capacity else None
-            rgb = self._shade(k0, viewdirs, ray_id, m_dev)
-        rgb_marched = composite(weights, rgb, alphainv_last, ray_id, off3, bg, m_dev)
-        ret = {'alphainv_last': alphainv_last, 'weights': weights, 'rgb_marched': rgb_marched,
-               'raw_alpha': alpha, 'raw_rgb': rgb, 'ray_id': ray_id}
-        if _capacity:
-            ret['n_samples'] = m_dev
-        if render_depth:
-            ret['depth'] = composite_depth(weights.detach(), step_id, off3, N)
-        return ret
-
-    def _forward_unfused(self, rays_o, rays_d, viewdirs, global_step=None, **render_kwargs):
-        """The reference's op sequence (lib/dvgo.py:458-577) on the drop-in ops."""
-        N = len(rays_o)
-        ray_pts, ray_id, step_id = self.sample_ray(rays_o=rays_o, rays_d=rays_d,
-                                                   is_train=global_step is not None, **render_kwargs)
-        interval = render_kwargs['stepsize'] * self.voxel_size_ratio
-        if self.mask_cache is not None:                      # skip known free space
-            mask = self.mask_cache(ray_pts)
-            ray_pts, ray_id, step_id = ray_pts[mask], ray_id[mask], step_id[mask]
-        density = self.grid_sampler(ray_pts, self.density)  # post-activated alpha
-        alpha = self.activate_density(density, interval)
-        if self.fast_color_thres > 0:
-            mask = alpha > self.fast_color_thres
-            ray_pts, ray_id, step_id = ray_pts[mask], ray_id[mask], step_id[mask]
-            alpha = alpha[mask]
-        weights, alphainv_last = Alphas2Weights.apply(alpha, ray_id, N)
-        if self.fast_color_thres > 0:
-            mask = weights > self.fast_color_thres
-            weights, alpha = weights[mask], alpha[mask]
-            ray_pts, ray_id, step_id = ray_pts[mask], ray_id[mask], step_id[mask]
-        if self.uses_posenc:       # (the reference also interpolates k0 here and never uses the result: skipped)
-            rgb = self._shade_posenc(ray_pts, viewdirs, ray_id)
-        else:
-            k0 = self.grid_sampler(ray_pts, self.k0)
-            rgb = self._shade(k0, viewdirs, ray_id)
-        rgb_marched = segment_coo(src=(weights.unsqueeze(-1) * rgb), index=ray_id,
-                                  out=torch.zeros([N, 3], device=rays_o.device), reduce='sum')
-        rgb_marched = rgb_marched + alphainv_last.unsqueeze(-1) * render_kwargs['bg']
-        ret = {'alphainv_last': alphainv_last, 'weights': weights, 'rgb_marched': rgb_marched,
-               'raw_alpha': alpha, 'raw_rgb': rgb, 'ray_id': ray_id}
-        if render_kwargs.get('render_depth', False):
-            with torch.no_grad():
-                ret['depth'] = segment_coo(src=(weights * step_id), index=ray_id,
-                                           out=torch.zeros([N], device=rays_o.device), reduce='sum')
-        return ret

@@ -204,7 +204,7 @@ def vertex_colors(model, verts, normals):
     """model._shade of k0 at the vertices, seen head-on from outside (view direction -normal) -> [V,3] in [0,1].
     A positional-encoding model (posbase_pe > 0) colours from the vertex positions themselves; its k0 is not read."""
     out = torch.empty((verts.shape[0], 3), dtype=torch.float32, device=verts.device)
-    posenc = getattr(model, 'uses_posenc', False)
+    posenc = model.uses_posenc
     for i in range(0, verts.shape[0], COLOR_CHUNK):
         v, nrm = verts[i:i + COLOR_CHUNK], normals[i:i + COLOR_CHUNK]
         rid = torch.arange(v.shape[0], device=v.device)

@@ -10,7 +10,6 @@
 No CLI, config files, logging to disk or dataset I/O: those are out of scope.
 """
 import torch
-import torch.nn.functional as F
 
 from .render import batch_indices_generator
 from .train import TrainStep, create_optimizer_or_freeze_model
@@ -64,8 +63,7 @@ def fit_stage(model, rays_o, rays_d, viewdirs, target, cfg_train, render_kwargs,
     for global_step in range(1, n_iters + 1):
         if model.mask_cache is not None and (global_step + 500) % 1000 == 0:
             with torch.no_grad():
-                self_alpha = F.max_pool3d(model.activate_density(model.density), kernel_size=3, padding=1, stride=1)[0, 0]
-                model.mask_cache.mask &= (self_alpha > model.fast_color_thres)
+                model.mask_cache.mask &= model._alpha_mask()
         if global_step in pg_scale:
             n_rest = len(pg_scale) - pg_scale.index(global_step) - 1
             _scale_volume_grid(model, int(num_voxels_final / (2 ** n_rest)))

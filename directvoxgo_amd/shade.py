@@ -70,7 +70,6 @@ class defer_wgrad:
 @torch.no_grad()
 def viewdir_embed(viewdirs, viewfreq):
     """cat([v, sin(v (x) freq), cos(v (x) freq)]) of lib/dvgo.py:524-525 in one launch -> [N, 3 + 6F]."""
-    from ._lib import _flt  # noqa: F401
     N, F = viewdirs.shape[0], viewfreq.shape[0]
     emb = torch.empty((N, 3 + 6 * F), dtype=torch.float32, device=viewdirs.device)
     with L.device_of(viewdirs):
@@ -93,6 +92,27 @@ def _scratch(width, device):
     lib = L.lib()
     n = int(lib.dvgo_shade_scratch_bytes(int(width)))
     return torch.empty(n, dtype=torch.uint8, device=device) if n > 0 else None
+
+
+def _unpack_record(tot, width, d_in):
+    """The compact weight-gradient record of include/dvgo_hip.h -> (gW1, gb1, gW2, gb2, gW3, gb3), views of it."""
+    o = 0
+    gW2 = tot[o:o + width * width].view(width, width); o += width * width
+    gW1 = tot[o:o + width * d_in].view(width, d_in); o += width * d_in
+    gW3 = tot[o:o + 3 * width].view(3, width); o += 3 * width
+    gb1, gb2, gb3 = tot[o:o + width], tot[o + width:o + 2 * width], tot[o + 2 * width:o + 2 * width + 3]
+    return gW1, gb1, gW2, gb2, gW3, gb3
+
+
+def _weight_grads(params, wgrad, device, k, n, g_first=None):
+    """What a colour head's backward returns: `n` gradients, the first input's `g_first`, and at k..k+5 those of the six
+    parameters -- from `wgrad()` run now, or None when an active `defer_wgrad` takes the closure."""
+    grads = [g_first] + [None] * (n - 1)
+    if defer_wgrad._active is not None:
+        defer_wgrad._active.submit(params, wgrad, device)
+    else:
+        grads[k:k + 6] = wgrad()
+    return tuple(grads)
 
 
 class _Shade(torch.autograd.Function):
@@ -155,19 +175,9 @@ class _Shade(torch.autograd.Function):
                 L.call('dvgo_shade_wgrad', ptr(G1), ptr(gz), ptr(masks), ptr(W3.contiguous()), ptr(H1), ptr(H2), ptr(feat), _int(C), ptr(emb),
                        _int(emb.shape[1]), ptr(ray_id), _i64(M), ptr(m_dev), _int(width), _int(1 if diffuse else 0), _int(n_parts),
                        ptr(part), ptr(tot), stream_of(feat))
-            o = 0                                # the compact record of include/dvgo_hip.h: the gradients are views of it
-            gW2 = tot[o:o + width * width].view(width, width); o += width * width
-            gW1 = tot[o:o + width * d_in].view(width, d_in); o += width * d_in
-            gW3 = tot[o:o + 3 * width].view(3, width); o += 3 * width
-            gb1, gb2, gb3 = tot[o:o + width], tot[o + width:o + 2 * width], tot[o + 2 * width:o + 2 * width + 3]
-            return gW1, gb1, gW2, gb2, gW3, gb3
+            return _unpack_record(tot, width, d_in)
 
-        gf = g_feat if ctx.needs_input_grad[0] else None
-        if defer_wgrad._active is not None:
-            defer_wgrad._active.submit(ctx.params, wgrad, feat.device)
-            return (gf, None, None, None, None, None, None, None, None, None, None, None)
-        gW1, gb1, gW2, gb2, gW3, gb3 = wgrad()
-        return (gf, None, None, gW1, gb1, gW2, gb2, gW3, gb3, None, None, None)
+        return _weight_grads(ctx.params, wgrad, feat.device, 3, 12, g_feat if ctx.needs_input_grad[0] else None)
 
 
 def shade(rgbnet, feat, emb, ray_id, diffuse, m_dev=None):
@@ -249,8 +259,7 @@ class _ShadePosenc(torch.autograd.Function):
                    ptr(W3.contiguous()), _int(width), ptr(G1), ptr(gz), stream_of(pts))
 
         def wgrad():
-            lib = L.lib()
-            rec = int(lib.dvgo_shade_pe_record_size(width, d_in))
+            rec = int(L.lib().dvgo_shade_pe_record_size(width, d_in))
             n_parts = max(1, min(N_PARTS, (M + 31) // 32))
             part = torch.empty((n_parts, rec), dtype=torch.float32, device=pts.device)
             tot = torch.empty(rec, dtype=torch.float32, device=pts.device)
@@ -258,18 +267,9 @@ class _ShadePosenc(torch.autograd.Function):
                 L.call('dvgo_shade_pe_wgrad', ptr(G1), ptr(gz), ptr(masks), ptr(W3.contiguous()), ptr(H1), ptr(H2), ptr(pts),
                        ptr(freq), _int(freq.shape[0]), ptr(emb), _int(emb.shape[1]), ptr(ray_id), _i64(M), _int(width),
                        _int(d_in), _int(n_parts), ptr(part), ptr(tot), stream_of(pts))
-            o = 0                                # the compact record of include/dvgo_hip.h: the gradients are views of it
-            gW2 = tot[o:o + width * width].view(width, width); o += width * width
-            gW1 = tot[o:o + width * d_in].view(width, d_in); o += width * d_in
-            gW3 = tot[o:o + 3 * width].view(3, width); o += 3 * width
-            gb1, gb2, gb3 = tot[o:o + width], tot[o + width:o + 2 * width], tot[o + 2 * width:o + 2 * width + 3]
-            return gW1, gb1, gW2, gb2, gW3, gb3
+            return _unpack_record(tot, width, d_in)
 
-        if defer_wgrad._active is not None:
-            defer_wgrad._active.submit(ctx.params, wgrad, pts.device)
-            return (None,) * 11
-        gW1, gb1, gW2, gb2, gW3, gb3 = wgrad()
-        return (None, None, None, None, gW1, gb1, gW2, gb2, gW3, gb3, None)
+        return _weight_grads(ctx.params, wgrad, pts.device, 4, 11)
 
 
 def shade_posenc(rgbnet, pts, emb, ray_id, posfreq):

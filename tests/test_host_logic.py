@@ -280,3 +280,55 @@ def test_optimizer_state_is_saved_in_the_reference_layout_and_relaid_on_resume(t
     load_checkpoint(m2, opt2, p)
     st2 = opt2._state_of(m2.k0)
     assert st2['step'] == 4 and st2['exp_avg'].stride() == m2.k0.stride() and torch.equal(st2['exp_avg'], st['exp_avg'])
+
+
+_GRID_KEYS = ['density', 'k0']
+_HEAD_KEYS = ['viewfreq', 'rgbnet.0.weight', 'rgbnet.0.bias', 'rgbnet.2.0.weight', 'rgbnet.2.0.bias', 'rgbnet.3.weight',
+              'rgbnet.3.bias']
+_MASK_KEYS = ['mask_cache.mask', 'mask_cache.xyz2ijk_scale', 'mask_cache.xyz2ijk_shift']
+_DVGO_KWARGS = {'act_shift', 'alpha_init', 'fast_color_thres', 'mask_cache_path', 'mask_cache_thres', 'num_voxels',
+                'num_voxels_base', 'rgbnet_depth', 'rgbnet_dim', 'rgbnet_direct', 'rgbnet_full_implicit', 'rgbnet_width',
+                'viewbase_pe', 'voxel_size_ratio', 'xyz_max', 'xyz_min'}
+_MODEL_LAYOUTS = {          # class -> (box buffers in state_dict order, get_kwargs() keys), recorded before VoxelModel existed
+    'DirectVoxGO': (['xyz_min', 'xyz_max'], _DVGO_KWARGS),
+    'DirectMPIGO': (['xyz_min', 'xyz_max'],
+                    {'act_shift', 'fast_color_thres', 'mask_cache_path', 'mask_cache_thres', 'mpi_depth', 'num_voxels',
+                     'rgbnet_depth', 'rgbnet_dim', 'rgbnet_width', 'viewbase_pe', 'voxel_size_ratio', 'xyz_max', 'xyz_min'}),
+    'DirectContractedVoxGO': (['scene_center', 'scene_radius', 'xyz_min', 'xyz_max'],
+                              (_DVGO_KWARGS - {'mask_cache_path', 'mask_cache_thres', 'rgbnet_full_implicit'})
+                              | {'bg_len', 'contracted_norm', 'mask_cache_world_size'}),
+}
+
+
+@pytest.mark.parametrize('with_head', [False, True])
+@pytest.mark.parametrize('name', sorted(_MODEL_LAYOUTS))
+def test_scene_models_share_a_base_and_keep_their_checkpoint_layout(name, with_head):
+    """The three scene models are VoxelModels; their state_dict key ORDER, get_kwargs() keys and the rebuild from
+    get_kwargs() are what they were as three independent modules (the literals above were taken from those)."""
+    from directvoxgo_amd.checkpoint import model_kwargs_of
+    from directvoxgo_amd.dcvgo import DirectContractedVoxGO
+    from directvoxgo_amd.dmpigo import DirectMPIGO
+    from directvoxgo_amd.dvgo import DirectVoxGO
+    from directvoxgo_amd.voxel_model import VoxelModel
+    cls = {'DirectVoxGO': DirectVoxGO, 'DirectMPIGO': DirectMPIGO, 'DirectContractedVoxGO': DirectContractedVoxGO}[name]
+    kw = dict(fast_color_thres=1e-4, rgbnet_width=16)
+    if cls is DirectMPIGO:
+        kw.update(num_voxels=9 * 9 * 8, mpi_depth=8, viewbase_pe=2, rgbnet_dim=9 if with_head else 0)
+    else:
+        kw.update(num_voxels=9 ** 3, num_voxels_base=9 ** 3, alpha_init=1e-2, rgbnet_dim=12 if with_head else 0)
+    torch.manual_seed(0)
+    m = cls([-1, -1, -1], [1, 1, 1], **kw)
+    assert isinstance(m, VoxelModel)
+    box, kwargs_keys = _MODEL_LAYOUTS[name]
+    assert list(m.state_dict()) == _GRID_KEYS + box + (_HEAD_KEYS if with_head else []) + _MASK_KEYS
+    assert set(m.get_kwargs()) == kwargs_keys
+    assert m.world_size.tolist() == ([9, 9, 8] if cls is DirectMPIGO else [9, 9, 9])
+    if cls is DirectContractedVoxGO:      # its constructor takes no **kwargs: the derived entries go the way load_model drops them
+        m2 = cls(**model_kwargs_of({'model_kwargs': m.get_kwargs()}))
+    else:
+        m2 = type(m)(**m.get_kwargs())
+    m2.load_state_dict(m.state_dict())
+    for (k, a), (k2, b) in zip(m.state_dict().items(), m2.state_dict().items()):
+        assert k == k2 and torch.equal(a, b), k
+    # DirectMPIGO and DirectContractedVoxGO by VoxelModel's defaults; this DirectVoxGO: no posbase_pe, and a 16-wide head
+    assert m.uses_posenc is False and m.can_keep_count_on_device() is False
