@@ -157,6 +157,10 @@ def _check_model(model):
     from .dcvgo import DirectContractedVoxGO
     from .dmpigo import DirectMPIGO
     from .dvgo import DirectVoxGO
+    from .triplane import TriPlaneVoxGO
+    if isinstance(model, TriPlaneVoxGO):
+        raise NotImplementedError('extract_mesh: colouring the vertices of a TriPlaneVoxGO (features from planes, no k0) is '
+                                  'not built; only DirectVoxGO is supported')
     if isinstance(model, DirectContractedVoxGO):
         raise NotImplementedError('extract_mesh: DirectContractedVoxGO grids live in contracted space (a non-linear warp '
                                   'of the unbounded scene); only DirectVoxGO is supported')

@@ -6,6 +6,7 @@ saved-tensor conventions) on top of the HIP kernels:
   Raw2Alpha, Alphas2Weights   lib/dvgo.py:618-660
   MaskCache                   lib/dvgo.py:583-613
   grid_sample                 lib/dvgo.py:312-328 (grid_sampler -> F.grid_sample + its backward)
+  triplane_sample             lib/tri_dvgo.py:456-469 (grid_sampler2D -> three F.grid_sample, cat or sum, + backward)
   segment_coo                 torch_scatter.segment_coo(src, index, out, reduce='sum')
   total_variation_add_grad    lib/cuda/total_variation.cpp:16-24
 """
@@ -114,6 +115,121 @@ def grid_sample(grid, xyz, xyz_min, xyz_max):
     if out.shape[-1] == 1:
         out = out.squeeze(-1)
     return out
+
+
+PLANE_KEYS = ('xy', 'yz', 'zx')
+# Planes that are not channels-last are handed to the kernels as channels-last copies (and their gradients scattered
+# into channels-last buffers) once the samples outnumber the largest plane's texels: the copies are three passes over a
+# few MB, and the kernels' 16-byte texel loads and contiguous atomic runs need that layout.  Below it the kernels run on
+# the strides as given (they take either layout); tests set it to run a given layout through them.
+TRIPLANE_RELAYOUT = True
+
+
+def _plane_geom(plane, name):
+    """plane [1,C,H,W] (any dense strides) -> (H, W, sC, sH, sW) in elements."""
+    if plane.dim() != 4 or plane.shape[0] != 1:
+        raise RuntimeError(f'{name} must be [1,C,H,W]')
+    if not plane.is_cuda:
+        raise RuntimeError(f'{name} must be a CUDA tensor')
+    check_f32(plane, name)
+    _, _, H, W = plane.shape
+    _, sC, sH, sW = plane.stride()
+    return H, W, sC, sH, sW
+
+
+def _plane_list(planes):
+    if isinstance(planes, dict) or hasattr(planes, 'keys'):
+        return [planes[k] for k in PLANE_KEYS]
+    planes = list(planes)
+    if len(planes) != 3:
+        raise ValueError("planes: a dict with the keys 'xy', 'yz', 'zx' or a sequence of three")
+    return planes
+
+
+def triplane_fwd(planes, xyz, xyz_min, xyz_max, aggregation='concat'):
+    """dvgo_triplane_fwd on the planes' strides as they are: xyz [M,3] -> [M,3C] (concat) or [M,C] (sum).  No autograd."""
+    if aggregation not in ('concat', 'sum'):
+        raise ValueError(f"aggregation must be 'concat' or 'sum', got {aggregation!r}")
+    planes = _plane_list(planes)
+    geoms = [_plane_geom(p, k) for p, k in zip(planes, PLANE_KEYS)]
+    C = planes[0].shape[1]
+    if any(p.shape[1] != C for p in planes):
+        raise RuntimeError('the three planes must share their channel count')
+    check_input(xyz, 'xyz'); check_f32(xyz, 'xyz')
+    M = xyz.shape[0]
+    out = torch.empty((M, C if aggregation == 'sum' else 3 * C), dtype=torch.float32, device=xyz.device)
+    (Ha, Wa, ca, ha, wa), (Hb, Wb, cb, hb, wb), (Hc, Wc, cc, hc, wc) = geoms
+    with L.device_of(xyz):
+        L.call('dvgo_triplane_fwd', planes[0], Ha, Wa, ca, ha, wa, planes[1], Hb, Wb, cb, hb, wb, planes[2], Hc, Wc, cc, hc, wc,
+               C, xyz, xyz_min, xyz_max, M, 1 if aggregation == 'sum' else 0, out, stream_of(xyz))
+    return out
+
+
+def triplane_bwd(grad_out, grads, xyz, xyz_min, xyz_max, aggregation='concat', run=0):
+    """dvgo_triplane_bwd: accumulates into the three buffers `grads` (shaped and strided like planes) in place.
+    `run`: samples a lane merges before its atomics (0: the library's default)."""
+    grads = _plane_list(grads)
+    geoms = [_plane_geom(p, k) for p, k in zip(grads, PLANE_KEYS)]
+    C = grads[0].shape[1]
+    check_input(grad_out, 'grad_out'); check_f32(grad_out, 'grad_out')
+    M = xyz.shape[0]
+    if tuple(grad_out.shape) != (M, C if aggregation == 'sum' else 3 * C):
+        raise RuntimeError('grad_out has the wrong shape')
+    (Ha, Wa, ca, ha, wa), (Hb, Wb, cb, hb, wb), (Hc, Wc, cc, hc, wc) = geoms
+    with L.device_of(xyz):
+        L.call('dvgo_triplane_bwd', grad_out, grads[0], Ha, Wa, ca, ha, wa, grads[1], Hb, Wb, cb, hb, wb, grads[2], Hc, Wc, cc,
+               hc, wc, C, xyz, xyz_min, xyz_max, M, 1 if aggregation == 'sum' else 0, int(run), stream_of(xyz))
+    return grads
+
+
+def _is_channels_last(p):
+    return p.stride(1) == 1 or p.shape[1] == 1
+
+
+class _TriPlaneSample(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, xy, yz, zx, xyz, xyz_min, xyz_max, aggregation):
+        planes = [xy, yz, zx]
+        M = xyz.shape[0]
+        relayout = TRIPLANE_RELAYOUT and M >= max(p.shape[2] * p.shape[3] for p in planes)
+        ctx.relayout = [relayout and not _is_channels_last(p) for p in planes]
+        kp = [p.contiguous(memory_format=torch.channels_last) if r else p for p, r in zip(planes, ctx.relayout)]
+        out = triplane_fwd(kp, xyz, xyz_min, xyz_max, aggregation)
+        ctx.save_for_backward(xyz, xyz_min, xyz_max)
+        ctx.meta = planes
+        ctx.aggregation = aggregation
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        xyz, xyz_min, xyz_max = ctx.saved_tensors
+        grads = [None, None, None]
+        if any(ctx.needs_input_grad[:3]):
+            # zero-filled, with the strides of the plane (or channels-last where the kernel was handed a copy); a plane
+            # that wants no gradient still gets a buffer: the launch scatters into all three
+            grads = [torch.zeros_like(p, memory_format=torch.channels_last if r else torch.preserve_format)
+                     for p, r in zip(ctx.meta, ctx.relayout)]
+            triplane_bwd(grad_out.contiguous(), grads, xyz, xyz_min, xyz_max, ctx.aggregation)
+            grads = [g if need else None for g, need in zip(grads, ctx.needs_input_grad[:3])]
+        return grads[0], grads[1], grads[2], None, None, None, None
+
+
+def triplane_sample(planes, xyz, xyz_min, xyz_max, aggregation='concat'):
+    """The reference's grid_sampler2D (lib/tri_dvgo.py:456-469) as one HIP op: `planes` is a dict with the keys 'xy',
+    'yz', 'zx' (or the three in that order), each [1,C,H,W] float32 of any size and dense layout; xyz [...,3] world
+    coordinates -> [...,3C] ('concat': xy, yz, zx) or [...,C] ('sum': (xy + yz) + zx).  Plane xy has its rows along world
+    y and its columns along z, yz rows x / columns y, zx rows z / columns x (the reference's flipped ind_norm).
+    Differentiable w.r.t. the planes only."""
+    if aggregation not in ('concat', 'sum'):
+        raise ValueError(f"aggregation must be 'concat' or 'sum', got {aggregation!r}")
+    xy, yz, zx = _plane_list(planes)
+    for p, k in zip((xy, yz, zx), PLANE_KEYS):
+        _plane_geom(p, k)
+    shape = xyz.shape[:-1]
+    flat = xyz.reshape(-1, 3).contiguous()
+    out = _TriPlaneSample.apply(xy, yz, zx, flat, xyz_min.contiguous(), xyz_max.contiguous(), aggregation)
+    return out.reshape(*shape, out.shape[-1])
 
 
 class MaskCache(nn.Module):

@@ -187,7 +187,11 @@ class TrainStep:
         self.world = dist.get_world_size(process_group) if (dist.is_available() and dist.is_initialized()) else 1
         # a positional-encoding colour head (posbase_pe > 0) reads no k0: only the density grid gets a gradient, so the
         # paths that take both grids' gradients together (brick scatter with the fused Adam, combined gradient rows) stay off
-        self.k0_idle = bool(getattr(model, 'uses_posenc', False))
+        no_k0 = getattr(model, 'k0', None) is None           # TriPlaneVoxGO: the colour features come from planes, not a grid
+        self.k0_idle = bool(getattr(model, 'uses_posenc', False)) or no_k0
+        if no_k0 and self.world > 1:
+            raise NotImplementedError('data-parallel training of a model without k0 (TriPlaneVoxGO) is not built: train it on '
+                                      'one GPU')
         if self.k0_idle and self.world > 1:
             raise NotImplementedError('data-parallel training of a posbase_pe model (positional-encoding colour head) is not '
                                       'built: train it on one GPU')

@@ -1,0 +1,209 @@
+"""TriPlaneVoxGO: the reference fork's tri-plane scene model (lib/tri_dvgo.py:36-809), bilinear path, on the MI355X kernels.
+
+The density grid stays 3-D; colour features come from three 2-D feature planes.  Each plane is sampled bilinearly at two
+of a sample's three coordinates and the three results are concatenated (`tri_aggregation='concat'`, 3 * rgbnet_dim
+features) or summed ('sum', rgbnet_dim features) -- lib/tri_dvgo.py:456-469, here one HIP op (ops.triplane_sample,
+csrc/triplane.hip) -- and feed the shallow MLP exactly as k0 features do in DirectVoxGO (lib/tri_dvgo.py:746-783).
+
+Axis mapping (the reference's own: its ind_norm is the flipped coordinate triple and grid_sample's first grid component
+addresses W):   plane 'xy': rows y, columns z;   'yz': rows x, columns y;   'zx': rows z, columns x.
+
+In the reference the planes come out of an image encoder per call (`encode_feat`); the encoder, its `Mapping` network and
+the pose anchors are not part of this model.  `render(feats, ...)` takes such planes from the caller, gradients flow
+into them; `forward(...)` renders the model's own planes, `self.planes` (an nn.ParameterDict, zero-initialised, trained
+through `lrate_planes`).  There is no k0, as in the reference.
+
+Two execution paths produce the same dict and call the same sampler on bit-equal positions:
+  fused=True   fused_march(positions=True) -> triplane_sample -> colour head -> composite;
+  fused=False  the reference's op sequence on the drop-in ops.
+"""
+import numpy as np
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+
+from .dvgo import DirectVoxGO
+from .fused import composite, composite_depth, fused_march
+from .ops import PLANE_KEYS, Alphas2Weights, triplane_sample
+from .train import FINE_TRAIN
+from .voxel_model import VoxelModel, _freqs, _result, make_rgbnet
+
+# which world axis the rows (H) and the columns (W) of each plane follow
+PLANE_AXES = {'xy': (1, 2), 'yz': (0, 1), 'zx': (2, 0)}
+
+# configs/tri_default.py's fine stage on this model: the planes are trained like the feature grid they replace
+TRI_FINE_TRAIN = dict(FINE_TRAIN, lrate_planes=1e-1, skip_zero_grad_fields=['density'])
+
+_OUT_OF_SCOPE = {
+    'implicit_voxel_feat': 'the LIIF-style implicit plane decoder (Interp_MLP per plane) is not built: only the bilinear path is',
+    'liif': 'LIIF local-ensemble decoding belongs to implicit_voxel_feat, which is not built',
+    'feat_unfold': 'the 3x3 feature unfolding belongs to implicit_voxel_feat, which is not built',
+    'cell_decode': 'cell decoding belongs to implicit_voxel_feat, which is not built',
+    'global_cell_decode': 'appending the cell size to the features is not built',
+    'feat_fourier': 'the Fourier embedding of the features is not built',
+    'feat_pe': 'the positional encoding of the features (feat_fourier) is not built',
+    'rgbnet_full_implicit': 'the reference forward reads k0 before assigning it (lib/tri_dvgo.py:728-752): no behaviour to reproduce',
+}
+
+
+class TriPlaneVoxGO(DirectVoxGO):
+    """A VoxelModel (through DirectVoxGO, whose sampler, march configuration, occupancy and density maintenance it keeps)
+    without k0: the colour features are `triplane_sample(planes, pts)`."""
+
+    rgbnet_direct = False
+    posbase_pe = 0
+    uses_posenc = False
+    k0_dim = 0
+
+    def __init__(self, xyz_min, xyz_max, num_voxels=0, num_voxels_base=0, alpha_init=None,
+                 mask_cache_path=None, mask_cache_thres=1e-3, fast_color_thres=0,
+                 rgbnet_dim=6, rgbnet_direct=False, rgbnet_depth=3, rgbnet_width=128, viewbase_pe=4,
+                 tri_aggregation='concat', plane_size=None, channels_last=True, fused=True, verbose=False, **kwargs):
+        VoxelModel.__init__(self)
+        for key, why in _OUT_OF_SCOPE.items():
+            if kwargs.get(key):
+                raise NotImplementedError(f'{key}: {why}')
+        if kwargs.get('posbase_pe', 0) > 0 and (kwargs.get('cat_posemb') or kwargs.get('no_voxel_feat')):
+            raise NotImplementedError('cat_posemb / no_voxel_feat with posbase_pe > 0: the positional embedding beside or '
+                                      'instead of the plane features is not built')
+        for key in ('name', 'n_feats', 'n_resblocks', 'pretrained_state_dict', 'map_depth', 'map_width'):
+            if key in kwargs:
+                raise NotImplementedError(f'{key}: the image encoder, its Mapping network and the pose anchors are not part '
+                                          'of this model; pass their planes to render(feats, ...)')
+        if rgbnet_dim <= 0:
+            raise NotImplementedError('rgbnet_dim <= 0: the reference has no colour-only tri-plane model (lib/tri_dvgo.py:189-190)')
+        if tri_aggregation not in ('concat', 'sum'):
+            raise ValueError(f"tri_aggregation must be 'concat' or 'sum', got {tri_aggregation!r}")
+        self.verbose = verbose
+        self.fused = bool(fused)
+        self.fused_shade = True
+        self.channels_last = bool(channels_last)
+        self._set_box(xyz_min, xyz_max)
+        self.fast_color_thres = fast_color_thres
+
+        # lib/tri_dvgo.py:124-134
+        self.num_voxels_base = num_voxels_base
+        self.voxel_size_base = ((self._xyz_max_cpu - self._xyz_min_cpu).prod() / self.num_voxels_base).pow(1 / 3)
+        self.alpha_init = alpha_init
+        self.act_shift = np.log(1 / (1 - alpha_init) - 1)
+        self._set_grid_resolution(num_voxels)
+        ws = [int(v) for v in self.world_size]
+        self.density = nn.Parameter(torch.zeros([1, 1, *ws]))
+
+        self.tri_aggregation = tri_aggregation
+        self.rgbnet_dim = int(rgbnet_dim)
+        self.rgbnet_direct = bool(rgbnet_direct)
+        self.plane_size = None if plane_size is None else (int(plane_size[0]), int(plane_size[1]))
+        self.rgbnet_kwargs = {
+            'rgbnet_dim': rgbnet_dim, 'rgbnet_direct': rgbnet_direct, 'rgbnet_depth': rgbnet_depth,
+            'rgbnet_width': rgbnet_width, 'viewbase_pe': viewbase_pe,
+        }
+        # lib/tri_dvgo.py:200-223: the feature width, and what of it the MLP reads before the view embedding
+        self.feat_dim = 3 * self.rgbnet_dim if tri_aggregation == 'concat' else self.rgbnet_dim
+        if not self.rgbnet_direct and self.feat_dim < 3:
+            raise ValueError('rgbnet_direct=False takes the first three feature channels as diffuse colour: needs at least 3')
+        self._init_head(self.feat_dim if self.rgbnet_direct else self.feat_dim - 3, viewbase_pe, rgbnet_width, rgbnet_depth)
+        self.planes = nn.ParameterDict({k: nn.Parameter(self._alloc_plane(self._plane_hw(k))) for k in PLANE_KEYS})
+        self._init_mask_cache(ws, mask_cache_path, mask_cache_thres)
+
+    # ------------------------------------------------------------------ construction
+    def _init_head(self, mlp_feat_dim, viewbase_pe, rgbnet_width, rgbnet_depth):
+        self.register_buffer('viewfreq', _freqs(viewbase_pe))
+        self.rgbnet = make_rgbnet(mlp_feat_dim + (3 + 3 * viewbase_pe * 2), rgbnet_width, rgbnet_depth)
+
+    def _plane_hw(self, key):
+        """(H, W) of plane `key`: `plane_size`, else the two world_size extents its rows and columns follow."""
+        if self.plane_size is not None:
+            return self.plane_size
+        ah, aw = PLANE_AXES[key]
+        return int(self.world_size[ah]), int(self.world_size[aw])
+
+    def _alloc_plane(self, hw, device=None):
+        p = torch.zeros([1, self.rgbnet_dim, *hw], device=device)
+        return p.contiguous(memory_format=torch.channels_last) if self.channels_last else p
+
+    def get_kwargs(self):
+        kw = super().get_kwargs()
+        kw.update(tri_aggregation=self.tri_aggregation, plane_size=self.plane_size)
+        return kw
+
+    # ------------------------------------------------------------------ grid maintenance
+    @torch.no_grad()
+    def scale_volume_grid(self, num_voxels):
+        """lib/tri_dvgo.py:372-407 (density and occupancy), plus the model's own planes: resized with the grid, bilinear
+        with align_corners=True, when they take their sizes from world_size; left alone under a fixed `plane_size`."""
+        self._set_grid_resolution(num_voxels)
+        ws = tuple(int(v) for v in self.world_size)
+        self.density = nn.Parameter(F.interpolate(self.density.data, size=ws, mode='trilinear', align_corners=True))
+        if self.plane_size is None:
+            for k in PLANE_KEYS:
+                p = F.interpolate(self.planes[k].data.contiguous(), size=self._plane_hw(k), mode='bilinear', align_corners=True)
+                if self.channels_last:
+                    p = p.contiguous(memory_format=torch.channels_last)
+                self.planes[k] = nn.Parameter(p)
+        mask = self._alpha_mask()
+        if self.mask_cache_path:
+            mask = self._coarse_mask(ws, self.density.device) & mask
+        self._set_mask_cache(mask)
+
+    def k0_total_variation_add_grad(self, weight, dense_mode, x_range=None):
+        raise NotImplementedError('k0_total_variation_add_grad: the tri-plane model has no k0 (the reference method reads an '
+                                  'attribute it never assigns, lib/tri_dvgo.py:446-449)')
+
+    def encode_feat(self, *args, **kwargs):
+        raise NotImplementedError('encode_feat: the image encoder, its Mapping network and the pose anchors are not part of '
+                                  'this model; pass their planes to render(feats, ...)')
+
+    def can_keep_count_on_device(self):
+        return False                 # the sampler sizes its output by the sample count: the forward reads it back
+
+    # ------------------------------------------------------------------ forward
+    def forward(self, rays_o, rays_d, viewdirs, global_step=None, **render_kwargs):
+        """Renders the model's own planes; see `render`."""
+        return self.render(self.planes, rays_o, rays_d, viewdirs, global_step, **render_kwargs)
+
+    def render(self, feats, rays_o, rays_d, viewdirs, global_step=None, **render_kwargs):
+        """lib/tri_dvgo.py:688-809.  `feats`: the three planes {'xy', 'yz', 'zx'}, each [1, rgbnet_dim, H, W] (any sizes;
+        gradients flow into them).  Returns the reference's dict: alphainv_last [N], weights [M], rgb_marched [N,3],
+        raw_alpha [M], raw_rgb [M,3], ray_id [M] (+ depth [N] when render_kwargs['render_depth'])."""
+        assert len(rays_o.shape) == 2 and rays_o.shape[-1] == 3, 'Only suuport point queries in [N, 3] format'
+        N = len(rays_o)
+        bg, render_depth = render_kwargs['bg'], render_kwargs.get('render_depth', False)
+        if self.fused:
+            cfg = self._march_cfg(render_kwargs['near'], render_kwargs['far'], render_kwargs['stepsize'])
+            # the march writes the kept samples' positions where it would write k0 features; the stand-in has no channel
+            no_k0 = self.density.detach()[:, :0]
+            weights, alpha, alphainv_last, pts, ray_id, step_id, off3 = fused_march(
+                self.density, no_k0, rays_o, rays_d, cfg, positions=True)
+            rgb = self._shade(self.sample_planes(pts, feats), viewdirs, ray_id)
+            ret = _result(alphainv_last, weights, composite(weights, rgb, alphainv_last, ray_id, off3, bg), alpha, rgb, ray_id)
+            if render_depth:
+                ret['depth'] = composite_depth(weights.detach(), step_id, off3, N)
+            return ret
+        pts, ray_id, step_id = self.sample_ray(rays_o=rays_o, rays_d=rays_d, is_train=global_step is not None, **render_kwargs)
+        if self.mask_cache is not None:                      # skip known free space
+            mask = self.mask_cache(pts)
+            pts, ray_id, step_id = pts[mask], ray_id[mask], step_id[mask]
+        alpha = self.activate_density(self.grid_sampler(pts, self.density), render_kwargs['stepsize'] * self.voxel_size_ratio)
+        if self.fast_color_thres > 0:
+            mask = alpha > self.fast_color_thres
+            pts, ray_id, step_id, alpha = pts[mask], ray_id[mask], step_id[mask], alpha[mask]
+        weights, alphainv_last = Alphas2Weights.apply(alpha, ray_id, N)
+        if self.fast_color_thres > 0:
+            mask = weights > self.fast_color_thres
+            pts, ray_id, step_id, alpha, weights = pts[mask], ray_id[mask], step_id[mask], alpha[mask], weights[mask]
+        rgb = self._shade(self.sample_planes(pts, feats), viewdirs, ray_id)
+        return self._sum_rays(N, weights, alpha, alphainv_last, rgb, ray_id, bg, render_depth, step_id)
+
+    def _sum_rays(self, N, weights, alpha, alphainv_last, rgb, ray_id, bg, render_depth, step_id):
+        """lib/tri_dvgo.py:786-808 with the fused path's own per-ray sum (fused.composite: one ray's samples in order) in
+        place of segment_coo, whose atomics sum in another order: the two paths then agree bit for bit in rgb_marched."""
+        off3 = torch.searchsorted(ray_id, torch.arange(N + 1, device=ray_id.device))       # ray_id is sorted
+        ret = _result(alphainv_last, weights, composite(weights, rgb, alphainv_last, ray_id, off3, bg), alpha, rgb, ray_id)
+        if render_depth:
+            ret['depth'] = composite_depth(weights.detach(), step_id, off3, N)
+        return ret
+
+    def sample_planes(self, pts, feats=None):
+        """grid_sampler2D (lib/tri_dvgo.py:456-469): [M, 3 * rgbnet_dim] or, tri_aggregation='sum', [M, rgbnet_dim]."""
+        return triplane_sample(self.planes if feats is None else feats, pts, self.xyz_min, self.xyz_max, self.tri_aggregation)

@@ -39,8 +39,8 @@ extern "C" {
 #define DVGO_ERANGE (-2)   /* size exceeds what the kernel's 32-bit indexing supports    */
 
 /* version of this ABI; bumped on any signature change (6: the positional-encoding colour head; 7: the contracted
- * sampler and the distortion loss of unbounded scenes) */
-#define DVGO_ABI_VERSION 7
+ * sampler and the distortion loss of unbounded scenes; 8: the tri-plane sampler) */
+#define DVGO_ABI_VERSION 8
 int dvgo_abi_version(void);
 
 /* Kernel-variant selection for A/B measurements (process-global; defaults are the fastest
@@ -615,6 +615,41 @@ int dvgo_contract_emit(const float* rays_o, const float* rays_d, int64_t n_rays,
 int dvgo_distortion_fwd_bwd(const float* w, const float* s, const int64_t* ray_id, int64_t m, int64_t n_rays,
                             int64_t n_norm, int n_max, float* grad, double* partials, unsigned int* ticket,
                             float* loss, void* stream);
+
+/* ---------------------------------------------------------------------------------
+ * Tri-plane features (csrc/triplane.hip).  Replaces lib/tri_dvgo.py:456-469 grid_sampler2D:
+ * three F.grid_sample(plane[1,C,H,W], ind_norm[..., pair], mode='bilinear', align_corners=True) calls, the
+ * transposes, and torch.cat (sum == 0) or xy + yz + zx (sum != 0), and their autograd backward w.r.t. the planes.
+ * Planes xy, yz, zx: fp32, C channels each, sizes H_s x W_s independent of each other, addressed through ELEMENT
+ * strides (sC, sH, sW): channel-first (sW == 1) and channels-last (sC == 1) both work.  The reference's ind_norm is
+ * the FLIPPED coordinate triple and grid_sample's first grid component addresses W, so whatever the names suggest:
+ *     plane   rows (H) follow world axis   columns (W) follow world axis
+ *     xy      y (1)                        z (2)
+ *     yz      x (0)                        y (1)
+ *     zx      z (2)                        x (0)
+ * Per axis g = ((((p - min) / (max - min)) * 2 - 1) + 1) / 2 * (size - 1), f = floor(g), weights (f + 1) - g and
+ * g - f; a corner's weight is wh * ww; corners in the order (h0,w0), (h0,w1), (h1,w0), (h1,w1), acc = fmaf(v, w, acc)
+ * from 0; corners outside the plane are skipped (zero padding).  A plane axis of size 1 is legal.
+ * dvgo_triplane_fwd: xyz [M,3] world coordinates, xyz_min / xyz_max device float[3] -> out [M, 3C] (xy, yz, zx) or,
+ *   sum != 0, [M, C] = (xy + yz) + zx.
+ * dvgo_triplane_bwd: grad_out as `out`; g_s[c, ih, iw] += w * grad_out[m, c'] (c' = s * C + c, or c when sum != 0)
+ *   into the caller's buffers (zero-filled or holding a partial sum; strides as the planes') with float atomics:
+ *   the summation order is not reproducible.  No gradient for xyz.  run: consecutive samples one lane sums in
+ *   registers while they stay in one texel cell, before its atomics (1: none; 0: the library's default).
+ * M == 0 or C == 0: no-op.  DVGO_EINVAL: negative M or C or run, a plane axis < 1, null pointers.  DVGO_ERANGE:
+ * M * 3C >= 2^31.
+ * --------------------------------------------------------------------------------- */
+int dvgo_triplane_fwd(const float* xy, int H_xy, int W_xy, int64_t sC_xy, int64_t sH_xy, int64_t sW_xy,
+                      const float* yz, int H_yz, int W_yz, int64_t sC_yz, int64_t sH_yz, int64_t sW_yz,
+                      const float* zx, int H_zx, int W_zx, int64_t sC_zx, int64_t sH_zx, int64_t sW_zx,
+                      int C, const float* xyz, const float* xyz_min, const float* xyz_max, int64_t M, int sum,
+                      float* out, void* stream);
+int dvgo_triplane_bwd(const float* grad_out,
+                      float* g_xy, int H_xy, int W_xy, int64_t sC_xy, int64_t sH_xy, int64_t sW_xy,
+                      float* g_yz, int H_yz, int W_yz, int64_t sC_yz, int64_t sH_yz, int64_t sW_yz,
+                      float* g_zx, int H_zx, int W_zx, int64_t sC_zx, int64_t sH_zx, int64_t sW_zx,
+                      int C, const float* xyz, const float* xyz_min, const float* xyz_max, int64_t M, int sum,
+                      int run, void* stream);
 
 #ifdef __cplusplus
 }
