@@ -5,6 +5,8 @@ seeded inputs and against the committed golden fixtures.
 Bars: integer ids, counts and masks exact; positions and everything
 that does not pass through libm bit-exact; activation values rtol 1e-5 / atol 1e-6;
 grid gradients rtol 1e-4 / atol 1e-6 (float atomics, summation order).
+The tighter statement of grid_sample, the view-weight scatter and segment_sum (derived bounds, edge rows, every dispatch
+branch) is tests/test_gpu_grid_oracle.py.
 """
 import numpy as np
 import pytest
@@ -252,6 +254,7 @@ def test_grid_sample_full_size_properties(ops):
 # ------------------------------------------------------------------ A9
 @pytest.mark.parametrize('C', [1, 3])
 def test_segment_coo(ops, oracle, C):
+    """One ragged input at a fixed tolerance; tests/test_gpu_grid_oracle.py::test_segment_sum is the tighter statement."""
     rng = np.random.default_rng(70 + C)
     lens, idx = ragged(rng, 500, 300)
     src = rng.standard_normal((idx.shape[0], C)).astype(np.float32)
