@@ -10,6 +10,8 @@ Two execution paths produce the same dict:
   fused=True   (default) csrc/march.hip: 4 kernels, 1 host sync per forward;
   fused=False  the reference's own op-by-op orchestration on the drop-in ops of
                render_utils.py / ops.py (what a maintainer gets by only swapping the bindings).
+Rays that require grad (camera-pose refinement, pose.py) take a third, op-by-op path that is also differentiable with respect
+to the rays: `_forward_raygrad`.
 `posbase_pe=P > 0` (lib/dvgo.py:97-107,528-534, the switch of configs/nerf and configs/nsvf) colours a sample from
 the positional encoding of its position instead of the feature grid: the colour head's input is
 cat([pts, sin(pts (x) posfreq), cos(pts (x) posfreq), viewdirs_emb]), there is no diffuse term, and k0 -- still allocated,
@@ -27,6 +29,7 @@ from . import _lib as L
 from . import render_utils as render_utils_hip
 from ._lib import _flt, _i64, _int, f3, ptr, stream_of
 from .fused import MarchConfig, fused_hit
+from .ops import ray_points
 from .shade import head_layers
 from .voxel_model import VoxelModel, _freqs, make_rgbnet, mlp_forward  # noqa: F401 (tests and tools import the last two from here)
 
@@ -177,6 +180,39 @@ class DirectVoxGO(VoxelModel):
             rays_o, rays_d, self.xyz_min, self.xyz_max, near, far, stepdist)
         mask_inbbox = ~mask_outbbox
         return ray_pts[mask_inbbox], ray_id[mask_inbbox], step_id[mask_inbbox]
+
+    # ------------------------------------------------------------------ ray gradients (camera-pose refinement, pose.py)
+    def forward(self, rays_o, rays_d, viewdirs, global_step=None, **render_kwargs):
+        """VoxelModel.forward; with grad mode on and `rays_o` or `rays_d` requiring grad (this class only, posbase_pe == 0,
+        whatever `self.fused` says) the render is also differentiable with respect to the rays: see `_forward_raygrad`."""
+        if (torch.is_grad_enabled() and (rays_o.requires_grad or rays_d.requires_grad) and type(self) is DirectVoxGO
+                and self.posbase_pe == 0):
+            return self._forward_raygrad(rays_o, rays_d, viewdirs, **render_kwargs)
+        return super().forward(rays_o, rays_d, viewdirs, global_step=global_step, **render_kwargs)
+
+    def _forward_raygrad(self, rays_o, rays_d, viewdirs, near, far, stepsize, bg, render_depth=False, **_unused):
+        """The op-by-op forward on positions that autograd knows as o + d * lam (ops.ray_points), sampled through the
+        position-differentiable trilinear op (csrc/grid_sample_xyz.hip).  Forward values are those of the `fused=False`
+        path: the positions are the sampling kernel's own, bit for bit.  Stop-gradients, by contract:
+          * lam = t_min[ray_id] + stepdist * step_id / |rays_d[ray_id]| is a constant: neither the box entry t_min nor the
+            norm passes a gradient back to the ray;
+          * the set of kept samples is fixed: the in-box test, the occupancy mask and both fast_color_thres filters select
+            rows and are not differentiated;
+          * viewdirs carries no gradient (the colour heads have no input gradient for the view embedding)."""
+        assert len(rays_o.shape) == 2 and rays_o.shape[-1] == 3, 'Only suuport point queries in [N, 3] format'
+        rays_o, rays_d = rays_o.contiguous(), rays_d.contiguous()
+        stepdist = stepsize * self.voxel_size
+        with torch.no_grad():
+            ray_pts, mask_outbbox, ray_id, step_id, _, t_min, _ = render_utils_hip.sample_pts_on_rays(
+                rays_o, rays_d, self.xyz_min, self.xyz_max, near, far, stepdist)
+            keep = ~mask_outbbox
+            ray_pts, ray_id, step_id = ray_pts[keep], ray_id[keep], step_id[keep]
+            if self.mask_cache is not None:
+                keep = self.mask_cache(ray_pts)
+                ray_pts, ray_id, step_id = ray_pts[keep], ray_id[keep], step_id[keep]
+            lam = t_min[ray_id] + (float(stepdist) * step_id) / rays_d.norm(dim=-1)[ray_id]
+        pts = ray_points(rays_o, rays_d, lam.contiguous(), ray_id, ray_pts.contiguous())
+        return self._forward_unfused(len(rays_o), viewdirs.detach(), stepsize, bg, render_depth, pts, ray_id, step_id)
 
     # ------------------------------------------------------------------ colour head and forward (H2)
     @property

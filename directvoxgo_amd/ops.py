@@ -5,7 +5,8 @@ saved-tensor conventions) on top of the HIP kernels:
 
   Raw2Alpha, Alphas2Weights   lib/dvgo.py:618-660
   MaskCache                   lib/dvgo.py:583-613
-  grid_sample                 lib/dvgo.py:312-328 (grid_sampler -> F.grid_sample + its backward)
+  grid_sample                 lib/dvgo.py:312-328 (grid_sampler -> F.grid_sample + its backward, w.r.t. the grid and the positions)
+  ray_points                  sample positions as a function of their rays (no counterpart: the reference's poses are constants)
   triplane_sample             lib/tri_dvgo.py:456-469 (grid_sampler2D -> three F.grid_sample, cat or sum, + backward)
   segment_coo                 torch_scatter.segment_coo(src, index, out, reduce='sum')
   total_variation_add_grad    lib/cuda/total_variation.cpp:16-24
@@ -81,7 +82,10 @@ class _GridSample(torch.autograd.Function):
         with L.device_of(xyz):
             L.call('dvgo_grid_sample_fwd', ptr(grid), _int(C), _int(X), _int(Y), _int(Z), _i64(sC), _i64(sX),
                    _i64(sY), _i64(sZ), ptr(xyz), ptr(xyz_min), ptr(xyz_max), _i64(M), ptr(out), stream_of(xyz))
-        ctx.save_for_backward(xyz, xyz_min, xyz_max)
+        if ctx.needs_input_grad[1]:       # the position gradient reads the grid's values, not only its geometry
+            ctx.save_for_backward(xyz, xyz_min, xyz_max, grid)
+        else:
+            ctx.save_for_backward(xyz, xyz_min, xyz_max)
         ctx.geom = (C, X, Y, Z, sC, sX, sY, sZ)
         ctx.grid_meta = grid
         return out
@@ -89,9 +93,17 @@ class _GridSample(torch.autograd.Function):
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, grad_out):
-        xyz, xyz_min, xyz_max = ctx.saved_tensors
+        xyz, xyz_min, xyz_max = ctx.saved_tensors[:3]
         C, X, Y, Z, sC, sX, sY, sZ = ctx.geom
-        grad_grid = None
+        grad_grid = grad_xyz = None
+        if ctx.needs_input_grad[1]:
+            grid = ctx.saved_tensors[3]
+            grad_out = grad_out.contiguous()
+            grad_xyz = torch.empty_like(xyz)                 # every row is written by the kernel
+            with L.device_of(xyz):
+                L.call('dvgo_grid_sample_bwd_xyz', ptr(grid), _int(C), _int(X), _int(Y), _int(Z), _i64(sC), _i64(sX),
+                       _i64(sY), _i64(sZ), ptr(grad_out), ptr(xyz), ptr(xyz_min), ptr(xyz_max), _i64(xyz.shape[0]),
+                       ptr(grad_xyz), stream_of(xyz))
         if ctx.needs_input_grad[0]:
             grad_out = grad_out.contiguous()
             # zero-filled, same strides as the parameter (F.grid_sample's backward does the same)
@@ -101,13 +113,14 @@ class _GridSample(torch.autograd.Function):
                 L.call('dvgo_grid_sample_bwd', ptr(grad_out), _int(C), _int(X), _int(Y), _int(Z), _i64(sC),
                        _i64(sX), _i64(sY), _i64(sZ), ptr(xyz), ptr(xyz_min), ptr(xyz_max), _i64(xyz.shape[0]),
                        ptr(grad_grid), stream_of(xyz))
-        return grad_grid, None, None, None
+        return grad_grid, grad_xyz, None, None
 
 
 def grid_sample(grid, xyz, xyz_min, xyz_max):
     """Trilinear interpolation with the exact contract of DirectVoxGO.grid_sampler
     (lib/dvgo.py:312-328): xyz [...,3] world coordinates -> [...,C], squeezed when C == 1.
-    Differentiable w.r.t. ``grid`` (xyz never requires grad on this path)."""
+    Differentiable w.r.t. ``grid`` and, when it requires grad, w.r.t. ``xyz`` (csrc/grid_sample_xyz.hip: the derivative of
+    the cell the forward chose, zero padding outside the grid; once differentiable)."""
     shape = xyz.shape[:-1]
     flat = xyz.reshape(-1, 3).contiguous()
     out = _GridSample.apply(grid, flat, xyz_min.contiguous(), xyz_max.contiguous())
@@ -296,6 +309,48 @@ def segment_coo(src, index, out, reduce='sum'):
     if reduce != 'sum':
         raise NotImplementedError("only reduce='sum' is used by the reference")
     return _SegmentSum.apply(src.contiguous(), index, out)
+
+
+def _segment_sum3(src, ray_id, n):
+    out = torch.zeros((n, 3), dtype=torch.float32, device=src.device)
+    with L.device_of(src):
+        L.call('dvgo_segment_sum', ptr(src), ptr(ray_id), _i64(src.shape[0]), _int(3), _i64(n), ptr(out), stream_of(src))
+    return out
+
+
+class _RayPoints(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, rays_o, rays_d, lam, ray_id, pts):
+        for x, name in ((rays_o, 'rays_o'), (rays_d, 'rays_d'), (pts, 'pts'), (lam, 'lam')):
+            check_input(x, name); check_f32(x, name)
+        check_input(ray_id, 'ray_id')
+        if ray_id.dtype != torch.int64:
+            raise RuntimeError('ray_id must be int64')
+        if pts.dim() != 2 or pts.shape[1] != 3 or lam.shape != ray_id.shape or lam.shape[0] != pts.shape[0]:
+            raise RuntimeError('pts must be [M,3], lam and ray_id [M]')
+        if rays_o.shape != rays_d.shape or rays_o.dim() != 2 or rays_o.shape[1] != 3:
+            raise RuntimeError('rays_o and rays_d must be [N,3]')
+        ctx.save_for_backward(lam, ray_id)
+        ctx.n_rays = rays_o.shape[0]
+        return pts.clone()
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        lam, ray_id = ctx.saved_tensors
+        g = g.contiguous()
+        grad_o = _segment_sum3(g, ray_id, ctx.n_rays) if ctx.needs_input_grad[0] else None
+        grad_d = _segment_sum3((lam.unsqueeze(-1) * g).contiguous(), ray_id, ctx.n_rays) if ctx.needs_input_grad[1] else None
+        return grad_o, grad_d, None, None, None
+
+
+def ray_points(rays_o, rays_d, lam, ray_id, pts):
+    """The sampler's positions as a differentiable function of their rays.  Returns `pts` [M,3] unchanged, bit for bit
+    (they are what the sampling kernel wrote), and states pts[m] = rays_o[ray_id[m]] + rays_d[ray_id[m]] * lam[m] to
+    autograd with `lam` [M] a constant: grad_o = segment_sum(g, ray_id), grad_d = segment_sum(lam[:, None] * g, ray_id),
+    both by dvgo_segment_sum into zero-filled [N,3] (a ray without samples gets exact zeros).  `ray_id` [M] int64 ascending,
+    as every sampler here writes it.  rays_o / rays_d [N,3] float32 CUDA tensors."""
+    return _RayPoints.apply(rays_o, rays_d, lam, ray_id, pts)
 
 
 def total_variation_add_grad(param, grad, wx, wy, wz, dense_mode, x_range=None):

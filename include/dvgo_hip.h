@@ -39,8 +39,9 @@ extern "C" {
 #define DVGO_ERANGE (-2)   /* size exceeds what the kernel's 32-bit indexing supports    */
 
 /* version of this ABI; bumped on any signature change (6: the positional-encoding colour head; 7: the contracted
- * sampler and the distortion loss of unbounded scenes; 8: the tri-plane sampler) */
-#define DVGO_ABI_VERSION 8
+ * sampler and the distortion loss of unbounded scenes; 8: the tri-plane sampler; 9: the trilinear sample's gradient
+ * with respect to the position) */
+#define DVGO_ABI_VERSION 9
 int dvgo_abi_version(void);
 
 /* Kernel-variant selection for A/B measurements (process-global; defaults are the fastest
@@ -650,6 +651,28 @@ int dvgo_triplane_bwd(const float* grad_out,
                       float* g_zx, int H_zx, int W_zx, int64_t sC_zx, int64_t sH_zx, int64_t sW_zx,
                       int C, const float* xyz, const float* xyz_min, const float* xyz_max, int64_t M, int sum,
                       int run, void* stream);
+
+/* ---------------------------------------------------------------------------------
+ * Position gradient of the trilinear sample (csrc/grid_sample_xyz.hip): the other half of
+ * grid_sampler_3d_backward, d out / d xyz, which the reference never asks for (its poses are constants).  What
+ * camera-pose refinement (directvoxgo_amd/pose.py) differentiates through.
+ * grid, strides, xyz, xyz_min / xyz_max as dvgo_grid_sample_fwd; grad_out [M,C] row-major; grad_xyz [M,3].
+ * Per sample: the cell, the per-axis float32 weights and the in-range test of the gather (floorf chooses the cell: on a
+ * lattice plane the derivative is the upper cell's, as in F.grid_sample's backward).  Per channel c, ascending, over the
+ * gather's corner order n = 0..7 (bit2 = +X, bit1 = +Y, bit0 = +Z), corners outside the grid skipped (zero padding),
+ * each chain from 0:
+ *     dX_c = fmaf(v, sx(n) * (wz * wy), dX_c)   dY_c = fmaf(v, sy(n) * (wz * wx), dY_c)   dZ_c = fmaf(v, sz(n) * (wy * wx), dZ_c)
+ * with the sign -1 on the lower corner of that axis and +1 on the upper; then ax = fmaf(grad_out[m,c], dX_c, ax), and
+ * grad_xyz[m,0] = ax * ((float)(X-1) / (xyz_max[0] - xyz_min[0])); likewise y and z.  A sample whose eight corners
+ * are all outside gets 0.0f, an axis of size 1 gives 0 on that axis.  Every row is written with plain stores by one
+ * lane: no atomics, no workspace, and grad_xyz need not be zeroed.  Channels-last with C % 4 == 0 and 16-byte aligned
+ * grid and grad_out reads 16-byte vectors; everything else goes through the element strides.
+ * M == 0: no-op.  DVGO_EINVAL: negative M or C, an axis < 1, null pointers with M > 0.  DVGO_ERANGE: M * C >= 2^31.
+ * --------------------------------------------------------------------------------- */
+int dvgo_grid_sample_bwd_xyz(const float* grid, int C, int X, int Y, int Z,
+                             int64_t sC, int64_t sX, int64_t sY, int64_t sZ,
+                             const float* grad_out, const float* xyz, const float* xyz_min, const float* xyz_max,
+                             int64_t M, float* grad_xyz, void* stream);
 
 #ifdef __cplusplus
 }
