@@ -8,6 +8,8 @@ saved-tensor conventions) on top of the HIP kernels:
   grid_sample                 lib/dvgo.py:312-328 (grid_sampler -> F.grid_sample + its backward, w.r.t. the grid and the positions)
   ray_points                  sample positions as a function of their rays (no counterpart: the reference's poses are constants)
   triplane_sample             lib/tri_dvgo.py:456-469 (grid_sampler2D -> three F.grid_sample, cat or sum, + backward)
+  liif_gather, liif_blend,    lib/tri_dvgo.py:481-565 (liif_interpolate: nearest-texel rows, blend weights, blend, + backward;
+  liif_decode                 the Interp_MLPs between them stay torch modules)
   segment_coo                 torch_scatter.segment_coo(src, index, out, reduce='sum')
   total_variation_add_grad    lib/cuda/total_variation.cpp:16-24
 """
@@ -243,6 +245,158 @@ def triplane_sample(planes, xyz, xyz_min, xyz_max, aggregation='concat'):
     flat = xyz.reshape(-1, 3).contiguous()
     out = _TriPlaneSample.apply(xy, yz, zx, flat, xyz_min.contiguous(), xyz_max.contiguous(), aggregation)
     return out.reshape(*shape, out.shape[-1])
+
+
+# ---------------------------------------------------------------------------------------------- LIIF plane decoder
+def _liif_args(planes, xyz, world_size):
+    """-> (planes, the 15 plane-geometry scalars in call order split per plane, C, M, (Wx, Wy, Wz))"""
+    planes = _plane_list(planes)
+    geoms = [_plane_geom(p, k) for p, k in zip(planes, PLANE_KEYS)]
+    C = planes[0].shape[1]
+    if any(p.shape[1] != C for p in planes):
+        raise RuntimeError('the three planes must share their channel count')
+    check_input(xyz, 'xyz'); check_f32(xyz, 'xyz')
+    if xyz.dim() != 2 or xyz.shape[1] != 3:
+        raise RuntimeError('xyz must be [M,3]')
+    ws = tuple(int(v) for v in world_size)
+    if len(ws) != 3 or min(ws) < 1:
+        raise ValueError(f'world_size must be three extents >= 1, got {ws}')
+    return planes, geoms, C, xyz.shape[0], ws
+
+
+def liif_gather_fwd(planes, xyz, xyz_min, xyz_max, world_size, cell_decode=True, local_ensemble=True):
+    """dvgo_liif_gather on the planes' strides as they are: xyz [M,3] -> inp [3,E,M,D], wgt [3,E,M] (E = 4 with
+    local_ensemble, else 1; D = C + 4 with cell_decode, else C + 2).  No autograd."""
+    planes, geoms, C, M, (Wx, Wy, Wz) = _liif_args(planes, xyz, world_size)
+    E, D = (4 if local_ensemble else 1), C + (4 if cell_decode else 2)
+    inp = torch.empty((3, E, M, D), dtype=torch.float32, device=xyz.device)
+    wgt = torch.empty((3, E, M), dtype=torch.float32, device=xyz.device)
+    (Ha, Wa, ca, ha, wa), (Hb, Wb, cb, hb, wb), (Hc, Wc, cc, hc, wc) = geoms
+    with L.device_of(xyz):
+        L.call('dvgo_liif_gather', planes[0], Ha, Wa, ca, ha, wa, planes[1], Hb, Wb, cb, hb, wb, planes[2], Hc, Wc, cc, hc, wc,
+               C, xyz, xyz_min, xyz_max, M, Wx, Wy, Wz, int(bool(cell_decode)), int(bool(local_ensemble)), inp, wgt,
+               stream_of(xyz))
+    return inp, wgt
+
+
+def liif_gather_bwd(grad_inp, grads, xyz, xyz_min, xyz_max, world_size, cell_decode=True, local_ensemble=True, run=0):
+    """dvgo_liif_scatter: accumulates the first C columns of grad_inp [3,E,M,D] into the three buffers `grads` (shaped
+    and strided like planes) in place.  `run`: samples a lane merges before its atomic (0: the library's default)."""
+    grads, geoms, C, M, (Wx, Wy, Wz) = _liif_args(grads, xyz, world_size)
+    E, D = (4 if local_ensemble else 1), C + (4 if cell_decode else 2)
+    check_input(grad_inp, 'grad_inp'); check_f32(grad_inp, 'grad_inp')
+    if tuple(grad_inp.shape) != (3, E, M, D):
+        raise RuntimeError('grad_inp has the wrong shape')
+    (Ha, Wa, ca, ha, wa), (Hb, Wb, cb, hb, wb), (Hc, Wc, cc, hc, wc) = geoms
+    with L.device_of(xyz):
+        L.call('dvgo_liif_scatter', grad_inp, grads[0], Ha, Wa, ca, ha, wa, grads[1], Hb, Wb, cb, hb, wb, grads[2], Hc, Wc, cc,
+               hc, wc, C, xyz, xyz_min, xyz_max, M, Wx, Wy, Wz, int(bool(cell_decode)), int(bool(local_ensemble)), int(run),
+               stream_of(xyz))
+    return grads
+
+
+def _blend_shape(pred, wgt):
+    check_input(pred, 'pred'); check_f32(pred, 'pred'); check_input(wgt, 'wgt'); check_f32(wgt, 'wgt')
+    if pred.dim() != 4 or pred.shape[0] != 3 or pred.shape[1] not in (1, 4) or tuple(wgt.shape) != tuple(pred.shape[:3]):
+        raise RuntimeError('pred must be [3,E,M,C] with E = 1 or 4 and wgt [3,E,M]')
+    return pred.shape[1:]
+
+
+def liif_blend_fwd(pred, wgt, aggregation='concat'):
+    """dvgo_liif_blend_fwd: pred [3,E,M,C], wgt [3,E,M] -> [M,3C] (concat) or [M,C] (sum).  No autograd."""
+    if aggregation not in ('concat', 'sum'):
+        raise ValueError(f"aggregation must be 'concat' or 'sum', got {aggregation!r}")
+    E, M, C = _blend_shape(pred, wgt)
+    out = torch.empty((M, C if aggregation == 'sum' else 3 * C), dtype=torch.float32, device=pred.device)
+    with L.device_of(pred):
+        L.call('dvgo_liif_blend_fwd', pred, wgt, C, M, E, 1 if aggregation == 'sum' else 0, out, stream_of(pred))
+    return out
+
+
+def liif_blend_bwd(grad_out, wgt, C, aggregation='concat'):
+    """dvgo_liif_blend_bwd: grad_out [M,3C] or [M,C], wgt [3,E,M] -> grad_pred [3,E,M,C]."""
+    check_input(grad_out, 'grad_out'); check_f32(grad_out, 'grad_out'); check_input(wgt, 'wgt'); check_f32(wgt, 'wgt')
+    _, E, M = wgt.shape
+    if tuple(grad_out.shape) != (M, C if aggregation == 'sum' else 3 * C):
+        raise RuntimeError('grad_out has the wrong shape')
+    grad_pred = torch.empty((3, E, M, C), dtype=torch.float32, device=wgt.device)
+    with L.device_of(wgt):
+        L.call('dvgo_liif_blend_bwd', grad_out, wgt, C, M, E, 1 if aggregation == 'sum' else 0, grad_pred, stream_of(wgt))
+    return grad_pred
+
+
+class _LiifGather(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, xy, yz, zx, xyz, xyz_min, xyz_max, world_size, cell_decode, local_ensemble):
+        planes = [xy, yz, zx]
+        M = xyz.shape[0]
+        relayout = TRIPLANE_RELAYOUT and M >= max(p.shape[2] * p.shape[3] for p in planes)
+        ctx.relayout = [relayout and not _is_channels_last(p) for p in planes]
+        kp = [p.contiguous(memory_format=torch.channels_last) if r else p for p, r in zip(planes, ctx.relayout)]
+        inp, wgt = liif_gather_fwd(kp, xyz, xyz_min, xyz_max, world_size, cell_decode, local_ensemble)
+        ctx.save_for_backward(xyz, xyz_min, xyz_max)
+        ctx.meta = planes
+        ctx.geometry = (world_size, cell_decode, local_ensemble)
+        ctx.mark_non_differentiable(wgt)
+        return inp, wgt
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_inp, _grad_wgt):
+        xyz, xyz_min, xyz_max = ctx.saved_tensors
+        grads = [None, None, None]
+        if any(ctx.needs_input_grad[:3]):
+            # as _TriPlaneSample.backward: zero-filled buffers with the strides the kernel saw, one launch into all three
+            grads = [torch.zeros_like(p, memory_format=torch.channels_last if r else torch.preserve_format)
+                     for p, r in zip(ctx.meta, ctx.relayout)]
+            liif_gather_bwd(grad_inp.contiguous(), grads, xyz, xyz_min, xyz_max, *ctx.geometry)
+            grads = [g if need else None for g, need in zip(grads, ctx.needs_input_grad[:3])]
+        return grads[0], grads[1], grads[2], None, None, None, None, None, None
+
+
+class _LiifBlend(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pred, wgt, aggregation):
+        ctx.save_for_backward(wgt)
+        ctx.aggregation, ctx.C = aggregation, pred.shape[3]
+        return liif_blend_fwd(pred, wgt, aggregation)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        wgt, = ctx.saved_tensors
+        return liif_blend_bwd(grad_out.contiguous(), wgt, ctx.C, ctx.aggregation), None, None
+
+
+def liif_gather(planes, xyz, xyz_min, xyz_max, world_size, cell_decode=True, local_ensemble=True):
+    """The gathers of the reference's liif_interpolate (lib/tri_dvgo.py:481-565) as one HIP op: planes as in
+    `triplane_sample`, xyz [M,3] -> (inp [3,E,M,D], wgt [3,E,M]): per plane (xy, yz, zx) and shifted position the MLP input
+    rows [nearest texel's C features, rel0, rel1(, cell0, cell1)] and the blend weights (include/dvgo_hip.h has the
+    arithmetic).  Differentiable w.r.t. the planes only, through the feature columns; wgt carries no gradient."""
+    xy, yz, zx = _plane_list(planes)
+    for p, k in zip((xy, yz, zx), PLANE_KEYS):
+        _plane_geom(p, k)
+    ws = tuple(int(v) for v in world_size)
+    return _LiifGather.apply(xy, yz, zx, xyz.reshape(-1, 3).contiguous(), xyz_min.contiguous(), xyz_max.contiguous(), ws,
+                             bool(cell_decode), bool(local_ensemble))
+
+
+def liif_blend(pred, wgt, aggregation='concat'):
+    """pred [3,E,M,C] blended over the shifts by wgt [3,E,M] and aggregated over the planes: [M,3C] ('concat') or [M,C]
+    ('sum': (xy + yz) + zx).  Differentiable w.r.t. pred only."""
+    if aggregation not in ('concat', 'sum'):
+        raise ValueError(f"aggregation must be 'concat' or 'sum', got {aggregation!r}")
+    return _LiifBlend.apply(pred.contiguous(), wgt, aggregation)
+
+
+def liif_decode(planes, nets, xyz, xyz_min, xyz_max, world_size, cell_decode=True, local_ensemble=True, aggregation='concat'):
+    """liif_interpolate: gather, the decoders, blend.  `nets`: {'xy': module, 'yz': module}; plane zx is decoded by
+    nets['yz'] as in the reference (lib/tri_dvgo.py:170-174), so the MLPs run twice -- once on the E*M rows of plane xy,
+    once on the 2*E*M rows of planes yz and zx -- instead of 3 E times."""
+    inp, wgt = liif_gather(planes, xyz, xyz_min, xyz_max, world_size, cell_decode, local_ensemble)
+    _, E, M, D = inp.shape
+    pred = torch.cat([nets['xy'](inp[0].reshape(E * M, D)), nets['yz'](inp[1:].reshape(2 * E * M, D))])
+    return liif_blend(pred.reshape(3, E, M, -1), wgt, aggregation)
 
 
 class MaskCache(nn.Module):

@@ -35,10 +35,10 @@ PLANE_AXES = {'xy': (1, 2), 'yz': (0, 1), 'zx': (2, 0)}
 TRI_FINE_TRAIN = dict(FINE_TRAIN, lrate_planes=1e-1, skip_zero_grad_fields=['density'])
 
 _OUT_OF_SCOPE = {
-    'implicit_voxel_feat': 'the LIIF-style implicit plane decoder (Interp_MLP per plane) is not built: only the bilinear path is',
-    'liif': 'LIIF local-ensemble decoding belongs to implicit_voxel_feat, which is not built',
-    'feat_unfold': 'the 3x3 feature unfolding belongs to implicit_voxel_feat, which is not built',
-    'cell_decode': 'cell decoding belongs to implicit_voxel_feat, which is not built',
+    'implicit_voxel_feat': 'this class is the bilinear path; the LIIF plane decoder (Interp_MLP per plane) is liif.LIIFTriPlaneVoxGO',
+    'liif': 'LIIF local-ensemble decoding belongs to implicit_voxel_feat: liif.LIIFTriPlaneVoxGO',
+    'feat_unfold': 'the 3x3 feature unfolding belongs to implicit_voxel_feat and is not built',
+    'cell_decode': 'cell decoding belongs to implicit_voxel_feat: liif.LIIFTriPlaneVoxGO',
     'global_cell_decode': 'appending the cell size to the features is not built',
     'feat_fourier': 'the Fourier embedding of the features is not built',
     'feat_pe': 'the positional encoding of the features (feat_fourier) is not built',
@@ -175,7 +175,7 @@ class TriPlaneVoxGO(DirectVoxGO):
             no_k0 = self.density.detach()[:, :0]
             weights, alpha, alphainv_last, pts, ray_id, step_id, off3 = fused_march(
                 self.density, no_k0, rays_o, rays_d, cfg, positions=True)
-            rgb = self._shade(self.sample_planes(pts, feats), viewdirs, ray_id)
+            rgb = self._shade(self._head_features(pts, feats), viewdirs, ray_id)
             ret = _result(alphainv_last, weights, composite(weights, rgb, alphainv_last, ray_id, off3, bg), alpha, rgb, ray_id)
             if render_depth:
                 ret['depth'] = composite_depth(weights.detach(), step_id, off3, N)
@@ -192,7 +192,7 @@ class TriPlaneVoxGO(DirectVoxGO):
         if self.fast_color_thres > 0:
             mask = weights > self.fast_color_thres
             pts, ray_id, step_id, alpha, weights = pts[mask], ray_id[mask], step_id[mask], alpha[mask], weights[mask]
-        rgb = self._shade(self.sample_planes(pts, feats), viewdirs, ray_id)
+        rgb = self._shade(self._head_features(pts, feats), viewdirs, ray_id)
         return self._sum_rays(N, weights, alpha, alphainv_last, rgb, ray_id, bg, render_depth, step_id)
 
     def _sum_rays(self, N, weights, alpha, alphainv_last, rgb, ray_id, bg, render_depth, step_id):
@@ -203,6 +203,10 @@ class TriPlaneVoxGO(DirectVoxGO):
         if render_depth:
             ret['depth'] = composite_depth(weights.detach(), step_id, off3, N)
         return ret
+
+    def _head_features(self, pts, feats):
+        """What the colour head reads of a sample before the view embedding: the plane features (a subclass may append)."""
+        return self.sample_planes(pts, feats)
 
     def sample_planes(self, pts, feats=None):
         """grid_sampler2D (lib/tri_dvgo.py:456-469): [M, 3 * rgbnet_dim] or, tri_aggregation='sum', [M, rgbnet_dim]."""

@@ -41,7 +41,7 @@ extern "C" {
 /* version of this ABI; bumped on any signature change (6: the positional-encoding colour head; 7: the contracted
  * sampler and the distortion loss of unbounded scenes; 8: the tri-plane sampler; 9: the trilinear sample's gradient
  * with respect to the position) */
-#define DVGO_ABI_VERSION 9
+#define DVGO_ABI_VERSION 10
 int dvgo_abi_version(void);
 
 /* Kernel-variant selection for A/B measurements (process-global; defaults are the fastest
@@ -673,6 +673,56 @@ int dvgo_grid_sample_bwd_xyz(const float* grid, int C, int X, int Y, int Z,
                              int64_t sC, int64_t sX, int64_t sY, int64_t sZ,
                              const float* grad_out, const float* xyz, const float* xyz_min, const float* xyz_max,
                              int64_t M, float* grad_xyz, void* stream);
+
+/* ---------------------------------------------------------------------------------
+ * LIIF plane decoder around its MLPs (csrc/liif.hip).  Replaces lib/tri_dvgo.py:481-565
+ * liif_interpolate except the Interp_MLP calls: per sample, plane and shifted position the nearest texel's features, the
+ * relative coordinates and the cell sizes as one MLP input row, the blend weights, the blend, and both gradients.
+ * Planes as in dvgo_triplane_*: pointer, H, W and three ELEMENT strides each, any dense layout.  (Wx, Wy, Wz) = world_size.
+ * All of the following in float32, in this order, no contraction:
+ *   n_a = ((p_a - min_a) / (max_a - min_a)) * 2 - 1                      for world axis a
+ *     plane   u (addresses rows, H_s)   v (addresses columns, W_s)   (Ta, Tb)
+ *     xy      n_z                       n_y                          (Wx, Wy)
+ *     yz      n_y                       n_x                          (Wy, Wz)
+ *     zx      n_x                       n_z                          (Wz, Wx)
+ *   shifts e = 0..3: (vx, vy) = (-1,-1), (-1,+1), (+1,-1), (+1,+1); E = 4.  local_ensemble == 0: one shift, E = 1,
+ *     with u' = clamp(u), v' = clamp(v).
+ *   u' = clamp(u + (vx * (1 / Ta) + 1e-6f), (float)(-1 + 1e-6), (float)(1 - 1e-6));   v' likewise with vy, 1 / Tb
+ *   near_S(c) = clip(rint(((c + 1) * S - 1) / 2), 0, S - 1), rint to even (grid_sample 'nearest', align_corners=False)
+ *   texel: row near_H(u'), column near_W(v')
+ *   q0 = node_Tb(near_Tb(v')), q1 = node_Ta(near_Ta(u')), node_T(i) = i * (2 / (T - 1)) - 1, node_1 = -1
+ *   rel0 = (u - q0) * H_s, rel1 = (v - q1) * W_s        (u against the v table: the reference's pairing)
+ *   row of inp: plane[:, row, col] (C values), rel0, rel1, then, cell_decode != 0, (1 / Ta) * H_s, (1 / Tb) * W_s:
+ *     D = C + 2 or C + 4
+ *   area_e = |rel0 * rel1| + 1e-9f; tot = ((a0 + a1) + a2) + a3; wgt_e = area_{E-1-e} / tot
+ * dvgo_liif_gather: xyz [M,3], xyz_min / xyz_max device float[3] -> inp [3, E, M, D], wgt [3, E, M], dense.  Channels-last
+ *   planes with 16-byte (C % 4 == 0 and D % 4 == 0) or 8-byte (C % 2 == 0) aligned texels are read and written in
+ *   pieces of that size; everything else goes element by element through the strides.
+ * dvgo_liif_scatter: g_s[c, row, col] += grad_inp[s, e, m, c] (the first C columns of each row) into the caller's buffers
+ *   (zero-filled or holding a partial sum; strides as the planes') with float atomics: the summation order is not
+ *   reproducible.  Texels are recomputed from xyz.  run: consecutive samples a lane sums in a register while they share
+ *   a texel (1: none; 0: the library's default, 4: started as a guess, measured since at one batch size only,
+ *   profiles/liif/README.md).
+ * dvgo_liif_blend_fwd: pred [3, E, M, C], wgt -> out [M, 3C] (sum == 0: xy, yz, zx) or [M, C] (sum != 0: (xy + yz) + zx);
+ *   per plane acc = fmaf(pred, wgt, acc) from 0 in shift order.
+ * dvgo_liif_blend_bwd: grad_pred[s, e, m, c] = grad_out[m, c'] * wgt[s, e, m] (c' = s * C + c, or c when sum != 0).
+ * M == 0 or C == 0: no-op.  DVGO_EINVAL: negative M, C or run, a plane axis or world extent < 1, E not 1 or 4, null
+ * pointers.  DVGO_ERANGE: M * 3 E D (gather, scatter) or M * 3 E C (blend) >= 2^31.
+ * --------------------------------------------------------------------------------- */
+int dvgo_liif_gather(const float* xy, int H_xy, int W_xy, int64_t sC_xy, int64_t sH_xy, int64_t sW_xy,
+                     const float* yz, int H_yz, int W_yz, int64_t sC_yz, int64_t sH_yz, int64_t sW_yz,
+                     const float* zx, int H_zx, int W_zx, int64_t sC_zx, int64_t sH_zx, int64_t sW_zx,
+                     int C, const float* xyz, const float* xyz_min, const float* xyz_max, int64_t M,
+                     int Wx, int Wy, int Wz, int cell_decode, int local_ensemble, float* inp, float* wgt, void* stream);
+int dvgo_liif_scatter(const float* grad_inp,
+                      float* g_xy, int H_xy, int W_xy, int64_t sC_xy, int64_t sH_xy, int64_t sW_xy,
+                      float* g_yz, int H_yz, int W_yz, int64_t sC_yz, int64_t sH_yz, int64_t sW_yz,
+                      float* g_zx, int H_zx, int W_zx, int64_t sC_zx, int64_t sH_zx, int64_t sW_zx,
+                      int C, const float* xyz, const float* xyz_min, const float* xyz_max, int64_t M,
+                      int Wx, int Wy, int Wz, int cell_decode, int local_ensemble, int run, void* stream);
+int dvgo_liif_blend_fwd(const float* pred, const float* wgt, int C, int64_t M, int E, int sum, float* out, void* stream);
+int dvgo_liif_blend_bwd(const float* grad_out, const float* wgt, int C, int64_t M, int E, int sum, float* grad_pred,
+                        void* stream);
 
 #ifdef __cplusplus
 }
