@@ -13,7 +13,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # DVGO_HIP_SO: another build of the same library (kernel A/B runs, tools/)
 SO_PATH = os.environ.get('DVGO_HIP_SO') or os.path.join(_HERE, 'csrc', 'libdvgo_hip.so')
-ABI_VERSION = 10
+ABI_VERSION = 11
 # the declarations the boundary is typed from (checkout layout: include/ beside the package)
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), 'include', 'dvgo_hip.h')
 

@@ -14,48 +14,7 @@
 // (common.h: dvgo_tri_value_c1 explains what the conditional form costs); a select drops the out-of-range ones, which
 // leaves the accumulation order above untouched.  Every row of grad_xyz is written by its lane with plain stores: no
 // atomics, no workspace, nothing to zero beforehand.
-#include "common.h"
-
-struct XyzCorners {
-  float wx[8], wy[8], wz[8];   // signed two-weight products of corner n for d/dx, d/dy, d/dz
-  int64_t off[8];              // element offset of the clamped corner (channel 0)
-  bool ok[8];                  // corner inside the lattice
-};
-
-__device__ __forceinline__ XyzCorners dvgo_xyz_corners(const TriSetup& t, int X, int Y, int Z, int64_t sX, int64_t sY, int64_t sZ) {
-  XyzCorners k;
-#pragma unroll
-  for (int n = 0; n < 8; ++n) {
-    const float wz = (n & 1) ? t.wz1 : t.wz0;
-    const float wy = (n & 2) ? t.wy1 : t.wy0;
-    const float wx = (n & 4) ? t.wx1 : t.wx0;
-    const float zy = wz * wy, zx = wz * wx, yx = wy * wx;
-    k.wx[n] = (n & 4) ? zy : -zy;
-    k.wy[n] = (n & 2) ? zx : -zx;
-    k.wz[n] = (n & 1) ? yx : -yx;
-    k.ok[n] = dvgo_tri_inb(t, n, X, Y, Z);
-    const int i = min(max(t.i0 + ((n >> 2) & 1), 0), X - 1);
-    const int j = min(max(t.j0 + ((n >> 1) & 1), 0), Y - 1);
-    const int kk = min(max(t.k0 + (n & 1), 0), Z - 1);
-    k.off[n] = (int64_t)i * sX + (int64_t)j * sY + (int64_t)kk * sZ;
-  }
-  return k;
-}
-
-// one channel: the three corner chains from 0, then the channel's term of the three sums
-#define DVGO_XYZ_CHANNEL(V, G)                                           \
-  do {                                                                   \
-    float dx = 0.f, dy = 0.f, dz = 0.f;                                  \
-    _Pragma("unroll") for (int n = 0; n < 8; ++n) {                      \
-      const float v_ = (V);                                              \
-      dx = k.ok[n] ? fmaf(v_, k.wx[n], dx) : dx;                         \
-      dy = k.ok[n] ? fmaf(v_, k.wy[n], dy) : dy;                         \
-      dz = k.ok[n] ? fmaf(v_, k.wz[n], dz) : dz;                         \
-    }                                                                    \
-    ax = fmaf((G), dx, ax);                                              \
-    ay = fmaf((G), dy, ay);                                              \
-    az = fmaf((G), dz, az);                                              \
-  } while (0)
+#include "xyz_corners.h"   // XyzCorners, dvgo_xyz_corners, DVGO_XYZ_CHANNEL: shared with march.hip's ray-gradient kernel
 
 template <int VEC>   // VEC = 4: channels-last with C % 4 == 0 and 16-B aligned bases; 1: generic (element strides)
 __global__ void __launch_bounds__(DVGO_BLOCK)
@@ -97,7 +56,6 @@ grid_sample_bwd_xyz_kernel(const float* __restrict__ grid, int C, int X, int Y, 
   grad_xyz[3 * m + 1] = ay * ((float)(Y - 1) / (mxy - mny));
   grad_xyz[3 * m + 2] = az * ((float)(Z - 1) / (mxz - mnz));
 }
-#undef DVGO_XYZ_CHANNEL
 
 extern "C" {
 

@@ -11,7 +11,8 @@ Two execution paths produce the same dict:
   fused=False  the reference's own op-by-op orchestration on the drop-in ops of
                render_utils.py / ops.py (what a maintainer gets by only swapping the bindings).
 Rays that require grad (camera-pose refinement, pose.py) take a third, op-by-op path that is also differentiable with respect
-to the rays: `_forward_raygrad`.
+to the rays: `_forward_raygrad`; with the class switch `fused_raygrad` set (pose.refine_poses(fused=True) sets it for its
+loop) they stay on the fused march, whose backward then also returns the ray gradients (csrc/march.hip: march_ray_bwd).
 `posbase_pe=P > 0` (lib/dvgo.py:97-107,528-534, the switch of configs/nerf and configs/nsvf) colours a sample from
 the positional encoding of its position instead of the feature grid: the colour head's input is
 cat([pts, sin(pts (x) posfreq), cos(pts (x) posfreq), viewdirs_emb]), there is no diffuse term, and k0 -- still allocated,
@@ -35,6 +36,11 @@ from .voxel_model import VoxelModel, _freqs, make_rgbnet, mlp_forward  # noqa: F
 
 
 class DirectVoxGO(VoxelModel):
+    # rays that require grad stay on the fused march (fused.py launches dvgo_march_ray_bwd in the backward) instead of taking
+    # `_forward_raygrad`.  A switch of the running process, not of the model: no constructor argument, not in get_kwargs(),
+    # not in checkpoints.
+    fused_raygrad = False
+
     def __init__(self, xyz_min, xyz_max, num_voxels=0, num_voxels_base=0, alpha_init=None,
                  mask_cache_path=None, mask_cache_thres=1e-3, fast_color_thres=0,
                  rgbnet_dim=0, rgbnet_direct=False, rgbnet_full_implicit=False,
@@ -184,9 +190,13 @@ class DirectVoxGO(VoxelModel):
     # ------------------------------------------------------------------ ray gradients (camera-pose refinement, pose.py)
     def forward(self, rays_o, rays_d, viewdirs, global_step=None, **render_kwargs):
         """VoxelModel.forward; with grad mode on and `rays_o` or `rays_d` requiring grad (this class only, posbase_pe == 0,
-        whatever `self.fused` says) the render is also differentiable with respect to the rays: see `_forward_raygrad`."""
+        whatever `self.fused` says) the render is also differentiable with respect to the rays: see `_forward_raygrad`.
+        With `fused_raygrad` set on a fused model such rays take the fused forward instead, rays attached and `viewdirs`
+        detached: the same stop-gradients, the derivative from the march's own backward."""
         if (torch.is_grad_enabled() and (rays_o.requires_grad or rays_d.requires_grad) and type(self) is DirectVoxGO
                 and self.posbase_pe == 0):
+            if self.fused_raygrad and self.fused and not self.uses_posenc:
+                return super().forward(rays_o, rays_d, viewdirs.detach(), global_step=global_step, **render_kwargs)
             return self._forward_raygrad(rays_o, rays_d, viewdirs, **render_kwargs)
         return super().forward(rays_o, rays_d, viewdirs, global_step=global_step, **render_kwargs)
 

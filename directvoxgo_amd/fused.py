@@ -232,6 +232,9 @@ class _FusedMarch(torch.autograd.Function):
         assert (kX, kY, kZ) == (X, Y, Z), 'density and k0 must share world_size'
         st = stream_of(rays_o)
         ndc = cfg.ndc_samples > 0
+        # rays that require grad (camera-pose refinement): the backward also launches dvgo_march_ray_bwd (fused_march has
+        # refused what that kernel does not differentiate)
+        ray_grad = bool(ctx.needs_input_grad[2] or ctx.needs_input_grad[3]) and not (positions or ndc)
         stride = cfg.ndc_samples if ndc else _rec_stride(cfg, N)
 
         setup_in_march = (not ndc) and stride > 0        # K1-K3 inside march_density: one launch less
@@ -305,8 +308,9 @@ class _FusedMarch(torch.autograd.Function):
         ctx.union = (bu, union_active, bu.n_union) if (bu is not None and bu.sparse) else None
         ctx.padded = padded
         ctx.density_meta, ctx.k0_meta = density, k0
+        ctx.ray_grad = ray_grad
         ctx.save_for_backward(rec2, n2, n_steps, cum if cum is not None else n_steps, off3, start, dirs, last,
-                              ray_id, step_id)
+                              ray_id, step_id, *((rays_o, rays_d) if ray_grad else ()))
         off3 = off3[:N + 1]
         ctx.mark_non_differentiable(alpha, ray_id, step_id, off3, *((feat,) if positions else ()))
         ctx.set_materialize_grads(False)     # no zero-filled [M3] int64 'gradients' for the id outputs (33 MB per step)
@@ -315,7 +319,7 @@ class _FusedMarch(torch.autograd.Function):
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, g_w, _g_alpha, g_last, g_feat, _g_rid, _g_sid, _g_off):
-        rec2, n2, n_steps, cum, off3, start, dirs, last, ray_id, step_id = ctx.saved_tensors
+        rec2, n2, n_steps, cum, off3, start, dirs, last, ray_id, step_id = ctx.saved_tensors[:10]
         X, Y, Z, C, sC, sX, sY, sZ, stride, N = ctx.geom
         cfg = ctx.cfg
         M3 = ray_id.shape[0]
@@ -326,9 +330,22 @@ class _FusedMarch(torch.autograd.Function):
             want_k0 = ctx.needs_input_grad[1] and g_feat is not None and C > 0
             want_d = ctx.needs_input_grad[0]
             gw = gl = None
-            if want_d:
+            if want_d or ctx.ray_grad:
                 gw = g_w.contiguous() if g_w is not None else torch.zeros(M3, dtype=torch.float32, device=dev)
                 gl = g_last.contiguous() if g_last is not None else None
+            rays = (None, None)
+            if ctx.ray_grad:
+                # FIRST, before any other launch of this backward: the brick scatter below may apply the optimizer's
+                # update to both grids in place (grid_rows_capture.adam), and this kernel must read the grids the
+                # forward read.  Same stream, so launch order is execution order.
+                rays_o, rays_d = ctx.saved_tensors[10:]
+                go = torch.empty((N, 3), dtype=torch.float32, device=dev)
+                gd = torch.empty((N, 3), dtype=torch.float32, device=dev)
+                L.call('dvgo_march_ray_bwd', rec2, n2, n_steps, cum if stride == 0 else None, stride, off3, N, start, dirs,
+                       cfg.stepdist, cfg.xyz_min_h, cfg.xyz_max_h, last, cfg.interval, rays_o, rays_d, cfg.near, cfg.far,
+                       ctx.density_meta, X, Y, Z, ctx.k0_meta, C, sC, sX, sY, sZ, gw, gl,
+                       g_feat.contiguous() if (g_feat is not None and C > 0) else None, go, gd, st)
+                rays = (go if ctx.needs_input_grad[2] else None, gd if ctx.needs_input_grad[3] else None)
 
             def density_bwd(dst, dst_stride, kept, cursor=None, recs=None):
                 L.call('dvgo_march_density_bwd', rec2, n2, n_steps, cum if stride == 0 else None, stride, off3, N, start, dirs,
@@ -340,7 +357,7 @@ class _FusedMarch(torch.autograd.Function):
                 raise RuntimeError('capacity-mode forward (device-side sample count) needs the brick scatter backward for both grids')
             if plan is not None:
                 ctx.plan = None                                 # the fill cursors are consumed: one backward per forward
-                return _brick_backward(ctx, plan, density_bwd, g_feat, start, dirs, st) + (None,) * 5
+                return _brick_backward(ctx, plan, density_bwd, g_feat, start, dirs, st) + rays + (None,) * 3
 
             # worth its two extra full-grid passes (zero 64 B, split 116 B per voxel) from ~1 kept sample per 6 voxels
             combined = (COMBINED_GRID_GRAD and want_k0 and want_d and C == 12 and M3 * COMBINED_MIN_RATIO >= X * Y * Z and tuple(ctx.density_meta.shape[2:]) == (X, Y, Z)
@@ -356,7 +373,7 @@ class _FusedMarch(torch.autograd.Function):
                 cap = grid_rows_capture._active
                 if cap is not None and cap.G is None and cap.density is ctx.density_meta and cap.k0 is ctx.k0_meta:
                     cap.G = G                  # the optimizer consumes the rows; no dense gradients are produced
-                    return None, None, None, None, None, None, None
+                    return (None, None) + rays + (None,) * 3
                 grad_k0 = torch.empty_like(ctx.k0_meta, memory_format=torch.preserve_format)
                 grad_density = torch.empty_like(ctx.density_meta)
                 assert grad_k0.stride() == ctx.k0_meta.stride() and grad_density.is_contiguous()
@@ -370,7 +387,7 @@ class _FusedMarch(torch.autograd.Function):
                 if want_d:
                     grad_density = torch.zeros_like(ctx.density_meta)
                     density_bwd(grad_density, 1, None)
-        return grad_density, grad_k0, None, None, None, None, None
+        return (grad_density, grad_k0) + rays + (None,) * 3
 
 
 def _brick_backward(ctx, plan, density_bwd, g_feat, start, dirs, st):
@@ -452,7 +469,12 @@ def fused_march(density, k0, rays_o, rays_d, cfg, capacity=False, positions=Fals
     `capacity=True`: no host synchronisation; the M3-sized outputs are allocated at their upper bound and only their
     first off3[N] rows are defined (pass `off3[N:]` as `m_dev` to the consumers).
     `positions=True` (positional-encoding colour head): k0 must have zero channels (nothing is read from it) and the
-    fourth output is the kept samples' positions [M3,3] instead of the features, with no gradient."""
+    fourth output is the kept samples' positions [M3,3] instead of the features, with no gradient.
+    `rays_o` / `rays_d` that require grad get one (csrc/march.hip: march_ray_bwd, launched first in the backward; the
+    stop-gradients are DirectVoxGO._forward_raygrad's); with `positions=True` or NDC sampling that is a NotImplementedError."""
+    if torch.is_grad_enabled() and (rays_o.requires_grad or rays_d.requires_grad) and (positions or cfg.ndc_samples > 0):
+        raise NotImplementedError('fused_march: rays that require grad are not differentiated through '
+                                  + ('the positional-encoding head\'s position input' if positions else 'NDC sampling'))
     return _FusedMarch.apply(density, k0, rays_o.contiguous(), rays_d.contiguous(), cfg, capacity, positions)
 
 

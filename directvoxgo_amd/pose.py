@@ -5,7 +5,9 @@ hold.  This module makes the poses learnable: `CameraRefiner` holds one se(3) co
 rays that are differentiable in it, `DirectVoxGO.forward` renders such rays with gradients flowing back through the sample
 positions (ops.ray_points, ops.grid_sample's position gradient: csrc/grid_sample_xyz.hip), and `refine_poses` is the
 eager optimisation loop -- poses alone against a trained model (registration of new images included), or poses and model
-together.
+together.  `refine_poses(..., fused=True)` keeps the render on the fused march (csrc/march.hip: march_ray_bwd returns the
+ray gradients from the march's own backward) and, with `train_model`, steps the model by a train.TrainStep: the brick
+scatter with the Adam update inside it, as in any other training step.
 
 Pure torch: everything but `refine_poses`' model call runs on CPU tensors too.
 """
@@ -114,7 +116,8 @@ def _supported(model):
     return type(model) is DirectVoxGO and model.posbase_pe == 0
 
 
-def refine_poses(model, refiner, images, cfg_train, render_kwargs, n_iters, n_rand, lrate_pose, train_model=False, seed=None):
+def refine_poses(model, refiner, images, cfg_train, render_kwargs, n_iters, n_rand, lrate_pose, train_model=False, seed=None,
+                 fused=False):
     """Optimise `refiner.delta` against `images` by rendering `model` from the corrected poses -> the loss of every
     iteration (floats).
 
@@ -124,6 +127,12 @@ def refine_poses(model, refiner, images, cfg_train, render_kwargs, n_iters, n_ra
     are stepped in the same iteration by a second optimiser (train.create_optimizer_or_freeze_model(model, cfg_train, 0));
     without it they receive no gradient and `.grad` is left alone.
 
+    `fused=True` (a model with `model.fused`, else ValueError): `DirectVoxGO.fused_raygrad` is set on the model for the
+    duration of the loop, so the render is the fused march and `delta`'s gradient comes from dvgo_march_ray_bwd; with
+    `train_model` the model is then stepped by a `train.TrainStep(model, cfg_train, render_kwargs)` -- per iteration
+    `opt_pose.zero_grad()`, `loss = step(rays_o, rays_d, viewdirs, target, it + 1)`, `opt_pose.step()` -- whose backward
+    updates both grids inside the brick scatter where the optimizer allows it (their `.grad` stays None).
+
     The gradient reaches `delta` through the sample positions only (DirectVoxGO._forward_raygrad states the stop-gradients).
     Only a plain DirectVoxGO with posbase_pe == 0 is supported: DirectMPIGO (NDC warp), DirectContractedVoxGO (contraction
     Jacobian), TriPlaneVoxGO (plane sampler) and positional-encoding heads (position input of the head) lack their
@@ -132,7 +141,9 @@ def refine_poses(model, refiner, images, cfg_train, render_kwargs, n_iters, n_ra
         kind = type(model).__name__ + (' with posbase_pe > 0' if getattr(model, 'posbase_pe', 0) > 0 else '')
         raise NotImplementedError(f'refine_poses: {kind} is not supported: only a plain DirectVoxGO with posbase_pe == 0 has '
                                   'the position derivative of its sampler')
-    from .train import create_optimizer_or_freeze_model, render_loss
+    if fused and not getattr(model, 'fused', False):
+        raise ValueError('refine_poses(fused=True) needs a model on the fused march (model.fused)')
+    from .train import TrainStep, create_optimizer_or_freeze_model, render_loss
     dev = refiner.delta.device
     HW = refiner.HW
     n = HW.shape[0]
@@ -152,25 +163,42 @@ def refine_poses(model, refiner, images, cfg_train, render_kwargs, n_iters, n_ra
     if seed is not None:
         gen.manual_seed(int(seed))
     opt_pose = torch.optim.Adam([refiner.delta], lr=lrate_pose)
-    opt_model = create_optimizer_or_freeze_model(model, cfg_train, 0) if train_model else None
+    step = TrainStep(model, cfg_train, render_kwargs) if (fused and train_model) else None
+    opt_model = create_optimizer_or_freeze_model(model, cfg_train, 0) if (train_model and step is None) else None
     losses = []
-    for _ in range(int(n_iters)):
-        if not every:
-            view = torch.randint(n, (n_rand,), generator=gen).to(dev)
-            u = torch.rand((2, n_rand), generator=gen).to(dev)
-            pix_i = (u[0] * HW[view, 1]).long().minimum(HW[view, 1] - 1)
-            pix_j = (u[1] * HW[view, 0]).long().minimum(HW[view, 0] - 1)
-        target = flat[base[view] + pix_j * HW[view, 1] + pix_i]
-        rays_o, rays_d, viewdirs = refiner.rays(view, pix_i, pix_j)
-        res = model(rays_o, rays_d, viewdirs, global_step=None, **render_kwargs)
-        loss = render_loss(res, target, rays_o.shape[0], cfg_train)
-        opt_pose.zero_grad(set_to_none=True)
-        if opt_model is not None:
-            opt_model.zero_grad(set_to_none=True)
-            loss.backward()
-            opt_model.step()
-        else:
-            loss.backward(inputs=[refiner.delta])
-        opt_pose.step()
-        losses.append(loss.detach())
+    was = model.__dict__.get('fused_raygrad')          # (the class attribute unless somebody set it on the instance)
+    if fused:
+        model.fused_raygrad = True
+    try:
+        for it in range(int(n_iters)):
+            if not every:
+                view = torch.randint(n, (n_rand,), generator=gen).to(dev)
+                u = torch.rand((2, n_rand), generator=gen).to(dev)
+                pix_i = (u[0] * HW[view, 1]).long().minimum(HW[view, 1] - 1)
+                pix_j = (u[1] * HW[view, 0]).long().minimum(HW[view, 0] - 1)
+            target = flat[base[view] + pix_j * HW[view, 1] + pix_i]
+            rays_o, rays_d, viewdirs = refiner.rays(view, pix_i, pix_j)
+            if step is not None:
+                opt_pose.zero_grad(set_to_none=True)
+                loss = step(rays_o, rays_d, viewdirs, target, it + 1)
+                opt_pose.step()
+                losses.append(loss)
+                continue
+            res = model(rays_o, rays_d, viewdirs, global_step=None, **render_kwargs)
+            loss = render_loss(res, target, rays_o.shape[0], cfg_train)
+            opt_pose.zero_grad(set_to_none=True)
+            if opt_model is not None:
+                opt_model.zero_grad(set_to_none=True)
+                loss.backward()
+                opt_model.step()
+            else:
+                loss.backward(inputs=[refiner.delta])
+            opt_pose.step()
+            losses.append(loss.detach())
+    finally:
+        if fused:
+            if was is None:
+                del model.fused_raygrad
+            else:
+                model.fused_raygrad = was
     return [float(x) for x in losses]          # (read back once, after the loop)

@@ -302,7 +302,12 @@ class TrainStep:
     def __call__(self, rays_o, rays_d, viewdirs, target, global_step):
         """rays are this rank's shard; returns the (local share of the) loss as a 0-dim tensor (after `capture()`: a
         tensor that the next call overwrites)."""
-        if self._graph is not None and rays_o.shape == self._static[0].shape:
+        ray_grad = torch.is_grad_enabled() and (rays_o.requires_grad or rays_d.requires_grad)
+        if ray_grad and self.world > 1:
+            raise NotImplementedError('TrainStep: rays that require grad (learnable poses) are not built for data-parallel '
+                                      'training: the pose gradient would need its own reduction')
+        # (a captured graph holds copies of the rays: it cannot return a gradient to them.  Such a call runs eagerly)
+        if self._graph is not None and rays_o.shape == self._static[0].shape and not ray_grad:
             return self._replay(rays_o, rays_d, viewdirs, target)
         return self._eager(rays_o, rays_d, viewdirs, target, global_step)
 

@@ -40,8 +40,8 @@ extern "C" {
 
 /* version of this ABI; bumped on any signature change (6: the positional-encoding colour head; 7: the contracted
  * sampler and the distortion loss of unbounded scenes; 8: the tri-plane sampler; 9: the trilinear sample's gradient
- * with respect to the position) */
-#define DVGO_ABI_VERSION 10
+ * with respect to the position; 10: the LIIF plane decoder; 11: the fused march's gradient with respect to its rays) */
+#define DVGO_ABI_VERSION 11
 int dvgo_abi_version(void);
 
 /* Kernel-variant selection for A/B measurements (process-global; defaults are the fastest
@@ -298,6 +298,43 @@ int dvgo_march_density_bwd(const dvgo_rec2_t* rec2, const int32_t* n2, const int
                            int X, int Y, int Z, float* grad_density, int64_t grad_stride, float* grad_kept,
                            int32_t* brick_cursor, void* brick_recs,
                            void* stream);
+
+/* dvgo_march_ray_bwd: the gradient of the fused march with respect to its RAYS (csrc/march.hip; DESIGN.md section 6h;
+ *   camera-pose refinement on the fused path).  One wavefront per ray; metric steps only
+ *   (stepdist > 0: NDC spacing is not differentiated).
+ *   rec2 .. alphainv_last, interval, grad_weights, grad_last: as dvgo_march_density_bwd, from the same forward.  The walk
+ *   is that kernel's: chunks of 64 records from the far end, and per record the same g_d (K13 in double, dvgo_pow_neg, the
+ *   three double multiplies, narrowed once) and the same position p = fmaf(rays_dir, dist, rays_start), dist = stepdist *
+ *   step, with the same bits.
+ *   rays_o, rays_d [N,3], near, far: what dvgo_march_density's ray setup read; t_min and |d| = sqrtf(fmaf(dz, dz, fmaf(dy,
+ *   dy, dx * dx))) are recomputed from them by the same expressions.
+ *   density [X,Y,Z] contiguous; k0 with C channels and its four ELEMENT strides (as dvgo_march_gather); grad_feat [M3,C]
+ *   row-major in the M3 order of dvgo_march_gather, or NULL: no feature term.  grad_weights may be NULL when M3 == 0.
+ *   The grids must hold what the forward read: launch this before anything that updates them in place.
+ *   Per record, with the cell, the per-axis weights and the in-range test of the gather, and the corner chains of
+ *   dvgo_grid_sample_bwd_xyz (n = 0..7, corners outside skipped, each chain from 0):
+ *       dX = chain over the density grid;  ax = fmaf(g_d, dX, 0);  likewise ay, az
+ *       for a record kept by dvgo_march_gather (index i in the M3 order), when grad_feat is given, c ascending:
+ *           dX_c = chain over k0 channel c;  ax = fmaf(grad_feat[i * C + c], dX_c, ax);  likewise ay, az
+ *       g_p = (ax * ((float)(X-1) / (xyz_max[0] - xyz_min[0])), ay * ..., az * ...)
+ *       lam = t_min + dist / |d|
+ *   A record with g_d == 0 and no feature term contributes exact zeros.  Per ray, in float32 and in a fixed order (per
+ *   chunk a butterfly over the 64 lanes, lanes without a record adding 0; chunks far to near into one accumulator):
+ *       grad_o[ray] = sum g_p          grad_d[ray] = sum (lam * g_p)
+ *   Every ray < n_rays is written with plain stores by one lane, zeros for a ray without records: no atomics, no
+ *   workspace, nothing to zero beforehand, bitwise repeatable.  Channels-last k0 with C % 4 == 0 and 16-byte aligned k0
+ *   and grad_feat reads 16-byte vectors; everything else goes through the element strides.
+ *   n_rays == 0: no-op.  DVGO_EINVAL: negative n_rays or C, an axis < 1, stepdist <= 0, null required pointers, neither
+ *   n_steps_cumsum nor rec_stride > 0.  DVGO_ERANGE: n_rays * 64 >= 2^31. */
+int dvgo_march_ray_bwd(const dvgo_rec2_t* rec2, const int32_t* n2, const int64_t* n_steps,
+                       const int64_t* n_steps_cumsum, int64_t rec_stride, const int64_t* off3, int64_t n_rays,
+                       const float* rays_start, const float* rays_dir, float stepdist,
+                       const float* xyz_min, const float* xyz_max, const float* alphainv_last, float interval,
+                       const float* rays_o, const float* rays_d, float near, float far,
+                       const float* density, int X, int Y, int Z,
+                       const float* k0, int C, int64_t sC, int64_t sX, int64_t sY, int64_t sZ,
+                       const float* grad_weights /* [M3] */, const float* grad_last /* [N] */,
+                       const float* grad_feat /* [M3,C] */, float* grad_o, float* grad_d, void* stream);
 
 /* ---------------------------------------------------------------------------------
  * Brick scatter: the grid-gradient sums of grid_sampler_3d_backward (behind lib/dvgo.py:321; 8*C float atomics per

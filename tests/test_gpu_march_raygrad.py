@@ -1,0 +1,473 @@
+"""GPU: the fused march's gradient with respect to its rays (csrc/march.hip: dvgo_march_ray_bwd), from the kernel to
+pose.refine_poses(fused=True).
+
+  kernel      called directly on what a fused_march forward saved, grad_o / grad_d pre-filled with NaN, every ray inside the
+              bound of tests/march_raygrad_oracle.py: the edge-case table (tests/march_cases.py: n2 in {0, 1, 63, 64, 65, 256},
+              early stops on lane 63 of a chunk and lane 0 of the next, flagged and unflagged records in one ray, samples on
+              xyz_max whose upper corners are outside) and a random 20^3 scene with 96 rays; fixed-stride and exact record
+              layout; k0 as C = 12 channels-last (float4 path), the same tensor misaligned by one float (generic path), C = 3;
+              grad_last given and NULL, grad_feat NULL; N = 5 (a partly filled workgroup) and N = 0 (no launch)
+  end to end  with DirectVoxGO.fused_raygrad the result dict is the fused forward's bit for bit, ray_id the eager path's, and
+              rays_o.grad / rays_d.grad are held to the float64 restatement of tests/test_gpu_raygrad.py by its rule
+  grids       on the brick path everything the scatter reads keeps its bits when the rays require grad and both gradients stay
+              inside the brick oracle's bound (the scatter's own summation order is not repeatable); grad_o / grad_d repeat
+  order       one TrainStep call whose brick kernel applies Adam in place returns the ray gradients of the grids the forward read
+  refine      the capture of test_refine_poses_recovers_a_perturbed_capture comes back on the fused path; poses and model
+              together step the grids inside the brick kernel
+  captured    after TrainStep.capture() a call with rays that require grad runs eagerly
+  refused     NDC sampling, the positional-encoding head and a data-parallel TrainStep raise NotImplementedError for such rays
+The worst err / bound per kernel case is printed (pytest -s): information, never a threshold.
+"""
+import math
+
+import numpy as np
+import pytest
+import torch
+
+import march_cases as C
+import march_oracle as M
+import march_raygrad_oracle as MR
+from test_gpu_raygrad import (LRATE_POSE, RK, _capture, _device_record, _dict_bits_equal, _pose_errors, _restate, cu, host, in_layout,
+                              make_model, same_bits)
+
+pytestmark = pytest.mark.gpu
+
+# Rays left out of the kernel test because `march_oracle.density_bwd_reference` is itself non-finite for one of their records,
+# {scene: {ray: what excludes it}}.  None: with exp_d == inf the reference is p = (1 + inf)^-1.5 == 0, g_d == 0, and with
+# alpha == 1 the quotient acc / 1e-10 stays far inside float32; `march_raygrad_oracle.check` fails if this list and the rays
+# without a finite reference differ.
+EXCLUDED = {'fine129': {}, 'rand20': {}}
+
+
+class _Calls:
+    """names of the library calls issued inside, in order"""
+
+    def __enter__(self):
+        from directvoxgo_amd import _lib
+        self._L, self._orig, self.names = _lib, _lib.call, []
+
+        def call(name, *args):
+            self.names.append(name)
+            return self._orig(name, *args)
+        _lib.call = call
+        return self
+
+    def __exit__(self, *exc):
+        self._L.call = self._orig
+        return False
+
+
+class _stride_layout:
+    def __init__(self, layout):
+        self.layout = layout
+
+    def __enter__(self):
+        from directvoxgo_amd import fused as F
+        self.saved = F._MAX_STRIDE_SCRATCH_BYTES
+        if self.layout == 'exact':
+            F._MAX_STRIDE_SCRATCH_BYTES = 0
+
+    def __exit__(self, *exc):
+        from directvoxgo_amd import fused as F
+        F._MAX_STRIDE_SCRATCH_BYTES = self.saved
+        return False
+
+
+# ------------------------------------------------------------------------------------------ the kernel
+def _table_scene():
+    from directvoxgo_amd import fused as F
+    sc = C.fine_scene()
+    density = cu(sc.density)[None, None].contiguous()
+    cfg = F.MarchConfig(cu(sc.xyz_min), cu(sc.xyz_max), sc.stepdist, sc.act_shift, sc.interval, sc.thres, sc.near, sc.far,
+                        mask=cu(sc.mask), xyz2ijk_scale=cu(sc.mask_scale), xyz2ijk_shift=cu(sc.mask_shift))
+    o, d = (cu(a) for a in sc.arrays())
+    return sc, density, cfg, o, d
+
+
+def _random_scene():
+    from directvoxgo_amd import scenes
+    m = make_model(12, 20, seed=3)
+    o, d, _ = scenes.camera_rays(8, 12, 13.0, scenes.pose_spherical(30.0, -30.0, 4.0))
+    assert o.shape == (96, 3)
+    return None, m.density.detach().clone(), m._march_cfg(RK['near'], RK['far'], RK['stepsize']), o.cuda(), d.cuda()
+
+
+def _k0_variants(dims, seed):
+    """{name: ([1,C,X,Y,Z] device tensor, [C,X,Y,Z] numpy)}"""
+    rng = np.random.default_rng(seed)
+    v12 = (0.3 * rng.standard_normal((12, *dims))).astype(np.float32)
+    v3 = (0.3 * rng.standard_normal((3, *dims))).astype(np.float32)
+    out = {'cl12': (in_layout(v12, 'cl'), v12), 'cl12+1': (in_layout(v12, 'cl', 1), v12), 'cl3': (in_layout(v3, 'cl'), v3)}
+    assert out['cl12'][0].data_ptr() % 16 == 0 and out['cl12+1'][0].data_ptr() % 16 == 4 and out['cl12'][0].stride(1) == 1
+    return out
+
+
+def _forward(density, k0, o, d, cfg):
+    """a fused_march forward with rays that require grad -> (what it saved, rec_stride, outputs)"""
+    from directvoxgo_amd import fused as F
+    ro, rd = o.clone().requires_grad_(), d.clone().requires_grad_()
+    w, alpha, last, feat, ray_id, step_id, off3 = F.fused_march(density, k0, ro, rd, cfg)
+    fn = w.grad_fn
+    assert fn.ray_grad and len(fn.saved_tensors) == 12 and same_bits(fn.saved_tensors[10], o) and same_bits(fn.saved_tensors[11], d)
+    return fn.saved_tensors, fn.geom[8], w
+
+
+def _launch(L, saved, stride, cfg, o, d, density, k0, gw, gl, gfeat, N):
+    rec2, n2, n_steps, cum, off3, start, dirs, last = saved[:8]
+    X, Y, Z = density.shape[2:]
+    go = torch.full((max(N, 1), 3), float('nan'), device='cuda')
+    gd = torch.full((max(N, 1), 3), float('nan'), device='cuda')
+    L.call('dvgo_march_ray_bwd', rec2, n2, n_steps, cum if stride == 0 else None, stride, off3, N, start, dirs, cfg.stepdist,
+           cfg.xyz_min_h, cfg.xyz_max_h, last, cfg.interval, o, d, cfg.near, cfg.far, density, X, Y, Z, k0, k0.shape[1], k0.stride(1),
+           k0.stride(2), k0.stride(3), k0.stride(4), gw, gl, gfeat, go, gd, L.stream_of(go))
+    torch.cuda.synchronize()
+    return host(go), host(gd)
+
+
+def _records(saved, stride):
+    rec2, n2, n_steps, cum = (host(t) for t in saved[:4])
+    return M.Records(rec2, n2, M.rec_base(n_steps, cum if stride == 0 else None, stride)), n_steps
+
+
+def _t_min(o, d, cfg):
+    from directvoxgo_amd import render_utils
+    return host(render_utils.sample_pts_on_rays(o, d, cfg.xyz_min_t, cfg.xyz_max_t, cfg.near, cfg.far, cfg.stepdist)[5])
+
+
+# (k0 variant, grad_last given, grad_feat given)
+CASES = [('cl12', True, True), ('cl12+1', False, True), ('cl3', True, True), ('cl12', True, False)]
+
+
+@pytest.mark.parametrize('layout', ['stride', 'exact'])
+@pytest.mark.parametrize('which', ['fine129', 'rand20'])
+def test_kernel_inside_the_oracle_bound(which, layout):
+    from directvoxgo_amd import _lib as L
+    sc, density, cfg, o, d = _table_scene() if which == 'fine129' else _random_scene()
+    dims = tuple(int(v) for v in density.shape[2:])
+    ks = _k0_variants(dims, 17)
+    N = o.shape[0]
+    with _stride_layout(layout):
+        saved, stride, w = _forward(density, ks['cl12'][0], o, d, cfg)
+    assert (stride == 0) == (layout == 'exact')
+    Rc, n_steps = _records(saved, stride)
+    off3, last = host(saved[4])[:N + 1], host(saved[7])
+    M3 = int(off3[-1])
+    n3 = np.bincount(Rc.ray, Rc.flag, N).astype(np.int64)
+    if sc is not None:                                          # the chunk and stop cases are there, on the device's records
+        q = C.Result(Rc, n3, last, n_steps, host(saved[5]))
+        for name, target, pred in sc.rows:
+            assert pred(q), f'row {name} ({target}) does not hit its edge on the device'
+        assert {0, 1, 63, 64, 65, 256} <= set(Rc.n.tolist())
+        stops = {q.stopped_at(r) for r in range(N)}
+        assert {63, 64, 127, 192} <= stops                      # lane 63 of a chunk, lane 0 of the next
+        assert np.any((n3 > 0) & (n3 < Rc.n))                   # flagged and unflagged records in one ray
+    else:
+        assert Rc.ray.shape[0] >= M3 > 300
+    t_min = _t_min(o, d, cfg)
+    gen = torch.Generator(device='cuda').manual_seed(29)
+    gw = torch.randn(M3, device='cuda', generator=gen)
+    gl = torch.randn(N, device='cuda', generator=gen)
+    gwr = M.gw_per_record(Rc, off3, host(gw))
+    mn, mx = np.array(list(cfg.xyz_min_h), np.float32), np.array(list(cfg.xyz_max_h), np.float32)
+    dens_np = host(density)[0, 0]
+    for kname, with_last, with_feat in CASES:
+        k0, k0_np = ks[kname]
+        Cc = k0.shape[1]
+        gfeat = torch.randn((M3, Cc), device='cuda', generator=gen) if with_feat else None
+        go, gd = _launch(L, saved, stride, cfg, o, d, density, k0, gw, gl if with_last else None, gfeat, N)
+        G = MR.reference(Rc, last, gwr, host(gl) if with_last else None, cfg.interval, host(saved[5]), host(saved[6]), cfg.stepdist, mn, mx,
+                         dens_np, k0_np if with_feat else None, MR.feat_rows(Rc, off3, host(gfeat), Cc) if with_feat else None,
+                         t_min, host(d))
+        assert float(np.abs(G.A).max()) > 1e-3 and float(np.abs(G.B).max()) > 1e-3
+        what = f'{which} {layout} k0={kname} grad_last={with_last} grad_feat={with_feat}'
+        r = MR.check(G, go, gd, EXCLUDED[which], what=what)
+        print(f'\nworst err / bound  {what}: {r:.4f}', end='')
+    if sc is not None:                                          # (row 'on-xyz_max': samples whose upper corners are outside the lattice)
+        assert any(row[0] == 'on-xyz_max' for row in sc.rows)
+
+
+def test_partly_filled_workgroup_and_no_rays():
+    """N = 5: two workgroups of four wavefronts, the second with one ray; N = 0: nothing is launched or written"""
+    from directvoxgo_amd import _lib as L
+    sc, density, cfg, o, d = _table_scene()
+    o, d = o[:5].contiguous(), d[:5].contiguous()
+    ks = _k0_variants(tuple(int(v) for v in density.shape[2:]), 17)
+    k0, k0_np = ks['cl12']
+    saved, stride, w = _forward(density, k0, o, d, cfg)
+    Rc, _ = _records(saved, stride)
+    assert Rc.n.tolist()[0] == 0 and Rc.n.shape[0] == 5 and Rc.ray.shape[0] > 60
+    off3, last = host(saved[4])[:6], host(saved[7])
+    M3 = int(off3[-1])
+    gen = torch.Generator(device='cuda').manual_seed(31)
+    gw, gl, gfeat = torch.randn(M3, device='cuda', generator=gen), torch.randn(5, device='cuda', generator=gen), torch.randn((M3, 12), device='cuda', generator=gen)
+    go, gd = _launch(L, saved, stride, cfg, o, d, density, k0, gw, gl, gfeat, 5)
+    mn, mx = np.array(list(cfg.xyz_min_h), np.float32), np.array(list(cfg.xyz_max_h), np.float32)
+    G = MR.reference(Rc, last, M.gw_per_record(Rc, off3, host(gw)), host(gl), cfg.interval, host(saved[5]), host(saved[6]), cfg.stepdist, mn, mx,
+                     host(density)[0, 0], k0_np, MR.feat_rows(Rc, off3, host(gfeat), 12), _t_min(o, d, cfg), host(d))
+    print(f'\nworst err / bound  N=5: {MR.check(G, go, gd, (), what="N=5"):.4f}', end='')
+    go0, gd0 = _launch(L, saved, stride, cfg, o, d, density, k0, gw, gl, gfeat, 0)
+    assert np.all(np.isnan(go0)) and np.all(np.isnan(gd0))
+
+
+# ------------------------------------------------------------------------------------------ end to end
+@pytest.fixture(scope='module', params=[0, 12], ids=['colour-grid', 'fused-head'])
+def scene(request):
+    from directvoxgo_amd import scenes
+    m = make_model(request.param, 20, seed=3)
+    o, d, v = scenes.camera_rays(8, 12, 13.0, scenes.pose_spherical(30.0, -30.0, 4.0))
+    assert o.shape == (96, 3)
+    return m, o.cuda(), d.cuda(), v.cuda()
+
+
+def test_fused_forward_keeps_its_bits_and_ray_gradients_match_the_float64_restatement(scene):
+    m, o, d, v = scene
+    assert m.fused and m.fused_raygrad is False
+    plain = m(o, d, v, **RK)                                     # the fused forward, rays that do not require grad
+    eager = m(o.clone().requires_grad_(), d.clone().requires_grad_(), v, **RK)      # today's diversion: _forward_raygrad
+    ro, rd = o.clone().requires_grad_(), d.clone().requires_grad_()
+    m.fused_raygrad = True
+    try:
+        with _Calls() as calls:
+            res = m(ro, rd, v, **RK)
+            res['rgb_marched'].square().sum().backward()
+    finally:
+        del m.fused_raygrad
+    assert 'dvgo_march_density' in calls.names and 'dvgo_grid_sample_bwd_xyz' not in calls.names and calls.names.count('dvgo_march_ray_bwd') == 1
+    _dict_bits_equal({k: t.detach() for k, t in plain.items()}, {k: t.detach() for k, t in res.items()})
+    assert same_bits(res['ray_id'], eager['ray_id']) and res['ray_id'].numel() > 300
+    assert ro.grad is not None and rd.grad is not None
+    rec = _device_record(m, o, d)
+    assert same_bits(rec['ray_id0'][rec['m1']][rec['m2']], res['ray_id'])         # the record is this forward's
+    o64, d64, marched64 = _restate(m, o, d, v, rec, torch.float64)
+    o32, d32, _ = _restate(m, o, d, v, rec, torch.float32)
+    assert float((marched64 - res['rgb_marched'].detach().cpu().double()).abs().max()) < 1e-4
+    name = 'fused-head' if m.rgbnet is not None else 'colour-grid'
+    for what, g64, g32, dev in (('rays_o.grad', o64, o32, ro.grad), ('rays_d.grad', d64, d32, rd.grad)):
+        e32 = float((g32 - g64).abs().max())
+        err = float((dev.detach().cpu().double() - g64).abs().max())
+        print(f'\nfused march {name} {what}: max |g64| {float(g64.abs().max()):.4g}  e32 {e32:.4g}  device error {err:.4g}  (allowed {4 * e32:.4g})', end='')
+        assert float(g64.abs().max()) > 1e-3 and e32 > 0
+        assert err <= 4 * e32, (what, err, e32)
+
+
+def _rays96():
+    from directvoxgo_amd import scenes
+    o, d, v = scenes.camera_rays(8, 12, 13.0, scenes.pose_spherical(30.0, -30.0, 4.0))
+    return o.cuda(), d.cuda(), v.cuda()
+
+
+def _sorted_lists(ins):
+    """the brick lists of one dvgo_brick_accumulate as sets: the 16-byte records of every brick in lexicographic order"""
+    off, recs = ins['off'].astype(np.int64), ins['recs'].reshape(-1, 4).view(np.int32)
+    brick = np.repeat(np.arange(off.shape[0] - 1), np.diff(off))
+    order = np.lexsort((recs[:, 3], recs[:, 2], recs[:, 1], recs[:, 0], brick))
+    return recs[order]
+
+
+def test_grid_gradients_are_what_they_were_and_ray_gradients_repeat():
+    """The brick path (C = 12, both grids want a gradient): nothing but the two new outputs moves.
+
+    One would want density.grad and k0.grad bit-equal to those of the same backward with rays that do not require grad.
+    That cannot be asserted of this scatter: march_density_bwd reserves the list slots of a brick with one returning atomic
+    per chunk and brick_accumulate takes its sort tickets with LDS atomics, so the order in which a voxel's terms are summed
+    differs from run to run, with or without this feature.  Measured on an MI355X (this scene, three backward passes: plain
+    rays, rays requiring grad, rays requiring grad again): plain against rays, density.grad differs in 10 of 8000 elements and
+    k0.grad in 138 of 96000, max |diff| 3.7e-9 at max |value| 0.17; rays against rays AGAIN, the same setting twice, 26 and
+    292 elements, max |diff| 7.5e-9; the brick lists were in a different order in every pass.  The test prints these figures.
+    What the test holds instead, and it is no less: everything the scatter
+    READS is bit-equal between the passes -- the upstream gradients handed to dvgo_march_density_bwd, grad_feat, the ray
+    tables, the brick offsets, and the brick lists as sets (records sorted within each brick; a record carries the sample's
+    density gradient g_d) -- and every pass's density.grad and k0.grad are inside tests/brick_oracle.py's bound of the float64
+    sums of those identical inputs (`LaunchSpy`), so two passes differ by at most twice that bound.  grad_o and grad_d, which
+    have a fixed summation order, are bit-equal between two runs."""
+    import brick_oracle as B
+    m = make_model(12, 20, seed=3)
+    o, d, v = _rays96()
+    m.fused_raygrad = True
+    ix = B.param_index('dvgo_march_density_bwd')
+
+    def run(need):
+        m.zero_grad(set_to_none=True)
+        ro, rd = o.clone().requires_grad_(need), d.clone().requires_grad_(need)
+        seen = {}
+        with B.LaunchSpy(check=True) as spy:
+            call = spy._L.call
+
+            def tap(name, *args):
+                if name == 'dvgo_march_density_bwd':
+                    seen['gw'], seen['gl'] = (host(args[ix[k]]).copy() for k in ('grad_weights', 'grad_last'))
+                return call(name, *args)
+            spy._L.call = tap
+            m(ro, rd, v, **RK)['rgb_marched'].square().sum().backward()
+            torch.cuda.synchronize()
+        assert len(spy.launches) == 1 and spy.launches[0].kind == 'dense' and ('dvgo_march_ray_bwd' in spy.calls) == need
+        if need:
+            assert spy.calls.index('dvgo_march_ray_bwd') < spy.calls.index('dvgo_march_density_bwd')
+        return dict(gd=m.density.grad.clone(), gk=m.k0.grad.clone(), go=ro.grad, gr=rd.grad, ins=spy.launches[0].inputs,
+                    worst=spy.launches[0].worst, **seen)
+
+    plain, first, second = run(False), run(True), run(True)
+    assert plain['go'] is None and plain['gr'] is None and float(plain['gd'].abs().sum()) > 0 and float(plain['gk'].abs().sum()) > 0
+    for other in (first, second):
+        assert same_bits(plain['gw'], other['gw']) and same_bits(plain['gl'], other['gl'])
+        for k in ('off', 'grad_feat', 'rays_start', 'rays_dir'):
+            assert same_bits(plain['ins'][k], other['ins'][k]), k
+        assert plain['ins']['recs'].shape == other['ins']['recs'].shape and plain['ins']['recs'].shape[0] > 300
+        assert np.array_equal(_sorted_lists(plain['ins']), _sorted_lists(other['ins']))
+        assert plain['gk'].stride() == other['gk'].stride()
+    for name, a, b in (('plain / rays', plain, first), ('rays / rays again', first, second)):
+        for g in ('gd', 'gk'):
+            diff = (a[g] - b[g]).abs()
+            print(f'\n{name}: {g} differs in {int((diff != 0).sum())} of {diff.numel()} elements, max |diff| {float(diff.max()):.3g} '
+                  f'(max |value| {float(a[g].abs().max()):.3g}); lists in the same order: {bool(np.array_equal(a["ins"]["recs"], b["ins"]["recs"]))}', end='')
+    print(f'\nworst err / bound of the dense gradients against the float64 sums: {[round(float(x["worst"]), 4) for x in (plain, first, second)]}', end='')
+    assert same_bits(first['go'], second['go']) and same_bits(first['gr'], second['gr'])
+    assert float(first['go'].abs().sum()) > 0 and float(first['gr'].abs().sum()) > 0
+    assert bool(torch.isfinite(first['go']).all()) and bool(torch.isfinite(first['gr']).all())
+
+
+def test_ray_kernel_reads_the_grids_the_forward_read_not_the_updated_ones():
+    """One TrainStep call on path 'fused' (the brick kernel applies Adam to both grids in place, lr 0.1) with rays that require
+    grad: their gradients are those of a plain backward through the same forward on an identical model that nobody steps.
+    Fails if dvgo_march_ray_bwd runs after the in-place update."""
+    from directvoxgo_amd.train import FINE_TRAIN, TrainStep, fused_render_loss
+    o, d, v = _rays96()
+    rk = dict(near=2.0, far=6.0, stepsize=0.5, bg=1)
+    target = torch.rand((96, 3), generator=torch.Generator().manual_seed(9)).cuda()
+    m, twin = make_model(12, 20, seed=3), make_model(12, 20, seed=3)
+    for a, b in zip(m.parameters(), twin.parameters()):
+        assert same_bits(a, b)
+    m.fused_raygrad = twin.fused_raygrad = True
+    cfg = dict(FINE_TRAIN)
+    step = TrainStep(m, cfg, rk)
+    before_d, before_k = m.density.detach().clone(), m.k0.detach().clone()
+    ro, rd = o.clone().requires_grad_(), d.clone().requires_grad_()
+    with _Calls() as calls:
+        loss = step(ro, rd, v, target, 5000)
+    assert step.last_fused_adam and math.isfinite(float(loss))
+    assert not torch.equal(before_d, m.density.detach()) and not torch.equal(before_k, m.k0.detach())
+    assert m.density.grad is None and m.k0.grad is None
+    assert calls.names.index('dvgo_march_ray_bwd') < calls.names.index('dvgo_brick_accumulate')
+    ro2, rd2 = o.clone().requires_grad_(), d.clone().requires_grad_()
+    res = twin(ro2, rd2, v, global_step=5000, **rk)
+    fused_render_loss(res, target, 96, cfg).backward()
+    assert same_bits(before_d, twin.density.detach())           # nobody stepped the twin
+    assert float(ro.grad.abs().sum()) > 0 and float(rd.grad.abs().sum()) > 0
+    assert same_bits(ro.grad, ro2.grad) and same_bits(rd.grad, rd2.grad)
+
+
+# ------------------------------------------------------------------------------------------ refine_poses(fused=True)
+def test_refine_poses_fused_recovers_a_perturbed_capture(monkeypatch):
+    from directvoxgo_amd import train
+    from directvoxgo_amd.pose import CameraRefiner, refine_poses
+    from directvoxgo_amd.train import COARSE_TRAIN
+    m = make_model(0, 24, seed=5, capture=True)
+    for p in m.parameters():
+        p.requires_grad_(False)
+    true, noisy, HW, Ks = _capture(seed=7)
+    n, hw = len(true), int(HW[0, 0])
+    rk = dict(near=2.0, far=6.0, stepsize=0.5, bg=1)
+    exact = CameraRefiner(true, HW, Ks).cuda()
+    view = torch.arange(n, device='cuda').repeat_interleave(hw * hw)
+    p = torch.arange(hw * hw, device='cuda').repeat(n)
+    with torch.no_grad():
+        o, d, v = exact.rays(view, p % hw, p // hw)
+        images = m(o, d, v, **rk)['rgb_marched'].reshape(n, hw, hw, 3)
+    assert float(images.std()) > 0.05
+    ref = CameraRefiner(noisy, HW, Ks).cuda()
+    rot0, tr0 = _pose_errors(ref.poses(), true)
+    cfg = dict(COARSE_TRAIN, weight_entropy_last=0.0, weight_rgbper=0.0)
+    with _Calls() as calls:
+        losses = refine_poses(m, ref, images, cfg, rk, n_iters=200, n_rand=None, lrate_pose=LRATE_POSE, fused=True)
+    rot1, tr1 = _pose_errors(ref.poses(), true)
+    assert calls.names.count('dvgo_march_ray_bwd') == 200 and 'dvgo_grid_sample_bwd_xyz' not in calls.names
+    assert 'fused_raygrad' not in m.__dict__                     # restored
+    print(f'\nrefine_poses(fused=True): loss {losses[0]:.3e} -> {losses[-1]:.3e}; rotation error (deg) {np.degrees(rot0.numpy()).round(3).tolist()} -> '
+          f'{np.degrees(rot1.numpy()).round(3).tolist()}; translation error {tr0.numpy().round(4).tolist()} -> {tr1.numpy().round(4).tolist()}', end='')
+    assert torch.allclose(rot0, torch.full_like(rot0, math.radians(2.0)), atol=1e-4) and torch.allclose(tr0, torch.full_like(tr0, 0.12), atol=1e-4)
+    assert len(losses) == 200 and all(math.isfinite(x) for x in losses)
+    assert losses[-1] < losses[0]
+    assert bool((rot1 < rot0).all()) and bool((tr1 < tr0).all())
+    assert all(q.grad is None for q in m.parameters())           # a frozen model is left alone
+
+    # poses and model together: the model is stepped by a TrainStep, the grids inside the brick kernel
+    steps = []
+
+    class Recorded(train.TrainStep):
+        def __init__(self, *a, **k):
+            super().__init__(*a, **k)
+            steps.append(self)
+    monkeypatch.setattr(train, 'TrainStep', Recorded)
+    m2 = make_model(0, 24, seed=5, capture=True)
+    ref2 = CameraRefiner(noisy, HW, Ks).cuda()
+    before = m2.density.detach().clone()
+    # masked Adam on both grids (the fine stage's setting): the update the brick kernel can apply itself
+    cfg2 = dict(COARSE_TRAIN, skip_zero_grad_fields=['density', 'k0'])
+    with _Calls() as calls:
+        losses2 = refine_poses(m2, ref2, images, cfg2, rk, n_iters=20, n_rand=1024, lrate_pose=LRATE_POSE, train_model=True, seed=1, fused=True)
+    assert len(losses2) == 20 and all(math.isfinite(x) for x in losses2)
+    g = ref2.delta.grad
+    assert g is not None and bool(torch.isfinite(g).all()) and float(g.abs().sum()) > 0
+    assert not torch.equal(before, m2.density.detach()) and float(ref2.delta.detach().abs().sum()) > 0
+    assert m2.density.grad is None and m2.k0.grad is None
+    assert len(steps) == 1 and steps[0].last_fused_adam and calls.names.count('dvgo_brick_accumulate') == 20
+    assert calls.names.count('dvgo_march_ray_bwd') == 20 and 'fused_raygrad' not in m2.__dict__
+
+
+# ------------------------------------------------------------------------------------------ a captured step
+def test_captured_step_runs_eagerly_for_rays_that_require_grad():
+    from directvoxgo_amd.train import FINE_TRAIN, TrainStep
+    o, d, v = _rays96()
+    rk = dict(near=2.0, far=6.0, stepsize=0.5, bg=1)
+    target = torch.rand((96, 3), generator=torch.Generator().manual_seed(9)).cuda()
+    m = make_model(12, 20, seed=3)
+    m.fused_raygrad = True
+    step = TrainStep(m, dict(FINE_TRAIN), rk)
+    assert step.capture(o, d, v, target, global_step=5000)
+    with _Calls() as calls:
+        step(o, d, v, target, 5004)
+    assert 'dvgo_march_density' not in calls.names              # replayed
+    ro, rd = o.clone().requires_grad_(), d.clone().requires_grad_()
+    with _Calls() as calls:
+        loss = step(ro, rd, v, target, 5005)
+    torch.cuda.synchronize()
+    assert 'dvgo_march_density' in calls.names and calls.names.count('dvgo_march_ray_bwd') == 1
+    assert math.isfinite(float(loss))
+    for g in (ro.grad, rd.grad):
+        assert g is not None and bool(torch.isfinite(g).all()) and float(g.abs().sum()) > 0
+    with _Calls() as calls:
+        step(o, d, v, target, 5006)
+    assert 'dvgo_march_density' not in calls.names              # and the graph is still there for plain rays
+
+
+# ------------------------------------------------------------------------------------------ what is not differentiated
+def test_rays_that_require_grad_are_refused_where_the_march_is_not_differentiated():
+    """NDC sampling and the positional-encoding head's positions: NotImplementedError in the forward, before any launch;
+    the same calls with plain rays go through.  A data-parallel TrainStep refuses such rays too."""
+    from directvoxgo_amd import fused as F
+    from directvoxgo_amd.train import FINE_TRAIN, TrainStep
+    sc = C.ndc_scene(64)
+    density = cu(sc.density)[None, None].contiguous()
+    k0 = in_layout((0.3 * np.random.default_rng(1).standard_normal((sc.C, *sc.density.shape))).astype(np.float32), 'cl')
+    cfg = F.MarchConfig(cu(sc.xyz_min), cu(sc.xyz_max), sc.stepdist, sc.act_shift, sc.interval, sc.thres, sc.near, sc.far,
+                        mask=cu(sc.mask), xyz2ijk_scale=cu(sc.mask_scale), xyz2ijk_shift=cu(sc.mask_shift), ndc_samples=sc.ndc)
+    o, d = (cu(a) for a in sc.arrays())
+    assert F.fused_march(density, k0, o, d, cfg)[0].numel() > 0
+    with _Calls() as calls, pytest.raises(NotImplementedError, match='NDC'):
+        F.fused_march(density, k0, o.clone().requires_grad_(), d, cfg)
+    assert calls.names == []
+    sc, density, cfg, o, d = _table_scene()
+    none = torch.zeros((1, 0, *density.shape[2:]), device='cuda')
+    assert F.fused_march(density, none, o, d, cfg, positions=True)[3].shape[1] == 3
+    with _Calls() as calls, pytest.raises(NotImplementedError, match='positional'):
+        F.fused_march(density, none, o, d.clone().requires_grad_(), cfg, positions=True)
+    assert calls.names == []
+    with torch.no_grad():                                       # no grad mode: nothing asks for the derivative
+        assert F.fused_march(density, none, o, d.clone().requires_grad_(), cfg, positions=True)[3].shape[1] == 3
+    m = make_model(12, 20, seed=3)
+    step = TrainStep(m, dict(FINE_TRAIN), dict(near=2.0, far=6.0, stepsize=0.5, bg=1))
+    step.world = 2                                              # (what a second rank would make it; nothing is launched)
+    ro, rd, v = _rays96()
+    with _Calls() as calls, pytest.raises(NotImplementedError, match='data-parallel'):
+        step(ro.clone().requires_grad_(), rd, v, torch.zeros((96, 3), device='cuda'), 5000)
+    assert calls.names == []
