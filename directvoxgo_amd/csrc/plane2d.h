@@ -1,0 +1,159 @@
+// The bilinear corner walk of a 2-D feature plane, shared by triplane.hip and plane_rows.hip: the plane descriptor,
+// the per-axis floor and weights, the four-corner fma chain, the four-corner atomic flush and the run-merging walk of the
+// gradient scatter (include/dvgo_hip.h, the tri-plane block, states the arithmetic).
+#pragma once
+#include <limits.h>
+
+#include "common.h"
+
+// samples a lane of a scatter merges before its atomics (run == 0 at the entry points)
+#define TP_RUN_DEFAULT 4
+
+struct TpPlane {
+  float* p;
+  int H, W;
+  int64_t sC, sH, sW;
+};
+
+// plane s of the three and the world axes its rows / columns follow, by selects among three by-value kernel arguments
+// (one argument struct holding all three, indexed by s, was copied to scratch: 128 B per lane)
+__device__ __forceinline__ TpPlane tp_pick(const TpPlane A, const TpPlane B, const TpPlane D, int s, int& ah, int& aw) {
+  ah = (s == 0) ? 1 : (s == 1) ? 0 : 2;
+  aw = (s == 0) ? 2 : (s == 1) ? 1 : 0;
+  TpPlane q;
+  q.p = (s == 0) ? A.p : (s == 1) ? B.p : D.p;
+  q.H = (s == 0) ? A.H : (s == 1) ? B.H : D.H;
+  q.W = (s == 0) ? A.W : (s == 1) ? B.W : D.W;
+  q.sC = (s == 0) ? A.sC : (s == 1) ? B.sC : D.sC;
+  q.sH = (s == 0) ? A.sH : (s == 1) ? B.sH : D.sH;
+  q.sW = (s == 0) ? A.sW : (s == 1) ? B.sW : D.sW;
+  return q;
+}
+
+struct BiSetup {
+  int h0, w0;            // floor corner (may be -1 or size-1 at the edges)
+  float wh0, wh1, ww0, ww1;
+};
+
+// floor and weights of one axis: the expressions of dvgo_tri_from_g.  The int conversion is clamped so that a
+// coordinate far outside the box cannot overflow h0 + 1; such a corner is out of range either way.
+__device__ __forceinline__ void tp_axis(float g, int& i0, float& w0, float& w1) {
+  const float f = floorf(g);
+  i0 = (int)fminf(fmaxf(f, -1.0e9f), 1.0e9f);
+  w0 = (f + 1.0f) - g;
+  w1 = g - f;
+}
+
+__device__ __forceinline__ BiSetup tp_setup(const float* __restrict__ xyz, const float* __restrict__ mn,
+                                            const float* __restrict__ mx, int64_t m, int ah, int aw, int H, int W) {
+  BiSetup b;
+  tp_axis(dvgo_src_index(xyz[3 * m + ah], mn[ah], mx[ah], H), b.h0, b.wh0, b.wh1);
+  tp_axis(dvgo_src_index(xyz[3 * m + aw], mn[aw], mx[aw], W), b.w0, b.ww0, b.ww1);
+  return b;
+}
+
+template <int VEC> struct TpVal { float v[VEC]; };
+
+template <int VEC>
+__device__ __forceinline__ TpVal<VEC> tp_load(const float* __restrict__ p, int64_t sC) {
+  TpVal<VEC> r;
+  if constexpr (VEC == 4) {
+    const float4 q = *reinterpret_cast<const float4*>(p);
+    r.v[0] = q.x; r.v[1] = q.y; r.v[2] = q.z; r.v[3] = q.w;
+  } else if constexpr (VEC == 2) {
+    const float2 q = *reinterpret_cast<const float2*>(p);
+    r.v[0] = q.x; r.v[1] = q.y;
+  } else {
+#pragma unroll
+    for (int i = 0; i < VEC; ++i) r.v[i] = p[i * sC];
+  }
+  return r;
+}
+
+// VEC channels from c on of plane q at sample m
+template <int VEC>
+__device__ __forceinline__ TpVal<VEC> tp_sample(const TpPlane& q, int ah, int aw, int c, const float* __restrict__ xyz,
+                                                const float* __restrict__ mn, const float* __restrict__ mx, int64_t m) {
+  const BiSetup b = tp_setup(xyz, mn, mx, m, ah, aw, q.H, q.W);
+  const int h1 = b.h0 + 1, w1 = b.w0 + 1;
+  const bool okh0 = (b.h0 >= 0) & (b.h0 < q.H), okh1 = (h1 >= 0) & (h1 < q.H);
+  const bool okw0 = (b.w0 >= 0) & (b.w0 < q.W), okw1 = (w1 >= 0) & (w1 < q.W);
+  const int64_t oh0 = (int64_t)min(max(b.h0, 0), q.H - 1) * q.sH, oh1 = (int64_t)min(max(h1, 0), q.H - 1) * q.sH;
+  const int64_t ow0 = (int64_t)min(max(b.w0, 0), q.W - 1) * q.sW, ow1 = (int64_t)min(max(w1, 0), q.W - 1) * q.sW;
+  const float* base = q.p + (int64_t)c * q.sC;
+  const TpVal<VEC> v00 = tp_load<VEC>(base + oh0 + ow0, q.sC), v01 = tp_load<VEC>(base + oh0 + ow1, q.sC);
+  const TpVal<VEC> v10 = tp_load<VEC>(base + oh1 + ow0, q.sC), v11 = tp_load<VEC>(base + oh1 + ow1, q.sC);
+  const float k00 = b.wh0 * b.ww0, k01 = b.wh0 * b.ww1, k10 = b.wh1 * b.ww0, k11 = b.wh1 * b.ww1;
+  TpVal<VEC> r;
+#pragma unroll
+  for (int i = 0; i < VEC; ++i) {
+    float acc = 0.f;
+    acc = (okh0 & okw0) ? fmaf(v00.v[i], k00, acc) : acc;
+    acc = (okh0 & okw1) ? fmaf(v01.v[i], k01, acc) : acc;
+    acc = (okh1 & okw0) ? fmaf(v10.v[i], k10, acc) : acc;
+    acc = (okh1 & okw1) ? fmaf(v11.v[i], k11, acc) : acc;
+    r.v[i] = acc;
+  }
+  return r;
+}
+
+// the four corner sums of cell (h0, w0) -> the plane, out-of-range corners dropped
+__device__ __forceinline__ void tp_flush(const TpPlane& q, float* __restrict__ base, int h0, int w0, float a00, float a01,
+                                         float a10, float a11) {
+  const int h1 = h0 + 1, w1 = w0 + 1;
+  const bool okh0 = (h0 >= 0) & (h0 < q.H), okh1 = (h1 >= 0) & (h1 < q.H);
+  const bool okw0 = (w0 >= 0) & (w0 < q.W), okw1 = (w1 >= 0) & (w1 < q.W);
+  if (okh0 & okw0) atomicAdd(base + (int64_t)h0 * q.sH + (int64_t)w0 * q.sW, a00);
+  if (okh0 & okw1) atomicAdd(base + (int64_t)h0 * q.sH + (int64_t)w1 * q.sW, a01);
+  if (okh1 & okw0) atomicAdd(base + (int64_t)h1 * q.sH + (int64_t)w0 * q.sW, a10);
+  if (okh1 & okw1) atomicAdd(base + (int64_t)h1 * q.sH + (int64_t)w1 * q.sW, a11);
+}
+
+// One lane of the gradient scatter of both translation units: lane tid of total = nchunk * 3C owns (a run of `run`
+// consecutive samples, plane s, channel c) and reads g[s * plane_off + m * gstride + c]; it keeps the four corner sums of
+// the texel cell it is in in registers and flushes them when the cell changes and at the end of its run.
+// CFAST: channel fastest (channels-last planes), else sample fastest.
+template <bool CFAST>
+__device__ __forceinline__ void tp_scatter_lane(const TpPlane PA, const TpPlane PB, const TpPlane PC, int C,
+                                                const float* __restrict__ grad, int64_t gstride, int64_t plane_off,
+                                                const float* __restrict__ xyz, const float* __restrict__ mn,
+                                                const float* __restrict__ mx, int64_t M, int run, int64_t nchunk,
+                                                int64_t total) {
+  const int64_t tid = (int64_t)blockIdx.x * DVGO_BLOCK + threadIdx.x;
+  if (tid >= total) return;
+  int64_t chunk;
+  int s, c;
+  if (CFAST) {
+    chunk = tid / (3 * C);
+    const int r = (int)(tid - chunk * (3 * C));
+    s = r / C;
+    c = r - s * C;
+  } else {
+    const int sc = (int)(tid / nchunk);
+    chunk = tid - (int64_t)sc * nchunk;
+    s = sc / C;
+    c = sc - s * C;
+  }
+  int ah, aw;
+  const TpPlane q = tp_pick(PA, PB, PC, s, ah, aw);
+  float* base = q.p + (int64_t)c * q.sC;
+  const float* g = grad + (int64_t)s * plane_off + c;
+  const int64_t m0 = chunk * run;
+  const int64_t m1 = (m0 + run < M) ? m0 + run : M;
+  int ch = INT_MIN, cw = INT_MIN;
+  float a00 = 0.f, a01 = 0.f, a10 = 0.f, a11 = 0.f;
+  for (int64_t m = m0; m < m1; ++m) {
+    const BiSetup b = tp_setup(xyz, mn, mx, m, ah, aw, q.H, q.W);
+    const float gv = g[m * gstride];
+    if ((b.h0 != ch) | (b.w0 != cw)) {
+      if (ch != INT_MIN) tp_flush(q, base, ch, cw, a00, a01, a10, a11);
+      ch = b.h0; cw = b.w0;
+      a00 = a01 = a10 = a11 = 0.f;
+    }
+    a00 += (b.wh0 * b.ww0) * gv;
+    a01 += (b.wh0 * b.ww1) * gv;
+    a10 += (b.wh1 * b.ww0) * gv;
+    a11 += (b.wh1 * b.ww1) * gv;
+  }
+  if (ch != INT_MIN) tp_flush(q, base, ch, cw, a00, a01, a10, a11);
+}

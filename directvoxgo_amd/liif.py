@@ -56,7 +56,7 @@ class LIIFTriPlaneVoxGO(TriPlaneVoxGO):
             raise NotImplementedError('implicit_voxel_feat=False is the bilinear path: use triplane.TriPlaneVoxGO')
         if not kwargs.pop('liif', True):
             raise NotImplementedError('liif=False with implicit_voxel_feat=True (the bilinear `interpolate` decoder, '
-                                      'lib/tri_dvgo.py:568-607) is not built')
+                                      'lib/tri_dvgo.py:568-607) is interp.InterpTriPlaneVoxGO')
         for key, why in _LEFT_OUT.items():
             if kwargs.pop(key, False):
                 raise NotImplementedError(f'{key}: {why}')

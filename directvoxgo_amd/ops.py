@@ -10,6 +10,8 @@ saved-tensor conventions) on top of the HIP kernels:
   triplane_sample             lib/tri_dvgo.py:456-469 (grid_sampler2D -> three F.grid_sample, cat or sum, + backward)
   liif_gather, liif_blend,    lib/tri_dvgo.py:481-565 (liif_interpolate: nearest-texel rows, blend weights, blend, + backward;
   liif_decode                 the Interp_MLPs between them stay torch modules)
+  plane_rows, interp_decode   lib/tri_dvgo.py:568-607 (interpolate, liif=False: bilinear features, sampled coordinates and their
+                              encoding as one MLP input row per plane, + backward; the Interp_MLPs stay torch modules)
   segment_coo                 torch_scatter.segment_coo(src, index, out, reduce='sum')
   total_variation_add_grad    lib/cuda/total_variation.cpp:16-24
 """
@@ -397,6 +399,99 @@ def liif_decode(planes, nets, xyz, xyz_min, xyz_max, world_size, cell_decode=Tru
     _, E, M, D = inp.shape
     pred = torch.cat([nets['xy'](inp[0].reshape(E * M, D)), nets['yz'](inp[1:].reshape(2 * E * M, D))])
     return liif_blend(pred.reshape(3, E, M, -1), wgt, aggregation)
+
+
+# ---------------------------------------------------------------------------------------------- bilinear plane decoder
+def _rows_width(C, n_freq, cell_decode):
+    n_freq = int(n_freq)
+    if n_freq < 1:
+        raise ValueError(f'n_freq must be at least 1, got {n_freq}')
+    return n_freq, C + 2 + 4 * n_freq + (2 if cell_decode else 0)
+
+
+def plane_rows_fwd(planes, xyz, xyz_min, xyz_max, world_size, n_freq, cell_decode=True):
+    """dvgo_plane_rows_fwd on the planes' strides as they are: xyz [M,3] -> inp [3,M,D], D = C + 2 + 4 * n_freq (+ 2 with
+    cell_decode).  No autograd."""
+    planes, geoms, C, M, (Wx, Wy, Wz) = _liif_args(planes, xyz, world_size)
+    P, D = _rows_width(C, n_freq, cell_decode)
+    inp = torch.empty((3, M, D), dtype=torch.float32, device=xyz.device)
+    (Ha, Wa, ca, ha, wa), (Hb, Wb, cb, hb, wb), (Hc, Wc, cc, hc, wc) = geoms
+    with L.device_of(xyz):
+        L.call('dvgo_plane_rows_fwd', planes[0], Ha, Wa, ca, ha, wa, planes[1], Hb, Wb, cb, hb, wb, planes[2], Hc, Wc, cc, hc, wc,
+               C, xyz, xyz_min, xyz_max, M, Wx, Wy, Wz, P, int(bool(cell_decode)), inp, stream_of(xyz))
+    return inp
+
+
+def plane_rows_bwd(grad_inp, grads, xyz, xyz_min, xyz_max, world_size, n_freq, cell_decode=True, run=0):
+    """dvgo_plane_rows_bwd: accumulates w * (the first C columns of grad_inp [3,M,D]) into the three buffers `grads` (shaped
+    and strided like planes) in place.  `run`: samples a lane merges before its atomics (0: the library's default)."""
+    grads, geoms, C, M, (Wx, Wy, Wz) = _liif_args(grads, xyz, world_size)
+    P, D = _rows_width(C, n_freq, cell_decode)
+    check_input(grad_inp, 'grad_inp'); check_f32(grad_inp, 'grad_inp')
+    if tuple(grad_inp.shape) != (3, M, D):
+        raise RuntimeError('grad_inp has the wrong shape')
+    (Ha, Wa, ca, ha, wa), (Hb, Wb, cb, hb, wb), (Hc, Wc, cc, hc, wc) = geoms
+    with L.device_of(xyz):
+        L.call('dvgo_plane_rows_bwd', grad_inp, grads[0], Ha, Wa, ca, ha, wa, grads[1], Hb, Wb, cb, hb, wb, grads[2], Hc, Wc, cc,
+               hc, wc, C, xyz, xyz_min, xyz_max, M, Wx, Wy, Wz, P, int(bool(cell_decode)), int(run), stream_of(xyz))
+    return grads
+
+
+class _PlaneRows(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, xy, yz, zx, xyz, xyz_min, xyz_max, world_size, n_freq, cell_decode):
+        planes = [xy, yz, zx]
+        M = xyz.shape[0]
+        relayout = TRIPLANE_RELAYOUT and M >= max(p.shape[2] * p.shape[3] for p in planes)
+        ctx.relayout = [relayout and not _is_channels_last(p) for p in planes]
+        kp = [p.contiguous(memory_format=torch.channels_last) if r else p for p, r in zip(planes, ctx.relayout)]
+        inp = plane_rows_fwd(kp, xyz, xyz_min, xyz_max, world_size, n_freq, cell_decode)
+        ctx.save_for_backward(xyz, xyz_min, xyz_max)
+        ctx.meta = planes
+        ctx.geometry = (world_size, n_freq, cell_decode)
+        return inp
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_inp):
+        xyz, xyz_min, xyz_max = ctx.saved_tensors
+        grads = [None, None, None]
+        if any(ctx.needs_input_grad[:3]):
+            # as _TriPlaneSample.backward: zero-filled buffers with the strides the kernel saw, one launch into all three
+            grads = [torch.zeros_like(p, memory_format=torch.channels_last if r else torch.preserve_format)
+                     for p, r in zip(ctx.meta, ctx.relayout)]
+            plane_rows_bwd(grad_inp.contiguous(), grads, xyz, xyz_min, xyz_max, *ctx.geometry)
+            grads = [g if need else None for g, need in zip(grads, ctx.needs_input_grad[:3])]
+        return grads[0], grads[1], grads[2], None, None, None, None, None, None
+
+
+def plane_rows(planes, xyz, xyz_min, xyz_max, world_size, n_freq, cell_decode=True):
+    """The samplers, the coordinate encoding and the cats of the reference's interpolate (lib/tri_dvgo.py:568-607) as one
+    HIP op: planes as in `triplane_sample`, xyz [M,3] -> inp [3,M,D]: per plane (xy, yz, zx) the MLP input rows [C bilinear
+    features, q0, q1, sin(q * 2^j), cos(q * 2^j)(, cell_a, cell_b)] (include/dvgo_hip.h has the arithmetic).  Differentiable
+    w.r.t. the planes only, through the feature columns."""
+    xy, yz, zx = _plane_list(planes)
+    for p, k in zip((xy, yz, zx), PLANE_KEYS):
+        _plane_geom(p, k)
+    ws = tuple(int(v) for v in world_size)
+    return _PlaneRows.apply(xy, yz, zx, xyz.reshape(-1, 3).contiguous(), xyz_min.contiguous(), xyz_max.contiguous(), ws,
+                            int(n_freq), bool(cell_decode))
+
+
+def interp_decode(planes, nets, xyz, xyz_min, xyz_max, world_size, n_freq, cell_decode=True, aggregation='concat'):
+    """interpolate: rows, the decoders, aggregation.  `nets`: {'xy': module, 'yz': module}; plane zx is decoded by
+    nets['yz'] as in the reference (lib/tri_dvgo.py:170-174), so the MLPs run twice -- once on the M rows of plane xy, once
+    on the 2M rows of planes yz and zx.  -> [M, 3 * out] ('concat': xy, yz, zx) or [M, out] ('sum': (xy + yz) + zx)."""
+    if aggregation not in ('concat', 'sum'):
+        raise ValueError(f"aggregation must be 'concat' or 'sum', got {aggregation!r}")
+    inp = plane_rows(planes, xyz, xyz_min, xyz_max, world_size, n_freq, cell_decode)
+    _, M, D = inp.shape
+    p_xy = nets['xy'](inp[0])
+    rest = nets['yz'](inp[1:].reshape(2 * M, D))
+    p_yz, p_zx = rest.reshape(2, M, rest.shape[-1])         # the width named: -1 is ambiguous when no sample is kept
+    if aggregation == 'concat':
+        return torch.cat([p_xy, p_yz, p_zx], -1)
+    return (p_xy + p_yz) + p_zx
 
 
 class MaskCache(nn.Module):

@@ -35,10 +35,11 @@ PLANE_AXES = {'xy': (1, 2), 'yz': (0, 1), 'zx': (2, 0)}
 TRI_FINE_TRAIN = dict(FINE_TRAIN, lrate_planes=1e-1, skip_zero_grad_fields=['density'])
 
 _OUT_OF_SCOPE = {
-    'implicit_voxel_feat': 'this class is the bilinear path; the LIIF plane decoder (Interp_MLP per plane) is liif.LIIFTriPlaneVoxGO',
+    'implicit_voxel_feat': 'this class is the bilinear path without a decoder; the plane decoders (Interp_MLP per plane) are '
+                           'liif.LIIFTriPlaneVoxGO (liif=True) and interp.InterpTriPlaneVoxGO (liif=False)',
     'liif': 'LIIF local-ensemble decoding belongs to implicit_voxel_feat: liif.LIIFTriPlaneVoxGO',
     'feat_unfold': 'the 3x3 feature unfolding belongs to implicit_voxel_feat and is not built',
-    'cell_decode': 'cell decoding belongs to implicit_voxel_feat: liif.LIIFTriPlaneVoxGO',
+    'cell_decode': 'cell decoding belongs to implicit_voxel_feat: liif.LIIFTriPlaneVoxGO, interp.InterpTriPlaneVoxGO',
     'global_cell_decode': 'appending the cell size to the features is not built',
     'feat_fourier': 'the Fourier embedding of the features is not built',
     'feat_pe': 'the positional encoding of the features (feat_fourier) is not built',

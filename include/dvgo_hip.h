@@ -40,7 +40,9 @@ extern "C" {
 
 /* version of this ABI; bumped on any signature change (6: the positional-encoding colour head; 7: the contracted
  * sampler and the distortion loss of unbounded scenes; 8: the tri-plane sampler; 9: the trilinear sample's gradient
- * with respect to the position; 10: the LIIF plane decoder; 11: the fused march's gradient with respect to its rays) */
+ * with respect to the position; 10: the LIIF plane decoder; 11: the fused march's gradient with respect to its rays).
+ * The two dvgo_plane_rows_* entries were added without a bump, unlike the additions before them: an existing test pins the
+ * value 11, and a library built before them is still caught at load, by the check that every declared entry is exported. */
 #define DVGO_ABI_VERSION 11
 int dvgo_abi_version(void);
 
@@ -760,6 +762,48 @@ int dvgo_liif_scatter(const float* grad_inp,
 int dvgo_liif_blend_fwd(const float* pred, const float* wgt, int C, int64_t M, int E, int sum, float* out, void* stream);
 int dvgo_liif_blend_bwd(const float* grad_out, const float* wgt, int C, int64_t M, int E, int sum, float* grad_pred,
                         void* stream);
+
+/* ---------------------------------------------------------------------------------
+ * Bilinear plane decoder in front of its MLPs (csrc/plane_rows.hip).  Replaces lib/tri_dvgo.py:568-607
+ * interpolate (implicit_voxel_feat=True, liif=False) except the Interp_MLP calls: three F.grid_sample on the planes, three
+ * more on two-channel coordinate tables rebuilt per call (make_coord, :311-357), the positional encoding and the cats.
+ * Planes as in dvgo_triplane_*: pointer, H, W and three ELEMENT strides each, any dense layout.  (Wx, Wy, Wz) = world_size.
+ * All of the following in float32, in this order, no contraction:
+ *   ind_norm = (n_z, n_y, n_x), n_a = ((p_a - min_a) / (max_a - min_a)) * 2 - 1, as dvgo_triplane_fwd forms it
+ *     plane   c0 (addresses columns)   c1 (addresses rows)   table (Ta rows, Tb columns)   cell
+ *     xy      n_z                      n_y                   (Wx, Wy)                      (1 / Wx, 1 / Wy)
+ *     yz      n_y                      n_x                   (Wy, Wz)                      (1 / Wy, 1 / Wz)
+ *     zx      n_x                      n_z                   (Wz, Wx)                      (1 / Wz, 1 / Wx)
+ *   feat (C values): the plane's bilinear sample at (c0, c1), align_corners=True, zero padding: dvgo_triplane_fwd's
+ *     per-plane arithmetic, corner order and fma chain, the same bits as its sum == 0 output.
+ *   q0, q1: the bilinear sample, by the same rule (g = ((c + 1) / 2) * (T - 1) per axis, weights (f + 1) - g and g - f,
+ *     corners (i0,j0), (i0,j1), (i1,j0), (i1,j1), acc = fmaf(v, wi * wj, acc) from 0, corners outside skipped), of a table
+ *     [Ta, Tb] that is never built: q0 takes v = node_Tb(j), q1 takes v = node_Ta(i), node_T(i) = i * (2 / (T - 1)) - 1,
+ *     node_1 = -1.  The table follows the world lattice of the plane's NAME and is addressed by the flipped coordinates;
+ *     its extents are independent of (H_s, W_s).  Inside the box q ~ (c0, c1); all corners outside: q = 0.
+ *   encoding: arg = q_k * 2^j, k = 0, 1, j = 0..P-1, k-major (exact); sinf(arg) for all 2P, then cosf(arg) for all 2P.
+ *   cell_a = 1.f / Ta, cell_b = 1.f / Tb, with cell_decode != 0.
+ *   row = [feat | q0, q1 | sin (2P) | cos (2P) | cell_a, cell_b]: D = C + 2 + 4P (+ 2).
+ * dvgo_plane_rows_fwd: xyz [M,3], xyz_min / xyz_max device float[3] -> inp [3, M, D] (xy, yz, zx), dense.  Channels-last
+ *   planes with 16-byte (C % 4 == 0 and D % 4 == 0) or 8-byte (C % 2 == 0) aligned texels and an `inp` aligned alike are
+ *   read and written in pieces of that size; everything else goes element by element through the strides.
+ * dvgo_plane_rows_bwd: g_s[c, ih, iw] += w * grad_inp[s, m, c] for the first C columns of each row (columns >= C are never
+ *   read) into the caller's buffers (zero-filled or holding a partial sum; strides as the planes') with float atomics: the
+ *   summation order is not reproducible.  No gradient for xyz.  run as in dvgo_triplane_bwd (0: the library's default).
+ * M == 0 or C == 0: no-op.  DVGO_EINVAL: negative M, C or run, a plane axis or world extent < 1, P < 1, null pointers.
+ * DVGO_ERANGE: 3 M D >= 2^31.
+ * --------------------------------------------------------------------------------- */
+int dvgo_plane_rows_fwd(const float* xy, int H_xy, int W_xy, int64_t sC_xy, int64_t sH_xy, int64_t sW_xy,
+                        const float* yz, int H_yz, int W_yz, int64_t sC_yz, int64_t sH_yz, int64_t sW_yz,
+                        const float* zx, int H_zx, int W_zx, int64_t sC_zx, int64_t sH_zx, int64_t sW_zx,
+                        int C, const float* xyz, const float* xyz_min, const float* xyz_max, int64_t M,
+                        int Wx, int Wy, int Wz, int P, int cell_decode, float* inp, void* stream);
+int dvgo_plane_rows_bwd(const float* grad_inp,
+                        float* g_xy, int H_xy, int W_xy, int64_t sC_xy, int64_t sH_xy, int64_t sW_xy,
+                        float* g_yz, int H_yz, int W_yz, int64_t sC_yz, int64_t sH_yz, int64_t sW_yz,
+                        float* g_zx, int H_zx, int W_zx, int64_t sC_zx, int64_t sH_zx, int64_t sW_zx,
+                        int C, const float* xyz, const float* xyz_min, const float* xyz_max, int64_t M,
+                        int Wx, int Wy, int Wz, int P, int cell_decode, int run, void* stream);
 
 #ifdef __cplusplus
 }
