@@ -12,6 +12,8 @@ saved-tensor conventions) on top of the HIP kernels:
   liif_decode                 the Interp_MLPs between them stay torch modules)
   plane_rows, interp_decode   lib/tri_dvgo.py:568-607 (interpolate, liif=False: bilinear features, sampled coordinates and their
                               encoding as one MLP input row per plane, + backward; the Interp_MLPs stay torch modules)
+  vm_sample                   TensoRF's vector-matrix features (no counterpart in the reference): per component a plane's
+                              bilinear value times a line's linear value, + backward into planes and lines
   segment_coo                 torch_scatter.segment_coo(src, index, out, reduce='sum')
   total_variation_add_grad    lib/cuda/total_variation.cpp:16-24
 """
@@ -246,6 +248,108 @@ def triplane_sample(planes, xyz, xyz_min, xyz_max, aggregation='concat'):
     shape = xyz.shape[:-1]
     flat = xyz.reshape(-1, 3).contiguous()
     out = _TriPlaneSample.apply(xy, yz, zx, flat, xyz_min.contiguous(), xyz_max.contiguous(), aggregation)
+    return out.reshape(*shape, out.shape[-1])
+
+
+# ---------------------------------------------------------------------------------------------- VM decomposition
+def _line_geom(line, name):
+    """line [1,R,N,1] (any dense strides) -> (N, sC, sN) in elements."""
+    if line.dim() != 4 or line.shape[0] != 1 or line.shape[3] != 1:
+        raise RuntimeError(f'{name} must be [1,R,N,1]')
+    if not line.is_cuda:
+        raise RuntimeError(f'{name} must be a CUDA tensor')
+    check_f32(line, name)
+    return line.shape[2], line.stride(1), line.stride(2)
+
+
+def _vm_args(planes, lines, xyz):
+    """-> (planes, lines, the 27 geometry scalars interleaved with their tensors in call order, R, M)"""
+    planes, lines = _plane_list(planes), _plane_list(lines)
+    R = planes[0].shape[1]
+    if any(t.dim() != 4 or t.shape[1] != R for t in planes + lines):
+        raise RuntimeError('the three planes [1,R,H,W] and the three lines [1,R,N,1] must share their component count')
+    geom = []
+    for p, k in zip(planes, PLANE_KEYS):
+        geom += [p, *_plane_geom(p, k)]
+    for ln, k in zip(lines, PLANE_KEYS):
+        geom += [ln, *_line_geom(ln, k + '_line')]
+    check_input(xyz, 'xyz'); check_f32(xyz, 'xyz')
+    if xyz.dim() != 2 or xyz.shape[1] != 3:
+        raise RuntimeError('xyz must be [M,3]')
+    return planes, lines, geom, R, xyz.shape[0]
+
+
+def vm_fwd(planes, lines, xyz, xyz_min, xyz_max):
+    """dvgo_vm_fwd on the strides as they are: planes [1,R,H,W], lines [1,R,N,1], xyz [M,3] -> [M,3R], plane value times
+    line value per component (xy, yz, zx; include/dvgo_hip.h has the arithmetic).  No autograd."""
+    planes, lines, geom, R, M = _vm_args(planes, lines, xyz)
+    out = torch.empty((M, 3 * R), dtype=torch.float32, device=xyz.device)
+    with L.device_of(xyz):
+        L.call('dvgo_vm_fwd', *geom, R, xyz, xyz_min, xyz_max, M, out, stream_of(xyz))
+    return out
+
+
+def vm_bwd(grad_out, planes, lines, grad_planes, grad_lines, xyz, xyz_min, xyz_max, run=0, mode=0):
+    """dvgo_vm_bwd: accumulates into the six buffers `grad_planes` / `grad_lines` (shaped and strided like the planes and
+    lines they belong to) in place.  `run`: samples a lane merges before its atomics; `mode`: 1 all sums to global memory,
+    2 the line sums through a table in LDS (0: the library's choice, for both)."""
+    planes, lines, geom, R, M = _vm_args(planes, lines, xyz)
+    grad_planes, grad_lines = _plane_list(grad_planes), _plane_list(grad_lines)
+    for t, g in zip(planes + lines, grad_planes + grad_lines):
+        if g.shape != t.shape or g.dtype != torch.float32 or g.device != t.device or \
+                any(a != b for a, b, n in zip(g.stride(), t.stride(), t.shape) if n > 1):
+            raise RuntimeError('a gradient buffer must have the shape, strides, dtype and device of the tensor it belongs to')
+    check_input(grad_out, 'grad_out'); check_f32(grad_out, 'grad_out')
+    if tuple(grad_out.shape) != (M, 3 * R):
+        raise RuntimeError('grad_out has the wrong shape')
+    with L.device_of(xyz):
+        L.call('dvgo_vm_bwd', grad_out, *geom, *grad_planes, *grad_lines, R, xyz, xyz_min, xyz_max, M, int(run), int(mode),
+               stream_of(xyz))
+    return grad_planes, grad_lines
+
+
+class _VMSample(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, xyz, xyz_min, xyz_max, *tensors):
+        M = xyz.shape[0]
+        relayout = TRIPLANE_RELAYOUT and M >= max(p.shape[2] * p.shape[3] for p in tensors[:3])
+        ctx.relayout = [relayout and not _is_channels_last(t) for t in tensors]
+        kt = [t.contiguous(memory_format=torch.channels_last) if r else t for t, r in zip(tensors, ctx.relayout)]
+        out = vm_fwd(kt[:3], kt[3:], xyz, xyz_min, xyz_max)
+        ctx.save_for_backward(xyz, xyz_min, xyz_max, *kt)          # the gradient of a product reads the other factor
+        ctx.meta = tensors
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        xyz, xyz_min, xyz_max, *kt = ctx.saved_tensors
+        grads = [None] * 6
+        if any(ctx.needs_input_grad[3:]):
+            # as _TriPlaneSample.backward: zero-filled buffers with the strides the kernel saw, one launch into all six
+            grads = [torch.zeros_like(t, memory_format=torch.channels_last if r else torch.preserve_format)
+                     for t, r in zip(ctx.meta, ctx.relayout)]
+            vm_bwd(grad_out.contiguous(), kt[:3], kt[3:], grads[:3], grads[3:], xyz, xyz_min, xyz_max)
+            grads = [g if need else None for g, need in zip(grads, ctx.needs_input_grad[3:])]
+        return (None, None, None, *grads)
+
+
+def vm_sample(planes, lines, xyz, xyz_min, xyz_max):
+    """TensoRF's vector-matrix features as one HIP op: `planes` as in `triplane_sample`, each [1,R,H,W]; `lines` likewise a
+    dict with the keys 'xy', 'yz', 'zx' (or the three in that order), each [1,R,N,1], line s running along the world axis
+    plane s does not see (xy: x, yz: z, zx: y); xyz [...,3] world coordinates -> [...,3R]: per component the plane's
+    bilinear value times the line's linear value, in the order xy, yz, zx.  Differentiable w.r.t. planes and lines only."""
+    tensors = _plane_list(planes) + _plane_list(lines)
+    for ln, k in zip(tensors[3:], PLANE_KEYS):             # shapes before devices
+        if ln.dim() != 4 or ln.shape[0] != 1 or ln.shape[3] != 1:
+            raise RuntimeError(f'{k}_line must be [1,R,N,1]')
+    for p, k in zip(tensors[:3], PLANE_KEYS):
+        _plane_geom(p, k)
+    for ln, k in zip(tensors[3:], PLANE_KEYS):
+        _line_geom(ln, k + '_line')
+    shape = xyz.shape[:-1]
+    flat = xyz.reshape(-1, 3).contiguous()
+    out = _VMSample.apply(flat, xyz_min.contiguous(), xyz_max.contiguous(), *tensors)
     return out.reshape(*shape, out.shape[-1])
 
 

@@ -100,7 +100,7 @@ class TriPlaneVoxGO(DirectVoxGO):
             'rgbnet_width': rgbnet_width, 'viewbase_pe': viewbase_pe,
         }
         # lib/tri_dvgo.py:200-223: the feature width, and what of it the MLP reads before the view embedding
-        self.feat_dim = 3 * self.rgbnet_dim if tri_aggregation == 'concat' else self.rgbnet_dim
+        self.feat_dim = self._feature_width()
         if not self.rgbnet_direct and self.feat_dim < 3:
             raise ValueError('rgbnet_direct=False takes the first three feature channels as diffuse colour: needs at least 3')
         self._init_head(self.feat_dim if self.rgbnet_direct else self.feat_dim - 3, viewbase_pe, rgbnet_width, rgbnet_depth)
@@ -111,6 +111,10 @@ class TriPlaneVoxGO(DirectVoxGO):
     def _init_head(self, mlp_feat_dim, viewbase_pe, rgbnet_width, rgbnet_depth):
         self.register_buffer('viewfreq', _freqs(viewbase_pe))
         self.rgbnet = make_rgbnet(mlp_feat_dim + (3 + 3 * viewbase_pe * 2), rgbnet_width, rgbnet_depth)
+
+    def _feature_width(self):
+        """What `sample_planes` emits per sample (a subclass with another feature pipeline says its own)."""
+        return 3 * self.rgbnet_dim if self.tri_aggregation == 'concat' else self.rgbnet_dim
 
     def _plane_hw(self, key):
         """(H, W) of plane `key`: `plane_size`, else the two world_size extents its rows and columns follow."""

@@ -1,0 +1,95 @@
+"""VMTriPlaneVoxGO: the tri-plane model with TensoRF's vector-matrix (VM) decomposed colour features (Chen et al., ECCV
+2022, arXiv:2203.09517), on the MI355X kernels.
+
+The additive tri-plane of TriPlaneVoxGO can only express a sum of three 2-D functions.  Here every one of the `n_comp`
+components of a plane is multiplied by a 1-D line along the world axis that plane does not see (xy: x, yz: z, zx: y), and
+the 3 * n_comp products are mixed by a basis matrix into the `rgbnet_dim` features the colour head reads:
+
+    features = vm_sample(planes, lines, pts) @ basis            [M, 3 n_comp] @ [3 n_comp, rgbnet_dim]
+
+The sampler and its gradient are one HIP op (ops.vm_sample, csrc/vm.hip; include/dvgo_hip.h states the arithmetic); the
+matmul is torch's.  Density stays the dense 3-D grid on the fused march, as in the base.  No equality with any other
+implementation is claimed: the contract is INTEGRATION.md section 6d, held by tests/vm_oracle.py.
+
+Everything the base leaves out stays out: extract_mesh, data-parallel training, pose refinement, the plane decoders'
+options and the encoder's keys.  Not built either: a VM-decomposed density, L1 / total-variation regularisers on planes and
+lines, the basis matmul fused into the sampler.
+"""
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+
+from .ops import PLANE_KEYS, vm_sample
+from .triplane import TRI_FINE_TRAIN, TriPlaneVoxGO
+
+# which world axis the line of each plane follows: the one the plane's rows and columns do not
+LINE_AXIS = {'xy': 0, 'yz': 2, 'zx': 1}
+
+# TRI_FINE_TRAIN with TensoRF's published rates: 2e-2 for the grids (planes and lines), 1e-3 for the networks (the basis).
+# They are the paper's numbers and have not been tuned on this model.
+VM_FINE_TRAIN = dict(TRI_FINE_TRAIN, lrate_planes=2e-2, lrate_lines=2e-2, lrate_basis=1e-3)
+
+
+class VMTriPlaneVoxGO(TriPlaneVoxGO):
+    """TriPlaneVoxGO whose colour features are `vm_sample(planes, lines, pts) @ basis`.  Takes the base's arguments plus
+    `n_comp` (components per plane, R) and `line_size` (an int: the length of all three lines; None: each line takes the
+    `world_size` extent of its axis and is resized with the grid).  `rgbnet_dim` is the feature width the head sees.
+    `tri_aggregation` is not an option: the products are concatenated in front of the basis."""
+
+    def __init__(self, xyz_min, xyz_max, n_comp=16, line_size=None, **kwargs):
+        if kwargs.pop('tri_aggregation', 'concat') != 'concat':
+            raise ValueError("tri_aggregation is not an option of VMTriPlaneVoxGO: the 3 * n_comp products are concatenated "
+                             "and mixed by `basis`")
+        if int(n_comp) < 1:
+            raise ValueError(f'n_comp must be at least 1, got {n_comp}')
+        if line_size is not None and int(line_size) < 1:
+            raise ValueError(f'line_size must be at least 1, got {line_size}')
+        object.__setattr__(self, 'n_comp', int(n_comp))          # read by _alloc_plane, which the base constructor calls
+        super().__init__(xyz_min, xyz_max, **kwargs)
+        self.line_size = None if line_size is None else int(line_size)
+        self.lines = nn.ParameterDict({k: nn.Parameter(self._alloc_line(self._line_n(k))) for k in PLANE_KEYS})
+        self.basis = nn.Parameter(nn.Linear(3 * self.n_comp, self.rgbnet_dim, bias=False).weight.detach().t().contiguous())
+
+    # ------------------------------------------------------------------ construction
+    def _feature_width(self):
+        return self.rgbnet_dim               # what `basis` emits
+
+    def _alloc_plane(self, hw, device=None):
+        # a product of two zero tensors has a zero gradient for ever: TensoRF's 0.1 * randn, from torch's global generator
+        p = 0.1 * torch.randn([1, self.n_comp, *hw], device=device)
+        return p.contiguous(memory_format=torch.channels_last) if self.channels_last else p
+
+    def _line_n(self, key):
+        """The length of line `key`: `line_size`, else the world_size extent of the axis it follows."""
+        return self.line_size if self.line_size is not None else int(self.world_size[LINE_AXIS[key]])
+
+    def _alloc_line(self, n, device=None):
+        ln = 0.1 * torch.randn([1, self.n_comp, n, 1], device=device)
+        return ln.contiguous(memory_format=torch.channels_last) if self.channels_last else ln
+
+    def get_kwargs(self):
+        kw = super().get_kwargs()
+        del kw['tri_aggregation']
+        kw.update(n_comp=self.n_comp, line_size=self.line_size)
+        return kw
+
+    # ------------------------------------------------------------------ grid maintenance
+    @torch.no_grad()
+    def scale_volume_grid(self, num_voxels):
+        """The base's (density, occupancy, planes), plus the lines: resized with the grid, bilinear with
+        align_corners=True on [1, R, N, 1], when they take their lengths from world_size; left alone under `line_size`."""
+        super().scale_volume_grid(num_voxels)
+        if self.line_size is None:
+            for k in PLANE_KEYS:
+                ln = F.interpolate(self.lines[k].data.contiguous(), size=(self._line_n(k), 1), mode='bilinear', align_corners=True)
+                if self.channels_last:
+                    ln = ln.contiguous(memory_format=torch.channels_last)
+                self.lines[k] = nn.Parameter(ln)
+
+    # ------------------------------------------------------------------ features
+    def sample_planes(self, pts, feats=None):
+        """[M, rgbnet_dim].  `feats`: the planes under 'xy', 'yz', 'zx' and, optionally, lines under 'xy_line', 'yz_line',
+        'zx_line'; a missing line key means the model's own line.  The basis is always the model's."""
+        planes = self.planes if feats is None else feats
+        lines = {k: planes[k + '_line'] if k + '_line' in planes else self.lines[k] for k in PLANE_KEYS}
+        return vm_sample(planes, lines, pts, self.xyz_min, self.xyz_max) @ self.basis

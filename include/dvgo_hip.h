@@ -41,8 +41,8 @@ extern "C" {
 /* version of this ABI; bumped on any signature change (6: the positional-encoding colour head; 7: the contracted
  * sampler and the distortion loss of unbounded scenes; 8: the tri-plane sampler; 9: the trilinear sample's gradient
  * with respect to the position; 10: the LIIF plane decoder; 11: the fused march's gradient with respect to its rays).
- * The two dvgo_plane_rows_* entries were added without a bump, unlike the additions before them: an existing test pins the
- * value 11, and a library built before them is still caught at load, by the check that every declared entry is exported. */
+ * The two dvgo_plane_rows_* and the two dvgo_vm_* entries were added without a bump, unlike the additions before them: an
+ * existing test pins the value 11, and a library built before them is still caught at load, by the check that every declared entry is exported. */
 #define DVGO_ABI_VERSION 11
 int dvgo_abi_version(void);
 
@@ -804,6 +804,59 @@ int dvgo_plane_rows_bwd(const float* grad_inp,
                         float* g_zx, int H_zx, int W_zx, int64_t sC_zx, int64_t sH_zx, int64_t sW_zx,
                         int C, const float* xyz, const float* xyz_min, const float* xyz_max, int64_t M,
                         int Wx, int Wy, int Wz, int P, int cell_decode, int run, void* stream);
+
+/* ---------------------------------------------------------------------------------
+ * Vector-matrix (VM) decomposed features (csrc/vm.hip).  TensoRF's VM
+ * decomposition (Chen et al., ECCV 2022): every plane component is multiplied by a 1-D line along the world axis its plane
+ * does not see.  No counterpart in the reference; the contract is this text.
+ * Planes xy, yz, zx as in dvgo_triplane_*: fp32 [1, R, H_s, W_s], pointer, H, W and three ELEMENT strides each.  Lines
+ * l_xy, l_yz, l_zx: fp32 [1, R, N_s, 1], pointer, N and two ELEMENT strides each (lC: component, lN: node).  Any dense layout;
+ * every size is independent of the others; a size of 1 on any axis is legal.
+ *     plane   rows (H) follow world axis   columns (W) follow world axis   line follows world axis
+ *     xy      y (1)                        z (2)                           x (0)
+ *     yz      x (0)                        y (1)                           z (2)
+ *     zx      z (2)                        x (0)                           y (1)
+ * All in float32, no contraction:
+ *   p: the plane's bilinear value, dvgo_triplane_fwd's per-plane arithmetic, corner order and fma chain: the same bits as
+ *     its sum == 0 output for that plane and component.
+ *   l: g = ((((x_a - min_a) / (max_a - min_a)) * 2 - 1) + 1) / 2 * (N_s - 1), f = floor(g), w0 = (f + 1) - g, w1 = g - f,
+ *     l = 0; l = fmaf(v[f], w0, l) if 0 <= f < N_s; l = fmaf(v[f + 1], w1, l) if 0 <= f + 1 < N_s.
+ *   out[m, s * R + r] = p * l (one multiply), s in the order xy, yz, zx, r fastest: [M, 3R].
+ * dvgo_vm_fwd: xyz [M,3] world coordinates, xyz_min / xyz_max device float[3] -> out [M, 3R].  Bitwise repeatable.
+ *   R % 4 == 0 with channels-last (component stride 1), 16-byte aligned planes, lines and out: 16-byte loads and stores;
+ *   everything else goes element by element through the strides.
+ * dvgo_vm_bwd: the values of planes and lines, grad_out [M, 3R], and six gradient buffers g_s / gl_s (zero-filled or holding
+ *   a partial sum) with the shape and strides of the tensor each belongs to:
+ *     g_s[r, ih, iw] += k_corner * (l * grad_out[m, s * R + r])       k_corner = wh * ww
+ *     gl_s[r, n]     += w_node   * (p * grad_out[m, s * R + r])
+ *   with float atomics: the summation order is not reproducible.  No gradient for xyz.
+ *   run: consecutive samples one lane sums in registers while they stay in one texel cell (for the planes) and in one
+ *     line interval (for the lines), before its atomics (1: none; 0: the library's default).
+ *   mode 1: every sum goes to global memory; handles every shape.  mode 2: the node sums go through a table [3][N_s][R]
+ *     of float adds in LDS, added to gl_s once per workgroup with r fastest, zeros skipped; legal while the table
+ *     (N_xy + N_yz + N_zx) * R * 4 bytes is at most 64 KB.  mode 0: the library's choice, mode 2 where it is legal and
+ *     mode 1 elsewhere; its default run is 8 (both measured: profiles/vm/README.md).
+ * M == 0 or R == 0: no-op, no pointer is looked at.  DVGO_EINVAL: negative M, R or run, a plane axis or line length < 1,
+ * a mode outside 0..2, null pointers, an explicit mode 2 whose table exceeds 64 KB.  DVGO_ERANGE: M * 3R >= 2^31.  All of
+ * it is answered before any launch.
+ * --------------------------------------------------------------------------------- */
+int dvgo_vm_fwd(const float* xy, int H_xy, int W_xy, int64_t sC_xy, int64_t sH_xy, int64_t sW_xy,
+                const float* yz, int H_yz, int W_yz, int64_t sC_yz, int64_t sH_yz, int64_t sW_yz,
+                const float* zx, int H_zx, int W_zx, int64_t sC_zx, int64_t sH_zx, int64_t sW_zx,
+                const float* l_xy, int N_xy, int64_t lC_xy, int64_t lN_xy,
+                const float* l_yz, int N_yz, int64_t lC_yz, int64_t lN_yz,
+                const float* l_zx, int N_zx, int64_t lC_zx, int64_t lN_zx,
+                int R, const float* xyz, const float* xyz_min, const float* xyz_max, int64_t M, float* out, void* stream);
+int dvgo_vm_bwd(const float* grad_out,
+                const float* xy, int H_xy, int W_xy, int64_t sC_xy, int64_t sH_xy, int64_t sW_xy,
+                const float* yz, int H_yz, int W_yz, int64_t sC_yz, int64_t sH_yz, int64_t sW_yz,
+                const float* zx, int H_zx, int W_zx, int64_t sC_zx, int64_t sH_zx, int64_t sW_zx,
+                const float* l_xy, int N_xy, int64_t lC_xy, int64_t lN_xy,
+                const float* l_yz, int N_yz, int64_t lC_yz, int64_t lN_yz,
+                const float* l_zx, int N_zx, int64_t lC_zx, int64_t lN_zx,
+                float* g_xy, float* g_yz, float* g_zx, float* gl_xy, float* gl_yz, float* gl_zx,
+                int R, const float* xyz, const float* xyz_min, const float* xyz_max, int64_t M, int run, int mode,
+                void* stream);
 
 #ifdef __cplusplus
 }
