@@ -6,6 +6,8 @@
     density -= 1                                                                      run.py:334-345
   * batch draw from a permutation stream of the training rays                        run.py:348-353
   * TrainStep (forward, loss, backward, DP reduction, TV, MaskedAdam, lr decay)       run.py:372-406
+    (TV: weight_tv_density / weight_tv_k0, and on the tri-plane models the optional keys weight_tv_planes /
+    weight_tv_lines / weight_l1_lines, train.PLANE_REG_KEYS)
 
 No CLI, config files, logging to disk or dataset I/O: those are out of scope.
 """

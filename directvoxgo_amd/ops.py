@@ -16,7 +16,11 @@ saved-tensor conventions) on top of the HIP kernels:
                               bilinear value times a line's linear value, + backward into planes and lines
   segment_coo                 torch_scatter.segment_coo(src, index, out, reduce='sum')
   total_variation_add_grad    lib/cuda/total_variation.cpp:16-24
+  plane_reg_add_grad          total variation and L1 of the tri-plane models' planes and lines added to their gradients, one
+                              launch for all of them (no counterpart in the reference)
 """
+import ctypes
+
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -720,3 +724,31 @@ def total_variation_add_grad(param, grad, wx, wy, wz, dense_mode, x_range=None):
         L.call('dvgo_total_variation_add_grad_slab', ptr(param), ptr(grad), _flt(float(wx)), _flt(float(wy)),
                _flt(float(wz)), _i64(C), _i64(X), _i64(Y), _i64(Z), _i64(sC), _i64(sX), _i64(sY), _i64(sZ),
                _int(1 if dense_mode else 0), _i64(lo), _i64(hi), stream_of(param))
+
+
+def plane_reg_add_grad(params, grads, weights, dense_mode):
+    """Total-variation and L1 regularisers of plane-shaped parameters added to their gradients, in place on ``grads``, in
+    ONE launch for the whole list (csrc/plane_tv.hip; include/dvgo_hip.h states the arithmetic).  ``params`` / ``grads``:
+    up to 8 float32 tensors [1,C,H,W] (a line is [1,R,N,1]), each gradient sharing its parameter's (dense) strides;
+    ``weights``: per tensor (wh, ww, wl1), already normalised -- the kernel divides nothing.  No autograd."""
+    n = len(params)
+    if len(grads) != n or len(weights) != n:
+        raise ValueError(f'plane_reg_add_grad: {n} params, {len(grads)} grads, {len(weights)} weights')
+    if n == 0:
+        return
+    for p, g in zip(params, grads):
+        if not (p.is_cuda and g.is_cuda):
+            raise RuntimeError('param must be a CUDA tensor')
+        check_f32(p, 'param')
+        check_f32(g, 'grad')
+        if p.dim() != 4 or p.shape[0] != 1 or g.shape != p.shape:
+            raise RuntimeError('param and grad must be [1,C,H,W]')
+        if p.stride() != g.stride():
+            raise RuntimeError('param and grad must share strides')
+    table = lambda ts: (ctypes.c_void_p * n)(*[t.data_ptr() for t in ts])          # noqa: E731  (formed in the call below)
+    with L.device_of(params[0]):
+        L.call('dvgo_plane_reg_add_grad', table(params), table(grads),
+               (ctypes.c_int64 * (3 * n))(*[s for p in params for s in p.shape[1:]]),
+               (ctypes.c_int64 * (3 * n))(*[s for p in params for s in p.stride()[1:]]),
+               (ctypes.c_float * (3 * n))(*[float(w) for ws in weights for w in ws]),
+               n, 1 if dense_mode else 0, stream_of(params[0]))

@@ -38,6 +38,12 @@ FINE_TRAIN = dict(COARSE_TRAIN, N_iters=20000, pervoxel_lr=False, weight_entropy
                   pg_scale=[1000, 2000, 3000, 4000], skip_zero_grad_fields=['density', 'k0'])   # :59-68
 
 
+# optional config keys: total variation on the planes, total variation and L1 on the lines of the tri-plane models
+# (model.plane_regularizers_add_grad); read with cfg.get(key, 0.0), inside the tv_after / tv_before / tv_every window,
+# divided by the global ray count like weight_tv_density / weight_tv_k0.  No config here sets them: no weight has been tuned
+PLANE_REG_KEYS = ('weight_tv_planes', 'weight_tv_lines', 'weight_l1_lines')
+
+
 def create_optimizer_or_freeze_model(model, cfg_train, global_step):
     """lib/utils.py:20-48: one param group per `lrate_<name>` whose attribute exists on the model."""
     decay_steps = cfg_train['lrate_decay'] * 1000
@@ -201,6 +207,17 @@ class TrainStep:
         self.contracted = isinstance(model, DirectContractedVoxGO)
         if self.contracted and self.world > 1:
             raise NotImplementedError('data-parallel training of DirectContractedVoxGO is not built: train it on one GPU')
+        # regularisers of plane-shaped parameters (the tri-plane models' planes and lines): optional keys, absent = 0
+        self.plane_reg = {k: float(cfg_train.get(k, 0.0)) for k in PLANE_REG_KEYS}
+        self.plane_reg_on = any(w > 0 for w in self.plane_reg.values())
+        if self.plane_reg_on:
+            on = [k for k, w in self.plane_reg.items() if w > 0]
+            if not hasattr(model, 'plane_regularizers_add_grad'):
+                raise ValueError(f'{", ".join(on)}: {type(model).__name__} has no planes to regularise (the keys belong to the '
+                                 'tri-plane models)')
+            if not hasattr(model, 'lines') and (self.plane_reg['weight_tv_lines'] > 0 or self.plane_reg['weight_l1_lines'] > 0):
+                raise ValueError(f'weight_tv_lines / weight_l1_lines: {type(model).__name__} has no lines (they belong to '
+                                 'VMTriPlaneVoxGO)')
         self.decay_factor = 0.1 ** (1 / (cfg_train['lrate_decay'] * 1000))
         # every collective of the step outside fused.brick_union; None on one GPU
         self.dp = None if self.world == 1 else GridReducer(
@@ -242,7 +259,7 @@ class TrainStep:
     def can_capture(self):
         cfg, model = self.cfg, self.model
         density, k0 = getattr(model, 'density', None), getattr(model, 'k0', None)
-        tv = (cfg['weight_tv_density'] > 0 or cfg['weight_tv_k0'] > 0) and cfg['tv_before'] > cfg['tv_after']
+        tv = self._tv_weighted() and cfg['tv_before'] > cfg['tv_after']
         return bool(self.dp is None and self.fused_loss and self.rows_adam and not tv and not self.k0_idle and not self.contracted
                     and isinstance(self.optimizer, MaskedAdam) and isinstance(density, nn.Parameter) and density.is_cuda
                     and hasattr(model, 'can_keep_count_on_device') and model.can_keep_count_on_device()
@@ -311,10 +328,13 @@ class TrainStep:
             return self._replay(rays_o, rays_d, viewdirs, target)
         return self._eager(rays_o, rays_d, viewdirs, target, global_step)
 
+    def _tv_weighted(self):
+        """Some regulariser of `_tv_add_grad` has a positive weight."""
+        return bool(self.cfg['weight_tv_density'] > 0 or self.cfg['weight_tv_k0'] > 0 or self.plane_reg_on)
+
     def _plan(self, rays_o, global_step):
         cfg, model, opt = self.cfg, self.model, self.optimizer
-        tv = (cfg['tv_after'] < global_step < cfg['tv_before'] and global_step % cfg['tv_every'] == 0 and
-              (cfg['weight_tv_density'] > 0 or cfg['weight_tv_k0'] > 0))
+        tv = cfg['tv_after'] < global_step < cfg['tv_before'] and global_step % cfg['tv_every'] == 0 and self._tv_weighted()
         density, k0 = getattr(model, 'density', None), getattr(model, 'k0', None)
         # may the march's brick scatter apply the grid update itself?  One GPU: from its own tiles.  Data parallel: from the
         # all-reduced tiles of the bricks any rank touched (fused.brick_union) while that union stays small.
@@ -412,3 +432,5 @@ class TrainStep:
             self.model.density_total_variation_add_grad(cfg['weight_tv_density'] / n_global, dense, **x_range)
         if cfg['weight_tv_k0'] > 0:
             self.model.k0_total_variation_add_grad(cfg['weight_tv_k0'] / n_global, dense, **x_range)
+        if self.plane_reg_on:                                    # planes and lines, one launch (one GPU: no slab)
+            self.model.plane_regularizers_add_grad(dense, **{k: w / n_global for k, w in self.plane_reg.items()})

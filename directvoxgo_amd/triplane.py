@@ -13,6 +13,10 @@ the pose anchors are not part of this model.  `render(feats, ...)` takes such pl
 into them; `forward(...)` renders the model's own planes, `self.planes` (an nn.ParameterDict, zero-initialised, trained
 through `lrate_planes`).  There is no k0, as in the reference.
 
+Regulariser: `plane_regularizers_add_grad` adds the total-variation gradient of the three planes to their `.grad` in one
+HIP launch (ops.plane_reg_add_grad, csrc/plane_tv.hip); TrainStep calls it for the config key `weight_tv_planes` inside the
+usual tv_after / tv_before / tv_every window.  No default weight is proposed: none has been tuned on this model.
+
 Two execution paths produce the same dict and call the same sampler on bit-equal positions:
   fused=True   fused_march(positions=True) -> triplane_sample -> colour head -> composite;
   fused=False  the reference's op sequence on the drop-in ops.
@@ -24,7 +28,7 @@ import torch.nn.functional as F
 
 from .dvgo import DirectVoxGO
 from .fused import composite, composite_depth, fused_march
-from .ops import PLANE_KEYS, Alphas2Weights, triplane_sample
+from .ops import PLANE_KEYS, Alphas2Weights, plane_reg_add_grad, triplane_sample
 from .train import FINE_TRAIN
 from .voxel_model import VoxelModel, _freqs, _result, make_rgbnet
 
@@ -154,6 +158,41 @@ class TriPlaneVoxGO(DirectVoxGO):
     def k0_total_variation_add_grad(self, weight, dense_mode, x_range=None):
         raise NotImplementedError('k0_total_variation_add_grad: the tri-plane model has no k0 (the reference method reads an '
                                   'attribute it never assigns, lib/tri_dvgo.py:446-449)')
+
+    def _plane_reg_items(self, weight_tv_planes, weight_tv_lines, weight_l1_lines):
+        """[(parameter, (wh, ww, wl1))] of the tensors with a non-zero weight.  The normalisation mirrors `_tv_weights`
+        (lib/dvgo.py:297-305) and the 3-D kernel's division by its neighbour count, 6: a plane has 4 neighbours, a line 2."""
+        if weight_tv_lines != 0 or weight_l1_lines != 0:
+            raise ValueError(f'weight_tv_lines / weight_l1_lines: {type(self).__name__} has no lines')
+        if weight_tv_planes == 0:
+            return []
+        items = []
+        for k in PLANE_KEYS:
+            p = self.planes[k]
+            w = weight_tv_planes * max(p.shape[2], p.shape[3]) / 128 / 4
+            items.append((p, (w, w, 0.0)))
+        return items
+
+    def plane_regularizers_add_grad(self, dense_mode, weight_tv_planes=0.0, weight_tv_lines=0.0, weight_l1_lines=0.0):
+        """Total variation on the model's own planes, added to their `.grad` in one launch (ops.plane_reg_add_grad;
+        INTEGRATION.md section 6e): wh = ww = weight_tv_planes * max(H, W) / 128 / 4 per plane.  `dense_mode` False: only
+        texels whose gradient is non-zero are touched, and a plane without a `.grad` is skipped; True: every texel, and a
+        missing `.grad` is created as zeros with the parameter's strides first.  This class has no lines: a non-zero
+        line weight is a ValueError.  Planes handed to `render(feats=...)` belong to the caller and are not touched."""
+        items = self._plane_reg_items(weight_tv_planes, weight_tv_lines, weight_l1_lines)
+        params, grads, weights = [], [], []
+        for p, w in items:
+            if not p.requires_grad:                 # frozen by a zero learning rate: nothing reads its gradient
+                continue
+            if p.grad is None:
+                if not dense_mode:
+                    continue
+                p.grad = torch.zeros_like(p, memory_format=torch.preserve_format)
+            elif p.grad.stride() != p.stride():     # the kernel walks raw memory: the gradient in the parameter's layout
+                p.grad = torch.empty_like(p, memory_format=torch.preserve_format).copy_(p.grad)
+            params.append(p.detach()); grads.append(p.grad); weights.append(w)
+        if params:
+            plane_reg_add_grad(params, grads, weights, dense_mode)
 
     def encode_feat(self, *args, **kwargs):
         raise NotImplementedError('encode_feat: the image encoder, its Mapping network and the pose anchors are not part of '

@@ -12,8 +12,13 @@ matmul is torch's.  Density stays the dense 3-D grid on the fused march, as in t
 implementation is claimed: the contract is INTEGRATION.md section 6d, held by tests/vm_oracle.py.
 
 Everything the base leaves out stays out: extract_mesh, data-parallel training, pose refinement, the plane decoders'
-options and the encoder's keys.  Not built either: a VM-decomposed density, L1 / total-variation regularisers on planes and
-lines, the basis matmul fused into the sampler.
+options and the encoder's keys.  Not built either: a VM-decomposed density, the basis matmul fused into the sampler.
+
+Regularisers (TensoRF trains its VM model with them): `plane_regularizers_add_grad` adds total variation on the planes,
+total variation on the lines and L1 on the lines to the six gradients in one HIP launch (ops.plane_reg_add_grad,
+csrc/plane_tv.hip).  TrainStep reads `weight_tv_planes`, `weight_tv_lines` and `weight_l1_lines`
+from the config (absent: 0, nothing runs) inside the usual tv_after / tv_before / tv_every window.  VM_FINE_TRAIN sets none
+of them: no weight has been tuned on this model.
 """
 import torch
 import torch.nn as nn
@@ -85,6 +90,18 @@ class VMTriPlaneVoxGO(TriPlaneVoxGO):
                 if self.channels_last:
                     ln = ln.contiguous(memory_format=torch.channels_last)
                 self.lines[k] = nn.Parameter(ln)
+
+    def _plane_reg_items(self, weight_tv_planes, weight_tv_lines, weight_l1_lines):
+        """What `plane_regularizers_add_grad` (the base's) hands to its single launch: the base's planes, then the three
+        lines with total variation along each (wh = weight_tv_lines * N / 128 / 2: a node has 2 neighbours) and L1
+        (wl1 = weight_l1_lines: weight * sgn(value), not scaled by resolution)."""
+        items = super()._plane_reg_items(weight_tv_planes, 0.0, 0.0)
+        if weight_tv_lines != 0 or weight_l1_lines != 0:
+            for k in PLANE_KEYS:
+                ln = self.lines[k]
+                w = weight_tv_lines * ln.shape[2] / 128 / 2
+                items.append((ln, (w, 0.0, weight_l1_lines)))
+        return items
 
     # ------------------------------------------------------------------ features
     def sample_planes(self, pts, feats=None):

@@ -858,6 +858,38 @@ int dvgo_vm_bwd(const float* grad_out,
                 int R, const float* xyz, const float* xyz_min, const float* xyz_max, int64_t M, int run, int mode,
                 void* stream);
 
+/* ---------------------------------------------------------------------------------
+ * Total-variation and L1 regularisers of plane-shaped parameters, added to their gradients (csrc/plane_tv.hip; DESIGN.md
+ * section 6k).  The 2-D counterpart of dvgo_total_variation_add_grad for the feature planes
+ * [1,C,H,W] and lines [1,R,N,1] of the tri-plane models: up to 8 tensors in ONE launch.
+ * HOST tables, one entry per tensor t < n_tensors (as dvgo_copy_multi / dvgo_adam_upd_multi):
+ *   params[t], grads[t]   device pointers of a parameter and of its gradient, which share the strides below
+ *   sizes[3t .. 3t+2]     C, H, W, each at least 1
+ *   strides[3t .. 3t+2]   sC, sH, sW in ELEMENTS: any dense layout (the models store channels-last: sC = 1, sW = C, sH = W C)
+ *   weights[3t .. 3t+2]   wh, ww, wl1, already normalised by the caller: the kernel divides nothing
+ * A line [1,R,N,1] is a tensor with W == 1: its column terms vanish by themselves.
+ * Per element o = c sC + h sH + w sW, all in float32, no contraction, in exactly this order (the 3-D kernel's: innermost
+ * axis first), clamp1(v) = fminf(fmaxf(v, -1), 1):
+ *   if (!dense_mode && grad[o] == 0.0f)  grad[o] stays untouched (a -0.0 stays -0.0)
+ *   p = param[o];  g = 0
+ *   if (w > 0)      g = g + ww * clamp1(p - param[o - sW])
+ *   if (w < W - 1)  g = g + ww * clamp1(p - param[o + sW])
+ *   if (h > 0)      g = g + wh * clamp1(p - param[o - sH])
+ *   if (h < H - 1)  g = g + wh * clamp1(p - param[o + sH])
+ *   if (wl1 != 0)   g = g + wl1 * sgn(p)                        sgn(+-0) = 0
+ *   grad[o] = grad[o] + g
+ * (a boundary term may instead be multiplied by a zero weight on a clamped in-bounds load: bit-equal for finite
+ * parameters; non-finite parameters are outside the contract).  No atomics: bitwise repeatable.  With wl1 = 0 and
+ * wh = ww = w / 6 this is dvgo_total_variation_add_grad(wy = wz = w) on the same memory viewed as [1,C,1,H,W], bit for bit.
+ * A workgroup owns one contiguous row of one tensor (channels-last: the W C floats of one h; channel-first: the W floats of
+ * one (c, h); any other layout goes through the strides), found through a prefix table that travels with the launch.
+ * n_tensors == 0: no-op, no table is looked at.  DVGO_EINVAL: n_tensors < 0 or > 8, a null table, a size below 1, a null
+ * params[t] or grads[t].  DVGO_ERANGE: a tensor of 2^31 elements or more, or 2^31 rows or more in all.  All of it is
+ * answered before any launch.
+ * --------------------------------------------------------------------------------- */
+int dvgo_plane_reg_add_grad(const float* const* params, float* const* grads, const int64_t* sizes,
+                            const int64_t* strides, const float* weights, int n_tensors, int dense_mode, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
