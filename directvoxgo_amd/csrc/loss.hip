@@ -208,7 +208,8 @@ int dvgo_adam_upd_multi(float* const* params, const float* const* grads, float* 
   A.n = n_tensors;
   int64_t tot = 0;
   for (int k = 0; k < n_tensors; ++k) {
-    if (!params[k] || !grads[k] || !exp_avg[k] || !exp_avg_sq[k] || numel[k] < 0) return DVGO_EINVAL;
+    // an empty tensor has no memory (torch hands out a null data pointer): nothing of it is read, as in dvgo_copy_multi
+    if (numel[k] < 0 || (numel[k] > 0 && (!params[k] || !grads[k] || !exp_avg[k] || !exp_avg_sq[k]))) return DVGO_EINVAL;
     A.p[k] = params[k]; A.g[k] = grads[k]; A.m[k] = exp_avg[k]; A.v[k] = exp_avg_sq[k];
     A.start[k] = tot;
     tot += numel[k];

@@ -559,7 +559,8 @@ int dvgo_total_variation_add_grad_slab(const float* param, float* grad, float wx
  *   n_rays_global is the ray count over all ranks (data parallel).
  * dvgo_viewdir_embed: emb [N, 3 + 6F] = cat([v, sin(v (x) freq), cos(v (x) freq)]) (lib/dvgo.py:524-525).
  * dvgo_adam_upd_multi: plain Adam (mode 0 of dvgo_adam_upd) over up to 16 small tensors in one launch;
- *   the pointer tables and numel are HOST arrays.
+ *   the pointer tables and numel are HOST arrays.  A tensor with numel[k] == 0 is skipped and its four pointers may be
+ *   NULL (an empty torch tensor has no memory), as in dvgo_copy_multi; a NULL pointer with numel[k] > 0 is DVGO_EINVAL.
  * --------------------------------------------------------------------------------- */
 int dvgo_loss_fwd_bwd(const float* rgb_marched, const float* alphainv_last, const float* target, int64_t N,
                       const float* raw_rgb, const float* weights, const int64_t* ray_id, int64_t M, const int64_t* m_dev,

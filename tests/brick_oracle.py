@@ -283,10 +283,13 @@ class Hyper:
         self.masked_k, self.masked_d = bool(masked_k0), bool(masked_density)
 
 
-def adam_reference(p, g, m, v, ss, b1, b2, eps, masked):
-    """The rule itself in float32 numpy, op for op `adam_one` (host test: equals oracle.adam_upd).  In place."""
+def adam_reference(p, g, m, v, ss, b1, b2, eps, masked, perlr=None):
+    """The rule itself in float32 numpy, op for op `adam_one` (host test: equals oracle.adam_upd).  In place.
+    `perlr` (mode 2, `adam_one<2>`): the step size of an element is fl(ss * perlr)."""
     f = np.float32
     ss, b1, b2, eps = f(ss), f(b1), f(b2), f(eps)
+    if perlr is not None:
+        ss = ss * np.asarray(perlr, np.float32)
     upd = (g != 0) if masked else np.ones(g.shape, bool)
     m1 = fma32(b1, m, (f(1) - b1) * g)
     v1 = fma32(b2, v, ((f(1) - b2) * g) * g)

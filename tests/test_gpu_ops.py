@@ -439,6 +439,24 @@ def test_fused_loss_matches_reference_formula():
                 assert x is None or float(x.abs().max()) == 0.0
             else:
                 np.testing.assert_allclose(x.cpu().numpy(), y.cpu().numpy(), rtol=1e-5, atol=1e-10)
+    # the sample count on the device (render_result['n_samples'], every sync-free step): the rows at and past it are
+    # undefined -- NaN inputs here, gradients never written -- so only the rows below the count are compared
+    cfg, count = dict(FINE_TRAIN), 12345
+    leaves = [torch.rand(N, 3, device='cuda').requires_grad_(), torch.rand(N, device='cuda').requires_grad_(),
+              torch.rand(M, 3, device='cuda').requires_grad_(), torch.rand(M, device='cuda').requires_grad_()]
+    with torch.no_grad():
+        leaves[2][count:] = float('nan'); leaves[3][count:] = float('nan')
+    res = {'rgb_marched': leaves[0], 'alphainv_last': leaves[1], 'raw_rgb': leaves[2], 'weights': leaves[3], 'ray_id': rid,
+           'n_samples': torch.tensor([count], device='cuda')}
+    below = dict(res, raw_rgb=leaves[2][:count], weights=leaves[3][:count], ray_id=rid[:count])
+    a = render_loss(below, tgt, 2 * N, cfg)
+    ga = torch.autograd.grad(a, leaves[:3])
+    b = fused_render_loss(res, tgt, 2 * N, cfg)
+    gb = torch.autograd.grad(b, leaves[:3])
+    assert bool(torch.isfinite(b))
+    np.testing.assert_allclose(float(b), float(a), rtol=2e-5)
+    for x, y, rows in zip(gb, ga, (N, N, count)):
+        np.testing.assert_allclose(x[:rows].cpu().numpy(), y[:rows].cpu().numpy(), rtol=1e-5, atol=1e-10)
 
 
 def test_loss_gradients_handed_to_the_composite_backward_equal_autograd_sums():
