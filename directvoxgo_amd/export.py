@@ -158,6 +158,9 @@ def _check_model(model):
     from .dmpigo import DirectMPIGO
     from .dvgo import DirectVoxGO
     from .triplane import TriPlaneVoxGO
+    if getattr(model, 'hash_table', None) is not None:
+        raise NotImplementedError(f'extract_mesh: colouring the vertices of a {type(model).__name__} (features from a hash '
+                                  'table, no k0) is not built; only DirectVoxGO is supported')
     if isinstance(model, TriPlaneVoxGO):
         raise NotImplementedError('extract_mesh: colouring the vertices of a TriPlaneVoxGO (features from planes, no k0) is '
                                   'not built; only DirectVoxGO is supported')

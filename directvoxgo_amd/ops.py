@@ -14,6 +14,8 @@ saved-tensor conventions) on top of the HIP kernels:
                               encoding as one MLP input row per plane, + backward; the Interp_MLPs stay torch modules)
   vm_sample                   TensoRF's vector-matrix features (no counterpart in the reference): per component a plane's
                               bilinear value times a line's linear value, + backward into planes and lines
+  hash_sample                 Instant-NGP's multiresolution hash-grid features (no counterpart in the reference): L trilinear
+                              levels, dense or hashed, in one table, + backward into the table
   segment_coo                 torch_scatter.segment_coo(src, index, out, reduce='sum')
   total_variation_add_grad    lib/cuda/total_variation.cpp:16-24
   plane_reg_add_grad          total variation and L1 of the tri-plane models' planes and lines added to their gradients, one
@@ -354,6 +356,108 @@ def vm_sample(planes, lines, xyz, xyz_min, xyz_max):
     shape = xyz.shape[:-1]
     flat = xyz.reshape(-1, 3).contiguous()
     out = _VMSample.apply(flat, xyz_min.contiguous(), xyz_max.contiguous(), *tensors)
+    return out.reshape(*shape, out.shape[-1])
+
+
+# ---------------------------------------------------------------------------------------------- hash grid
+HASH_MAX_LEVELS = 32                     # DVGO_HASH_MAX_LEVELS
+
+
+class HashLevels:
+    """The level table of a hash grid as the library takes it: `res` [L,3] node counts and `offsets` [L+1] first rows, kept
+    as host arrays.  Checked here with the library's own rule, so a bad table is a ValueError before anything is launched."""
+
+    def __init__(self, res, offsets):
+        res = torch.as_tensor(res).detach().cpu().to(torch.int64).reshape(-1, 3)
+        offsets = torch.as_tensor(offsets).detach().cpu().to(torch.int64).reshape(-1)
+        L_ = res.shape[0]
+        if not 1 <= L_ <= HASH_MAX_LEVELS or offsets.numel() != L_ + 1:
+            raise ValueError(f'res must be [L,3] and offsets [L+1] with 1 <= L <= {HASH_MAX_LEVELS}, got {tuple(res.shape)} and '
+                             f'{tuple(offsets.shape)}')
+        self.res, self.offsets = res.tolist(), offsets.tolist()
+        if self.offsets[0] < 0:
+            raise ValueError('offsets[0] must not be negative')
+        self.hashed = []
+        for l, (r, a, b) in enumerate(zip(self.res, self.offsets[:-1], self.offsets[1:])):
+            nodes, size = r[0] * r[1] * r[2], b - a
+            if min(r) < 2 or max(r) >= 2 ** 31:
+                raise ValueError(f'level {l}: every node count must be at least 2 (and below 2^31), got {r}')
+            if size != nodes and (size < 1 or size > nodes or size & (size - 1)):
+                raise ValueError(f'level {l}: {size} rows for {r[0]} x {r[1]} x {r[2]} = {nodes} nodes: a level has one row per '
+                                 'node (dense) or a power of two below that (hashed)')
+            self.hashed.append(size != nodes)
+        self.L, self.rows = L_, self.offsets[-1]
+        self.c_res = (ctypes.c_int32 * (3 * L_))(*[v for r in self.res for v in r])
+        self.c_offsets = (ctypes.c_int64 * (L_ + 1))(*self.offsets)
+
+
+def _hash_args(table, levels, xyz, name='table'):
+    if table.dim() != 2 or table.shape[1] not in (1, 2, 4, 8):
+        raise ValueError(f'{name} must be [T, F] with F in (1, 2, 4, 8), got {tuple(table.shape)}')
+    if table.shape[0] < levels.rows:
+        raise ValueError(f'{name} has {table.shape[0]} rows, the level table addresses {levels.rows}')
+    check_input(table, name); check_f32(table, name)
+    check_input(xyz, 'xyz'); check_f32(xyz, 'xyz')
+    if xyz.dim() != 2 or xyz.shape[1] != 3:
+        raise RuntimeError('xyz must be [M,3]')
+    return table.shape[1], xyz.shape[0]
+
+
+def hash_fwd(table, xyz, xyz_min, xyz_max, levels):
+    """dvgo_hash_fwd: table [T,F], xyz [M,3], `levels` a HashLevels -> [M, L F] (include/dvgo_hip.h has the arithmetic).
+    No autograd."""
+    Fc, M = _hash_args(table, levels, xyz)
+    out = torch.empty((M, levels.L * Fc), dtype=torch.float32, device=xyz.device)
+    with L.device_of(xyz):
+        L.call('dvgo_hash_fwd', table, Fc, levels.L, levels.c_res, levels.c_offsets, xyz, xyz_min, xyz_max, M, out, stream_of(xyz))
+    return out
+
+
+def hash_bwd(grad_out, grad_table, xyz, xyz_min, xyz_max, levels, run=0, mode=0):
+    """dvgo_hash_bwd: accumulates into the buffer `grad_table` (shaped like the table) in place.  `mode` 1: a lane merges
+    `run` consecutive samples of a level while they stay in one cell; 3: the same with one lane per channel; 2: nothing
+    merged (0: the library's choice, for both)."""
+    Fc, M = _hash_args(grad_table, levels, xyz, 'grad_table')
+    check_input(grad_out, 'grad_out'); check_f32(grad_out, 'grad_out')
+    if tuple(grad_out.shape) != (M, levels.L * Fc):
+        raise RuntimeError('grad_out has the wrong shape')
+    with L.device_of(xyz):
+        L.call('dvgo_hash_bwd', grad_out, grad_table, Fc, levels.L, levels.c_res, levels.c_offsets, xyz, xyz_min, xyz_max, M,
+               int(run), int(mode), stream_of(xyz))
+    return grad_table
+
+
+class _HashSample(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, table, xyz, xyz_min, xyz_max, levels):
+        out = hash_fwd(table, xyz, xyz_min, xyz_max, levels)
+        ctx.save_for_backward(xyz, xyz_min, xyz_max)          # linear in the table: its values are not needed again
+        ctx.levels, ctx.shape = levels, table.shape
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        xyz, xyz_min, xyz_max = ctx.saved_tensors
+        grad = None
+        if ctx.needs_input_grad[0]:
+            grad = torch.zeros(ctx.shape, dtype=torch.float32, device=xyz.device)
+            hash_bwd(grad_out.contiguous(), grad, xyz, xyz_min, xyz_max, ctx.levels)
+        return grad, None, None, None, None
+
+
+def hash_sample(table, xyz, xyz_min, xyz_max, res, offsets=None):
+    """Multiresolution hash-grid features (Instant-NGP) as one HIP op: `table` [T_total, F] float32 contiguous, F in
+    (1, 2, 4, 8); `res` [L,3] the node counts of every level along x, y, z and `offsets` [L+1] the levels' first rows (host
+    values: tensors, arrays or lists), or `res` a HashLevels made from them once; xyz [...,3] world coordinates ->
+    [..., L F], level by level.  A level with one row per node is dense, any other is hashed into its power-of-two row
+    count; a table that fits neither is a ValueError.  Positions outside the box read its faces.  Differentiable w.r.t.
+    `table` only."""
+    levels = res if isinstance(res, HashLevels) else HashLevels(res, offsets)
+    shape = xyz.shape[:-1]
+    flat = xyz.detach().reshape(-1, 3).contiguous()
+    _hash_args(table, levels, flat)
+    out = _HashSample.apply(table, flat, xyz_min.contiguous(), xyz_max.contiguous(), levels)
     return out.reshape(*shape, out.shape[-1])
 
 

@@ -195,6 +195,9 @@ class TrainStep:
         # paths that take both grids' gradients together (brick scatter with the fused Adam, combined gradient rows) stay off
         no_k0 = getattr(model, 'k0', None) is None           # TriPlaneVoxGO: the colour features come from planes, not a grid
         self.k0_idle = bool(getattr(model, 'uses_posenc', False)) or no_k0
+        if getattr(model, 'hash_table', None) is not None and self.world > 1:
+            raise NotImplementedError(f'data-parallel training of {type(model).__name__} (hash-grid features, a model without '
+                                      'k0) is not built: train it on one GPU')
         if no_k0 and self.world > 1:
             raise NotImplementedError('data-parallel training of a model without k0 (TriPlaneVoxGO) is not built: train it on '
                                       'one GPU')

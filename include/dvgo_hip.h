@@ -41,7 +41,7 @@ extern "C" {
 /* version of this ABI; bumped on any signature change (6: the positional-encoding colour head; 7: the contracted
  * sampler and the distortion loss of unbounded scenes; 8: the tri-plane sampler; 9: the trilinear sample's gradient
  * with respect to the position; 10: the LIIF plane decoder; 11: the fused march's gradient with respect to its rays).
- * The two dvgo_plane_rows_* and the two dvgo_vm_* entries were added without a bump, unlike the additions before them: an
+ * The two dvgo_plane_rows_*, the two dvgo_vm_* and the two dvgo_hash_* entries were added without a bump, unlike the additions before them: an
  * existing test pins the value 11, and a library built before them is still caught at load, by the check that every declared entry is exported. */
 #define DVGO_ABI_VERSION 11
 int dvgo_abi_version(void);
@@ -890,6 +890,44 @@ int dvgo_vm_bwd(const float* grad_out,
  * --------------------------------------------------------------------------------- */
 int dvgo_plane_reg_add_grad(const float* const* params, float* const* grads, const int64_t* sizes,
                             const int64_t* strides, const float* weights, int n_tensors, int dense_mode, void* stream);
+
+/* ---------------------------------------------------------------------------------
+ * Multiresolution hash-grid features (csrc/hashgrid.hip).  The encoding
+ * of Instant-NGP (Mueller et al., SIGGRAPH 2022): L trilinear lattices of growing resolution whose nodes are rows of ONE
+ * table.  No counterpart in the reference; the contract is this text.
+ *   table    fp32 [T_total, F], contiguous, F in {1, 2, 4, 8}, aligned to min(4 F, 16) bytes (as are out, grad_out, grad_table)
+ *   res      HOST int32 [L, 3]: the node counts (Rx, Ry, Rz) of level l along the world axes, each at least 2
+ *   offsets  HOST int64 [L + 1], offsets[0] >= 0: the first row of every level; size_l = offsets[l + 1] - offsets[l]
+ *            size_l == Rx Ry Rz: level l is DENSE.  Otherwise it is HASHED and size_l must be a power of two below Rx Ry Rz.
+ *   1 <= L <= DVGO_HASH_MAX_LEVELS.
+ * Per sample m, level l and axis a, all in float32, no contraction:
+ *   g = ((((p_a - min_a) / (max_a - min_a)) * 2 - 1) + 1) / 2 * (R_a - 1)          (the library's align_corners=True coordinate)
+ *   g = fminf(fmaxf(g, 0), R_a - 1);   f = min((int)floorf(g), R_a - 2);   w0 = (f + 1) - g;   w1 = g - f
+ * so a position outside the box reads the box's face (no zero padding) and all eight corners exist.  Corner n = 0..7 is
+ * (fx + (n >> 2 & 1), fy + (n >> 1 & 1), fz + (n & 1)): x slowest, z fastest; its weight is (wx * wy) * wz.  Its row:
+ *   dense    (ix Ry + iy) Rz + iz
+ *   hashed   ((uint32)ix * 1u ^ (uint32)iy * 2654435761u ^ (uint32)iz * 805459861u) & (size_l - 1), wrapping 32-bit products
+ * dvgo_hash_fwd: xyz [M,3] world coordinates, xyz_min / xyz_max device float[3] -> out [M, L F]:
+ *   out[m, l F + c] = acc after acc = 0; acc = fmaf(table[offsets[l] + row_n, c], w_n, acc) for n = 0..7.  Bitwise repeatable.
+ * dvgo_hash_bwd: grad_out [M, L F] and a buffer grad_table [T_total, F] (zero-filled or holding a partial sum):
+ *   grad_table[offsets[l] + row_n, c] += w_n * grad_out[m, l F + c]
+ *   with float atomics: the summation order is not reproducible.  Two corners of one cell that share a row both add.  The
+ *   table's values are not read.  No gradient for xyz.
+ *   mode 1: a lane owns `run` consecutive samples of one level and sums the 8 F corner terms in registers while the samples
+ *     stay in one cell, before its atomics (run 1: nothing merged; 0: the library's default).  mode 2: one lane per (sample,
+ *     level, corner), nothing merged, run ignored.  mode 3: mode 1 with the F channels of a row on F neighbouring lanes (a lane
+ *     owns run, level and channel): one atomic instruction adds whole rows.  mode 0: the library's choice
+ *     (profiles/hash/README.md).
+ * M == 0: no-op, no device pointer is looked at (the level table is still checked).  DVGO_EINVAL: F outside {1,2,4,8}, L outside
+ * 1..DVGO_HASH_MAX_LEVELS, a node count below 2, offsets[0] < 0, a size_l that is neither the node count nor a power of two
+ * below it, negative M or run, a mode outside 0..3, null or misaligned pointers.  DVGO_ERANGE: M L F >= 2^31 (mode 2:
+ * 8 M L >= 2^31), Rx Ry >= 2^31, a hashed level of more than 2^31 rows.  All of it is answered before any launch.
+ * --------------------------------------------------------------------------------- */
+#define DVGO_HASH_MAX_LEVELS 32
+int dvgo_hash_fwd(const float* table, int F, int L, const int32_t* res, const int64_t* offsets, const float* xyz,
+                  const float* xyz_min, const float* xyz_max, int64_t M, float* out, void* stream);
+int dvgo_hash_bwd(const float* grad_out, float* grad_table, int F, int L, const int32_t* res, const int64_t* offsets,
+                  const float* xyz, const float* xyz_min, const float* xyz_max, int64_t M, int run, int mode, void* stream);
 
 #ifdef __cplusplus
 }
