@@ -16,6 +16,7 @@
 // and sums in a register while the nearest texel stays the same: consecutive kept samples of a ray are half a voxel
 // apart.  Lane order as in triplane_bwd_kernel: channel fastest when every plane is channels-last, else sample fastest.
 #include "common.h"
+#include "plane2d.h"
 
 // samples a lane of the scatter merges before its atomics.  Started as a guess (triplane.hip's value); measured at M = 131 072
 // it takes 0.35-0.57 of the unmerged time and 8 is 10-14 % faster still (profiles/liif/README.md): short batches not measured yet
@@ -119,13 +120,7 @@ liif_gather_kernel(LfPlane PA, LfPlane PB, LfPlane PC, int C, int D, int E, cons
   float* o = inp + ((int64_t)se * M + m) * D + c;
   if (c < C) {
     const float* t = q.p + (int64_t)c * q.sC + (int64_t)g.row * q.sH + (int64_t)g.col * q.sW;
-    if constexpr (VEC == 4) {
-      *reinterpret_cast<float4*>(o) = *reinterpret_cast<const float4*>(t);
-    } else if constexpr (VEC == 2) {
-      *reinterpret_cast<float2*>(o) = *reinterpret_cast<const float2*>(t);
-    } else {
-      o[0] = t[0];
-    }
+    tp_store<VEC>(o, tp_load<VEC>(t, q.sC));
     return;
   }
   const int k = c - C;                                   // 0 .. D - C - 1, a multiple of VEC
@@ -183,40 +178,17 @@ liif_scatter_kernel(LfPlane PA, LfPlane PB, LfPlane PC, int C, int D, int E, con
   if (cr >= 0) atomicAdd(base + (int64_t)cr * q.sH + (int64_t)cc * q.sW, acc);
 }
 
-template <int VEC> struct LfVal { float v[VEC]; };
-
-template <int VEC>
-__device__ __forceinline__ LfVal<VEC> lf_load(const float* __restrict__ p) {
-  LfVal<VEC> r;
-  if constexpr (VEC == 4) {
-    const float4 t = *reinterpret_cast<const float4*>(p);
-    r.v[0] = t.x; r.v[1] = t.y; r.v[2] = t.z; r.v[3] = t.w;
-  } else {
-    r.v[0] = p[0];
-  }
-  return r;
-}
-
-template <int VEC>
-__device__ __forceinline__ void lf_store(float* __restrict__ p, const LfVal<VEC>& r) {
-  if constexpr (VEC == 4) {
-    *reinterpret_cast<float4*>(p) = make_float4(r.v[0], r.v[1], r.v[2], r.v[3]);
-  } else {
-    p[0] = r.v[0];
-  }
-}
-
 // sum over the shifts of plane s at sample m, channels c .. c + VEC: acc = fmaf(pred, wgt, acc) from 0, in shift order
 template <int VEC>
-__device__ __forceinline__ LfVal<VEC> lf_blend(const float* __restrict__ pred, const float* __restrict__ wgt, int C,
+__device__ __forceinline__ TpVal<VEC> lf_blend(const float* __restrict__ pred, const float* __restrict__ wgt, int C,
                                                int64_t M, int E, int s, int64_t m, int c) {
-  LfVal<VEC> acc;
+  TpVal<VEC> acc;
 #pragma unroll
   for (int i = 0; i < VEC; ++i) acc.v[i] = 0.f;
   for (int e = 0; e < E; ++e) {
     const int64_t row = (int64_t)(s * E + e) * M + m;
     const float w = wgt[row];
-    const LfVal<VEC> p = lf_load<VEC>(pred + row * C + c);
+    const TpVal<VEC> p = tp_load<VEC>(pred + row * C + c, 1);
 #pragma unroll
     for (int i = 0; i < VEC; ++i) acc.v[i] = fmaf(p.v[i], w, acc.v[i]);
   }
@@ -233,19 +205,19 @@ liif_blend_fwd_kernel(const float* __restrict__ pred, const float* __restrict__ 
   const unsigned int cg = (unsigned int)C / VEC;
   const unsigned int per = SUM ? cg : 3u * cg;
   const unsigned int m = tid / per, j = tid - m * per;
-  LfVal<VEC> r;
+  TpVal<VEC> r;
   if (SUM) {
     const int c = (int)j * VEC;
-    const LfVal<VEC> a = lf_blend<VEC>(pred, wgt, C, M, E, 0, m, c);
-    const LfVal<VEC> b = lf_blend<VEC>(pred, wgt, C, M, E, 1, m, c);
-    const LfVal<VEC> d = lf_blend<VEC>(pred, wgt, C, M, E, 2, m, c);
+    const TpVal<VEC> a = lf_blend<VEC>(pred, wgt, C, M, E, 0, m, c);
+    const TpVal<VEC> b = lf_blend<VEC>(pred, wgt, C, M, E, 1, m, c);
+    const TpVal<VEC> d = lf_blend<VEC>(pred, wgt, C, M, E, 2, m, c);
 #pragma unroll
     for (int i = 0; i < VEC; ++i) r.v[i] = (a.v[i] + b.v[i]) + d.v[i];
   } else {
     const unsigned int s = j / cg;
     r = lf_blend<VEC>(pred, wgt, C, M, E, (int)s, m, (int)(j - s * cg) * VEC);
   }
-  lf_store<VEC>(out + (int64_t)tid * VEC, r);
+  tp_store<VEC>(out + (int64_t)tid * VEC, r);
 }
 
 // blockIdx.y = s * E + e; per = M * C / VEC lanes in x: grad_pred[s, e, m, c] = grad_out[m, c'] * wgt[s, e, m]
@@ -261,43 +233,24 @@ liif_blend_bwd_kernel(const float* __restrict__ gout, const float* __restrict__ 
   const unsigned int m = tid / cg;
   const int c = (int)(tid - m * cg) * VEC;
   const float w = wgt[(int64_t)se * M + m];
-  const LfVal<VEC> g = lf_load<VEC>(gout + (sum ? (int64_t)m * C + c : (int64_t)m * 3 * C + s * C + c));
-  LfVal<VEC> r;
+  const TpVal<VEC> g = tp_load<VEC>(gout + (sum ? (int64_t)m * C + c : (int64_t)m * 3 * C + s * C + c), 1);
+  TpVal<VEC> r;
 #pragma unroll
   for (int i = 0; i < VEC; ++i) r.v[i] = g.v[i] * w;
-  lf_store<VEC>(gpred + ((int64_t)se * M + m) * C + c, r);
+  tp_store<VEC>(gpred + ((int64_t)se * M + m) * C + c, r);
 }
 
-static bool lf_plane_ok(const LfPlane& q) { return q.H >= 1 && q.W >= 1; }
-static bool lf_plane_vec(const LfPlane& q, int V) {
-  return q.sC == 1 && (q.sH % V == 0 || q.H == 1) && (q.sW % V == 0 || q.W == 1) && ((((uintptr_t)q.p) & (4 * V - 1)) == 0);
+// plane q and the coordinate table it is decoded against (plane2d.h: pr_table)
+static LfPlane lf_plane(const TpPlane& q, int Ta, int Tb) {
+  const PrTable t = pr_table(Ta, Tb);
+  return LfPlane{q.p, q.H, q.W, q.sC, q.sH, q.sW, Ta, Tb, t.ra, t.rb, t.sa, t.sb};
 }
 
-static LfPlane lf_plane(const float* p, int H, int W, int64_t sC, int64_t sH, int64_t sW, int Ta, int Tb) {
-  LfPlane q;
-  q.p = const_cast<float*>(p);
-  q.H = H; q.W = W; q.sC = sC; q.sH = sH; q.sW = sW;
-  q.Ta = Ta; q.Tb = Tb;
-  q.ra = 1.0f / (float)Ta; q.rb = 1.0f / (float)Tb;
-  q.sa = (Ta > 1) ? 2.0f / (float)(Ta - 1) : 0.0f;
-  q.sb = (Tb > 1) ? 2.0f / (float)(Tb - 1) : 0.0f;
-  return q;
+// tp_check with this decoder's shapes, the world extents; a sample has 3 E rows of D floats
+static int lf_check(const TpPlanes& Q, int C, int64_t M, int Wx, int Wy, int Wz, const void* xyz, const void* mn,
+                    const void* mx, std::initializer_list<const void*> io, int D, int E) {
+  return tp_check(Q, C, M, Wx >= 1 && Wy >= 1 && Wz >= 1, xyz, mn, mx, io, 3 * E, D);
 }
-
-// 1: nothing to do; 0: launch; < 0: error.  width = the floats of a sample's slab rows (3 E D)
-static int lf_check(const LfPlane& a, const LfPlane& b, const LfPlane& c, int C, const void* xyz, const void* mn,
-                    const void* mx, int64_t M, int Wx, int Wy, int Wz, const void* io, const void* io2, int D, int E) {
-  if (M < 0 || C < 0 || !lf_plane_ok(a) || !lf_plane_ok(b) || !lf_plane_ok(c) || Wx < 1 || Wy < 1 || Wz < 1) return DVGO_EINVAL;
-  if (M == 0 || C == 0) return 1;
-  if (!a.p || !b.p || !c.p || !xyz || !mn || !mx || !io || !io2) return DVGO_EINVAL;
-  if (!dvgo_fits(M * 3 * E * (int64_t)D)) return DVGO_ERANGE;
-  return 0;
-}
-
-#define LF_PLANES(px, py, pz)                                                            \
-  const LfPlane A = lf_plane(px, H_xy, W_xy, sC_xy, sH_xy, sW_xy, Wx, Wy);               \
-  const LfPlane B = lf_plane(py, H_yz, W_yz, sC_yz, sH_yz, sW_yz, Wy, Wz);               \
-  const LfPlane P = lf_plane(pz, H_zx, W_zx, sC_zx, sH_zx, sW_zx, Wz, Wx)
 
 static int lf_blend_check(const void* a, const void* b, const void* c, int C, int64_t M, int E) {
   if (M < 0 || C < 0 || (E != 1 && E != 4)) return DVGO_EINVAL;
@@ -316,15 +269,15 @@ int dvgo_liif_gather(const float* xy, int H_xy, int W_xy, int64_t sC_xy, int64_t
                      const float* zx, int H_zx, int W_zx, int64_t sC_zx, int64_t sH_zx, int64_t sW_zx,
                      int C, const float* xyz, const float* xyz_min, const float* xyz_max, int64_t M,
                      int Wx, int Wy, int Wz, int cell_decode, int local_ensemble, float* inp, float* wgt, void* stream) {
-  LF_PLANES(xy, yz, zx);
+  const TpPlanes Q = TP_PLANES(xy, yz, zx);
   const int D = C + (cell_decode ? 4 : 2), E = local_ensemble ? 4 : 1;
-  const int rc = lf_check(A, B, P, C, xyz, xyz_min, xyz_max, M, Wx, Wy, Wz, inp, wgt, D, E);
-  if (rc < 0) return rc;
-  if (rc == 1) return 0;
+  const int rc = lf_check(Q, C, M, Wx, Wy, Wz, xyz, xyz_min, xyz_max, {inp, wgt}, D, E);
+  if (rc) return rc < 0 ? rc : 0;
   hipStream_t st = (hipStream_t)stream;
+  const LfPlane A = lf_plane(Q.a, Wx, Wy), B = lf_plane(Q.b, Wy, Wz), P = lf_plane(Q.c, Wz, Wx);
   int vec = 1;
-  if (C % 4 == 0 && D % 4 == 0 && lf_plane_vec(A, 4) && lf_plane_vec(B, 4) && lf_plane_vec(P, 4) && lf_al16(inp)) vec = 4;
-  else if (C % 2 == 0 && lf_plane_vec(A, 2) && lf_plane_vec(B, 2) && lf_plane_vec(P, 2) && ((((uintptr_t)inp) & 7) == 0)) vec = 2;
+  if (C % 4 == 0 && D % 4 == 0 && tp_planes_vec(Q, 4) && lf_al16(inp)) vec = 4;
+  else if (C % 2 == 0 && tp_planes_vec(Q, 2) && ((((uintptr_t)inp) & 7) == 0)) vec = 2;
   const unsigned int per = (unsigned int)(M * (D / vec));
   const dim3 grid((unsigned int)dvgo_blocks(per, DVGO_BLOCK), (unsigned int)(3 * E));
   if (vec == 4)
@@ -343,21 +296,19 @@ int dvgo_liif_scatter(const float* grad_inp,
                       float* g_zx, int H_zx, int W_zx, int64_t sC_zx, int64_t sH_zx, int64_t sW_zx,
                       int C, const float* xyz, const float* xyz_min, const float* xyz_max, int64_t M,
                       int Wx, int Wy, int Wz, int cell_decode, int local_ensemble, int run, void* stream) {
-  LF_PLANES(g_xy, g_yz, g_zx);
+  const TpPlanes Q = TP_PLANES(g_xy, g_yz, g_zx);
   const int D = C + (cell_decode ? 4 : 2), E = local_ensemble ? 4 : 1;
   if (run < 0) return DVGO_EINVAL;
-  const int rc = lf_check(A, B, P, C, xyz, xyz_min, xyz_max, M, Wx, Wy, Wz, grad_inp, grad_inp, D, E);
-  if (rc < 0) return rc;
-  if (rc == 1) return 0;
+  const int rc = lf_check(Q, C, M, Wx, Wy, Wz, xyz, xyz_min, xyz_max, {grad_inp}, D, E);
+  if (rc) return rc < 0 ? rc : 0;
   hipStream_t st = (hipStream_t)stream;
-  if (run == 0) run = LF_RUN_DEFAULT;
-  const int64_t nchunk = (M + run - 1) / run;
-  const int64_t per = nchunk * C;
-  const dim3 grid((unsigned int)dvgo_blocks(per, DVGO_BLOCK), (unsigned int)(3 * E));
-  if (A.sC == 1 && B.sC == 1 && P.sC == 1 && C > 1)
-    liif_scatter_kernel<true><<<grid, DVGO_BLOCK, 0, st>>>(A, B, P, C, D, E, grad_inp, xyz, xyz_min, xyz_max, M, run, nchunk, per);
+  const LfPlane A = lf_plane(Q.a, Wx, Wy), B = lf_plane(Q.b, Wy, Wz), P = lf_plane(Q.c, Wz, Wx);
+  const TpScatter S = tp_scatter(Q, C, M, run, LF_RUN_DEFAULT, C);       // one (plane, shift) per blockIdx.y
+  const dim3 grid((unsigned int)dvgo_blocks(S.lanes, DVGO_BLOCK), (unsigned int)(3 * E));
+  if (S.cfast)
+    liif_scatter_kernel<true><<<grid, DVGO_BLOCK, 0, st>>>(A, B, P, C, D, E, grad_inp, xyz, xyz_min, xyz_max, M, S.run, S.nchunk, S.lanes);
   else
-    liif_scatter_kernel<false><<<grid, DVGO_BLOCK, 0, st>>>(A, B, P, C, D, E, grad_inp, xyz, xyz_min, xyz_max, M, run, nchunk, per);
+    liif_scatter_kernel<false><<<grid, DVGO_BLOCK, 0, st>>>(A, B, P, C, D, E, grad_inp, xyz, xyz_min, xyz_max, M, S.run, S.nchunk, S.lanes);
   DVGO_LAUNCH_CHECK();
   return 0;
 }

@@ -1,8 +1,12 @@
-// The bilinear corner walk of a 2-D feature plane, shared by triplane.hip and plane_rows.hip: the plane descriptor,
-// the per-axis floor and weights, the four-corner fma chain, the four-corner atomic flush and the run-merging walk of the
-// gradient scatter (include/dvgo_hip.h, the tri-plane block, states the arithmetic).
+// What the samplers over three 2-D feature planes share (triplane.hip, plane_rows.hip, liif.hip, vm.hip).
+// Device: the plane descriptor, the per-axis floor and weights, the four-corner fma chain, the four-corner atomic flush
+// and the run-merging walk of the gradient scatter (include/dvgo_hip.h, the tri-plane block, states the arithmetic).
+// Host, below: the pack of the 18 plane scalars of an entry point, the vector-load predicate, the staged argument check,
+// the launch shape of a scatter and the coordinate-table numbers of the two decoders.
 #pragma once
 #include <limits.h>
+
+#include <initializer_list>
 
 #include "common.h"
 
@@ -68,6 +72,18 @@ __device__ __forceinline__ TpVal<VEC> tp_load(const float* __restrict__ p, int64
     for (int i = 0; i < VEC; ++i) r.v[i] = p[i * sC];
   }
   return r;
+}
+
+template <int VEC>
+__device__ __forceinline__ void tp_store(float* __restrict__ p, const TpVal<VEC>& r) {
+  if constexpr (VEC == 4) {
+    *reinterpret_cast<float4*>(p) = make_float4(r.v[0], r.v[1], r.v[2], r.v[3]);
+  } else if constexpr (VEC == 2) {
+    *reinterpret_cast<float2*>(p) = make_float2(r.v[0], r.v[1]);
+  } else {
+#pragma unroll
+    for (int i = 0; i < VEC; ++i) p[i] = r.v[i];
+  }
 }
 
 // VEC channels from c on of plane q at sample m
@@ -156,4 +172,69 @@ __device__ __forceinline__ void tp_scatter_lane(const TpPlane PA, const TpPlane 
     a11 += (b.wh1 * b.ww1) * gv;
   }
   if (ch != INT_MIN) tp_flush(q, base, ch, cw, a00, a01, a10, a11);
+}
+
+// ---------------------------------------------------------------------------------------------- host side
+struct TpPlanes { TpPlane a, b, c; };
+
+// the three planes of an entry point from its 18 plane scalars, which every entry point names alike
+#define TP_PLANES(px, py, pz)                                                           \
+  TpPlanes{TpPlane{const_cast<float*>(px), H_xy, W_xy, sC_xy, sH_xy, sW_xy},            \
+           TpPlane{const_cast<float*>(py), H_yz, W_yz, sC_yz, sH_yz, sW_yz},            \
+           TpPlane{const_cast<float*>(pz), H_zx, W_zx, sC_zx, sH_zx, sW_zx}}
+
+static bool tp_plane_ok(const TpPlane& q) { return q.H >= 1 && q.W >= 1; }
+
+// a texel's channels can be read V floats at a time: channels-last, every texel and the base on a 4 V byte boundary
+static bool tp_plane_vec(const TpPlane& q, int V) {
+  return q.sC == 1 && (q.sH % V == 0 || q.H == 1) && (q.sW % V == 0 || q.W == 1) && ((((uintptr_t)q.p) & (4 * V - 1)) == 0);
+}
+static bool tp_planes_vec(const TpPlanes& P, int V) { return tp_plane_vec(P.a, V) && tp_plane_vec(P.b, V) && tp_plane_vec(P.c, V); }
+
+// The argument check of every entry point that takes three planes.  < 0: the error; 1: nothing to do; 0: launch.
+// The stages and their order are the contract (tests/test_plane_entries_host.py): shapes, among them the caller's own
+// (`shape`: world extents, P, line lengths); M == 0 or C == 0, with no pointer looked at; NULL pointers, among them the
+// caller's own (`ptrs`); the 32-bit range of what a launch indexes, a sample's `rows` rows of `row` floats.
+static int tp_check(const TpPlanes& P, int C, int64_t M, bool shape, const void* xyz, const void* mn, const void* mx,
+                    std::initializer_list<const void*> ptrs, int rows, int64_t row) {
+  if (M < 0 || C < 0 || !tp_plane_ok(P.a) || !tp_plane_ok(P.b) || !tp_plane_ok(P.c) || !shape) return DVGO_EINVAL;
+  if (M == 0 || C == 0) return 1;
+  bool null = !P.a.p || !P.b.p || !P.c.p || !xyz || !mn || !mx;
+  for (const void* p : ptrs) null = null || !p;
+  if (null) return DVGO_EINVAL;
+  if (!dvgo_fits(row) || !dvgo_fits(M * rows * row)) return DVGO_ERANGE;
+  return 0;
+}
+
+// The launch shape of a gradient scatter: a lane merges `run` consecutive samples (0: `run_default`), nchunk = ceil(M / run)
+// runs times `per` lanes each; channel fastest when every plane is channels-last, else sample fastest.
+struct TpScatter {
+  int run;
+  int64_t nchunk, lanes;
+  bool cfast;
+};
+
+static TpScatter tp_scatter(const TpPlanes& P, int C, int64_t M, int run, int run_default, int per) {
+  TpScatter s;
+  s.run = run ? run : run_default;
+  s.nchunk = (M + s.run - 1) / s.run;
+  s.lanes = s.nchunk * per;
+  s.cfast = P.a.sC == 1 && P.b.sC == 1 && P.c.sC == 1 && C > 1;
+  return s;
+}
+
+// the coordinate table a plane is decoded against: Ta rows, Tb columns (two world_size extents)
+struct PrTable {
+  int Ta, Tb;
+  float sa, sb;          // 2 / (Ta - 1), 2 / (Tb - 1)   (0 when the extent is 1: node = -1)
+  float ra, rb;          // 1 / Ta, 1 / Tb
+};
+
+static PrTable pr_table(int Ta, int Tb) {
+  PrTable t;
+  t.Ta = Ta; t.Tb = Tb;
+  t.sa = (Ta > 1) ? 2.0f / (float)(Ta - 1) : 0.0f;
+  t.sb = (Tb > 1) ? 2.0f / (float)(Tb - 1) : 0.0f;
+  t.ra = 1.0f / (float)Ta; t.rb = 1.0f / (float)Tb;
+  return t;
 }

@@ -17,13 +17,6 @@
 #include "common.h"
 #include "plane2d.h"
 
-// the coordinate table a plane is decoded against: Ta rows, Tb columns (two world_size extents)
-struct PrTable {
-  int Ta, Tb;
-  float sa, sb;          // 2 / (Ta - 1), 2 / (Tb - 1)   (0 when the extent is 1: node = -1)
-  float ra, rb;          // 1 / Ta, 1 / Tb
-};
-
 __device__ __forceinline__ PrTable pr_pick(const PrTable A, const PrTable B, const PrTable D, int s) {
   PrTable t;
   t.Ta = (s == 0) ? A.Ta : (s == 1) ? B.Ta : D.Ta;
@@ -96,13 +89,7 @@ plane_rows_fwd_kernel(TpPlane PA, TpPlane PB, TpPlane PC, PrTable TA, PrTable TB
 #pragma unroll
     for (int i = 0; i < VEC; ++i) r.v[i] = pr_tail(c - C + i, P, q0, q1, t);
   }
-  if constexpr (VEC == 4) {
-    *reinterpret_cast<float4*>(o) = make_float4(r.v[0], r.v[1], r.v[2], r.v[3]);
-  } else if constexpr (VEC == 2) {
-    *reinterpret_cast<float2*>(o) = make_float2(r.v[0], r.v[1]);
-  } else {
-    o[0] = r.v[0];
-  }
+  tp_store<VEC>(o, r);
 }
 
 // total = nchunk * 3C lanes, nchunk = ceil(M / run): plane2d.h's walk over rows of D floats, plane s's slab M * D floats
@@ -115,36 +102,14 @@ plane_rows_bwd_kernel(TpPlane PA, TpPlane PB, TpPlane PC, int C, int D, const fl
   tp_scatter_lane<CFAST>(PA, PB, PC, C, ginp, D, M * D, xyz, mn, mx, M, run, nchunk, total);
 }
 
-static bool pr_plane_ok(const TpPlane& q) { return q.H >= 1 && q.W >= 1; }
-static bool pr_plane_vec(const TpPlane& q, int V) {
-  return q.sC == 1 && (q.sH % V == 0 || q.H == 1) && (q.sW % V == 0 || q.W == 1) && ((((uintptr_t)q.p) & (4 * V - 1)) == 0);
-}
+// a row's floats
+static int64_t pr_width(int C, int P, int cell_decode) { return (int64_t)C + 2 + 4 * (int64_t)P + (cell_decode ? 2 : 0); }
 
-static PrTable pr_table(int Ta, int Tb) {
-  PrTable t;
-  t.Ta = Ta; t.Tb = Tb;
-  t.sa = (Ta > 1) ? 2.0f / (float)(Ta - 1) : 0.0f;
-  t.sb = (Tb > 1) ? 2.0f / (float)(Tb - 1) : 0.0f;
-  t.ra = 1.0f / (float)Ta; t.rb = 1.0f / (float)Tb;
-  return t;
+// tp_check with this decoder's shapes: the world extents and P
+static int pr_check(const TpPlanes& Q, int C, int64_t M, int Wx, int Wy, int Wz, int P, const void* xyz, const void* mn,
+                    const void* mx, const void* io, int64_t D) {
+  return tp_check(Q, C, M, Wx >= 1 && Wy >= 1 && Wz >= 1 && P >= 1, xyz, mn, mx, {io}, 3, D);
 }
-
-// 1: nothing to do; 0: launch; < 0: error
-static int pr_check(const TpPlane& a, const TpPlane& b, const TpPlane& c, int C, const void* xyz, const void* mn,
-                    const void* mx, int64_t M, int Wx, int Wy, int Wz, int P, const void* io, int64_t D) {
-  if (M < 0 || C < 0 || !pr_plane_ok(a) || !pr_plane_ok(b) || !pr_plane_ok(c) || Wx < 1 || Wy < 1 || Wz < 1 || P < 1)
-    return DVGO_EINVAL;
-  if (M == 0 || C == 0) return 1;
-  if (!a.p || !b.p || !c.p || !xyz || !mn || !mx || !io) return DVGO_EINVAL;
-  if (!dvgo_fits(D) || !dvgo_fits(M * 3 * D)) return DVGO_ERANGE;
-  return 0;
-}
-
-#define PR_PLANES(px, py, pz)                                                                       \
-  const TpPlane A = TpPlane{const_cast<float*>(px), H_xy, W_xy, sC_xy, sH_xy, sW_xy};               \
-  const TpPlane B = TpPlane{const_cast<float*>(py), H_yz, W_yz, sC_yz, sH_yz, sW_yz};               \
-  const TpPlane Q = TpPlane{const_cast<float*>(pz), H_zx, W_zx, sC_zx, sH_zx, sW_zx};               \
-  const int64_t D = (int64_t)C + 2 + 4 * (int64_t)P + (cell_decode ? 2 : 0)
 
 extern "C" {
 
@@ -153,25 +118,25 @@ int dvgo_plane_rows_fwd(const float* xy, int H_xy, int W_xy, int64_t sC_xy, int6
                         const float* zx, int H_zx, int W_zx, int64_t sC_zx, int64_t sH_zx, int64_t sW_zx,
                         int C, const float* xyz, const float* xyz_min, const float* xyz_max, int64_t M,
                         int Wx, int Wy, int Wz, int P, int cell_decode, float* inp, void* stream) {
-  PR_PLANES(xy, yz, zx);
-  const int rc = pr_check(A, B, Q, C, xyz, xyz_min, xyz_max, M, Wx, Wy, Wz, P, inp, D);
-  if (rc < 0) return rc;
-  if (rc == 1) return 0;
+  const TpPlanes Q = TP_PLANES(xy, yz, zx);
+  const int64_t D = pr_width(C, P, cell_decode);
+  const int rc = pr_check(Q, C, M, Wx, Wy, Wz, P, xyz, xyz_min, xyz_max, inp, D);
+  if (rc) return rc < 0 ? rc : 0;
   hipStream_t st = (hipStream_t)stream;
   const PrTable TA = pr_table(Wx, Wy), TB = pr_table(Wy, Wz), TC = pr_table(Wz, Wx);
   int vec = 1;
-  if (C % 4 == 0 && D % 4 == 0 && pr_plane_vec(A, 4) && pr_plane_vec(B, 4) && pr_plane_vec(Q, 4) && ((((uintptr_t)inp) & 15) == 0))
+  if (C % 4 == 0 && D % 4 == 0 && tp_planes_vec(Q, 4) && ((((uintptr_t)inp) & 15) == 0))
     vec = 4;
-  else if (C % 2 == 0 && D % 2 == 0 && pr_plane_vec(A, 2) && pr_plane_vec(B, 2) && pr_plane_vec(Q, 2) && ((((uintptr_t)inp) & 7) == 0))
+  else if (C % 2 == 0 && D % 2 == 0 && tp_planes_vec(Q, 2) && ((((uintptr_t)inp) & 7) == 0))
     vec = 2;
   const unsigned int per = (unsigned int)(M * (D / vec));
   const dim3 grid((unsigned int)dvgo_blocks(per, DVGO_BLOCK), 3u);
   if (vec == 4)
-    plane_rows_fwd_kernel<4><<<grid, DVGO_BLOCK, 0, st>>>(A, B, Q, TA, TB, TC, C, (int)D, P, xyz, xyz_min, xyz_max, (unsigned int)M, per, inp);
+    plane_rows_fwd_kernel<4><<<grid, DVGO_BLOCK, 0, st>>>(Q.a, Q.b, Q.c, TA, TB, TC, C, (int)D, P, xyz, xyz_min, xyz_max, (unsigned int)M, per, inp);
   else if (vec == 2)
-    plane_rows_fwd_kernel<2><<<grid, DVGO_BLOCK, 0, st>>>(A, B, Q, TA, TB, TC, C, (int)D, P, xyz, xyz_min, xyz_max, (unsigned int)M, per, inp);
+    plane_rows_fwd_kernel<2><<<grid, DVGO_BLOCK, 0, st>>>(Q.a, Q.b, Q.c, TA, TB, TC, C, (int)D, P, xyz, xyz_min, xyz_max, (unsigned int)M, per, inp);
   else
-    plane_rows_fwd_kernel<1><<<grid, DVGO_BLOCK, 0, st>>>(A, B, Q, TA, TB, TC, C, (int)D, P, xyz, xyz_min, xyz_max, (unsigned int)M, per, inp);
+    plane_rows_fwd_kernel<1><<<grid, DVGO_BLOCK, 0, st>>>(Q.a, Q.b, Q.c, TA, TB, TC, C, (int)D, P, xyz, xyz_min, xyz_max, (unsigned int)M, per, inp);
   DVGO_LAUNCH_CHECK();
   return 0;
 }
@@ -182,20 +147,18 @@ int dvgo_plane_rows_bwd(const float* grad_inp,
                         float* g_zx, int H_zx, int W_zx, int64_t sC_zx, int64_t sH_zx, int64_t sW_zx,
                         int C, const float* xyz, const float* xyz_min, const float* xyz_max, int64_t M,
                         int Wx, int Wy, int Wz, int P, int cell_decode, int run, void* stream) {
-  PR_PLANES(g_xy, g_yz, g_zx);
+  const TpPlanes Q = TP_PLANES(g_xy, g_yz, g_zx);
+  const int64_t D = pr_width(C, P, cell_decode);
   if (run < 0) return DVGO_EINVAL;
-  const int rc = pr_check(A, B, Q, C, xyz, xyz_min, xyz_max, M, Wx, Wy, Wz, P, grad_inp, D);
-  if (rc < 0) return rc;
-  if (rc == 1) return 0;
+  const int rc = pr_check(Q, C, M, Wx, Wy, Wz, P, xyz, xyz_min, xyz_max, grad_inp, D);
+  if (rc) return rc < 0 ? rc : 0;
   hipStream_t st = (hipStream_t)stream;
-  if (run == 0) run = TP_RUN_DEFAULT;
-  const int64_t nchunk = (M + run - 1) / run;
-  const int64_t total = nchunk * 3 * C;
-  const int blocks = dvgo_blocks(total, DVGO_BLOCK);
-  if (A.sC == 1 && B.sC == 1 && Q.sC == 1 && C > 1)
-    plane_rows_bwd_kernel<true><<<blocks, DVGO_BLOCK, 0, st>>>(A, B, Q, C, (int)D, grad_inp, xyz, xyz_min, xyz_max, M, run, nchunk, total);
+  const TpScatter S = tp_scatter(Q, C, M, run, TP_RUN_DEFAULT, 3 * C);
+  const int blocks = dvgo_blocks(S.lanes, DVGO_BLOCK);
+  if (S.cfast)
+    plane_rows_bwd_kernel<true><<<blocks, DVGO_BLOCK, 0, st>>>(Q.a, Q.b, Q.c, C, (int)D, grad_inp, xyz, xyz_min, xyz_max, M, S.run, S.nchunk, S.lanes);
   else
-    plane_rows_bwd_kernel<false><<<blocks, DVGO_BLOCK, 0, st>>>(A, B, Q, C, (int)D, grad_inp, xyz, xyz_min, xyz_max, M, run, nchunk, total);
+    plane_rows_bwd_kernel<false><<<blocks, DVGO_BLOCK, 0, st>>>(Q.a, Q.b, Q.c, C, (int)D, grad_inp, xyz, xyz_min, xyz_max, M, S.run, S.nchunk, S.lanes);
   DVGO_LAUNCH_CHECK();
   return 0;
 }

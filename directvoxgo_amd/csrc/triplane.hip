@@ -23,8 +23,6 @@
 #include "common.h"
 #include "plane2d.h"
 
-struct TpPlanes { TpPlane a, b, c; };
-
 // total = M * (SUM ? C : 3C) / VEC lanes (< 2^31: the entry checks M * 3C)
 template <int VEC, bool SUM>
 __global__ void __launch_bounds__(DVGO_BLOCK)
@@ -53,13 +51,7 @@ triplane_fwd_kernel(TpPlane PA, TpPlane PB, TpPlane PC, int C, const float* __re
     const TpPlane q = tp_pick(PA, PB, PC, (int)s, ah, aw);
     r = tp_sample<VEC>(q, ah, aw, c, xyz, mn, mx, m);
   }
-  float* o = out + (int64_t)tid * VEC;
-  if constexpr (VEC == 4) {
-    *reinterpret_cast<float4*>(o) = make_float4(r.v[0], r.v[1], r.v[2], r.v[3]);
-  } else {
-#pragma unroll
-    for (int i = 0; i < VEC; ++i) o[i] = r.v[i];
-  }
+  tp_store<VEC>(out + (int64_t)tid * VEC, r);
 }
 
 // total = nchunk * 3C lanes, nchunk = ceil(M / run).  CFAST: channel fastest (channels-last planes), else sample fastest.
@@ -72,26 +64,6 @@ triplane_bwd_kernel(TpPlane PA, TpPlane PB, TpPlane PC, int C, const float* __re
   tp_scatter_lane<CFAST>(PA, PB, PC, C, grad_out, gstride, sum ? 0 : C, xyz, mn, mx, M, run, nchunk, total);
 }
 
-static bool tp_plane_ok(const TpPlane& q) { return q.H >= 1 && q.W >= 1; }
-static bool tp_plane_vec(const TpPlane& q) {
-  return q.sC == 1 && (q.sH % 4 == 0 || q.H == 1) && (q.sW % 4 == 0 || q.W == 1) && ((((uintptr_t)q.p) & 15) == 0);
-}
-
-static int tp_check(const TpPlanes& P, int C, const void* xyz, const void* mn, const void* mx, int64_t M,
-                    const void* io) {
-  if (M < 0 || C < 0 || !tp_plane_ok(P.a) || !tp_plane_ok(P.b) || !tp_plane_ok(P.c)) return DVGO_EINVAL;
-  if (M == 0 || C == 0) return 1;   // nothing to do
-  if (!P.a.p || !P.b.p || !P.c.p || !xyz || !mn || !mx || !io) return DVGO_EINVAL;
-  if (!dvgo_fits(M * 3 * (int64_t)C)) return DVGO_ERANGE;
-  return 0;
-}
-
-#define TP_PLANES(px, py, pz)                                                                   \
-  TpPlanes P;                                                                                   \
-  P.a = TpPlane{const_cast<float*>(px), H_xy, W_xy, sC_xy, sH_xy, sW_xy};                       \
-  P.b = TpPlane{const_cast<float*>(py), H_yz, W_yz, sC_yz, sH_yz, sW_yz};                       \
-  P.c = TpPlane{const_cast<float*>(pz), H_zx, W_zx, sC_zx, sH_zx, sW_zx}
-
 extern "C" {
 
 int dvgo_triplane_fwd(const float* xy, int H_xy, int W_xy, int64_t sC_xy, int64_t sH_xy, int64_t sW_xy,
@@ -99,13 +71,11 @@ int dvgo_triplane_fwd(const float* xy, int H_xy, int W_xy, int64_t sC_xy, int64_
                       const float* zx, int H_zx, int W_zx, int64_t sC_zx, int64_t sH_zx, int64_t sW_zx,
                       int C, const float* xyz, const float* xyz_min, const float* xyz_max, int64_t M, int sum,
                       float* out, void* stream) {
-  TP_PLANES(xy, yz, zx);
-  const int rc = tp_check(P, C, xyz, xyz_min, xyz_max, M, out);
-  if (rc < 0) return rc;
-  if (rc == 1) return 0;
+  const TpPlanes P = TP_PLANES(xy, yz, zx);
+  const int rc = tp_check(P, C, M, true, xyz, xyz_min, xyz_max, {out}, 3, C);
+  if (rc) return rc < 0 ? rc : 0;
   hipStream_t st = (hipStream_t)stream;
-  const bool vec = (C % 4 == 0) && tp_plane_vec(P.a) && tp_plane_vec(P.b) && tp_plane_vec(P.c) &&
-                   ((((uintptr_t)out) & 15) == 0);
+  const bool vec = (C % 4 == 0) && tp_planes_vec(P, 4) && ((((uintptr_t)out) & 15) == 0);
   const int64_t width = sum ? C : 3 * (int64_t)C;
   const unsigned int total = (unsigned int)(M * width / (vec ? 4 : 1));
   const int blocks = dvgo_blocks(total, DVGO_BLOCK);
@@ -127,23 +97,20 @@ int dvgo_triplane_bwd(const float* grad_out,
                       float* g_zx, int H_zx, int W_zx, int64_t sC_zx, int64_t sH_zx, int64_t sW_zx,
                       int C, const float* xyz, const float* xyz_min, const float* xyz_max, int64_t M, int sum,
                       int run, void* stream) {
-  TP_PLANES(g_xy, g_yz, g_zx);
+  const TpPlanes P = TP_PLANES(g_xy, g_yz, g_zx);
   if (run < 0) return DVGO_EINVAL;
-  const int rc = tp_check(P, C, xyz, xyz_min, xyz_max, M, grad_out);
-  if (rc < 0) return rc;
-  if (rc == 1) return 0;
+  const int rc = tp_check(P, C, M, true, xyz, xyz_min, xyz_max, {grad_out}, 3, C);
+  if (rc) return rc < 0 ? rc : 0;
   hipStream_t st = (hipStream_t)stream;
-  if (run == 0) run = TP_RUN_DEFAULT;
-  const int64_t nchunk = (M + run - 1) / run;
-  const int64_t total = nchunk * 3 * C;
-  const int blocks = dvgo_blocks(total, DVGO_BLOCK);
+  const TpScatter S = tp_scatter(P, C, M, run, TP_RUN_DEFAULT, 3 * C);
+  const int blocks = dvgo_blocks(S.lanes, DVGO_BLOCK);
   const int gstride = sum ? C : 3 * C;
-  if (P.a.sC == 1 && P.b.sC == 1 && P.c.sC == 1 && C > 1)
-    triplane_bwd_kernel<true><<<blocks, DVGO_BLOCK, 0, st>>>(P.a, P.b, P.c, C, grad_out, gstride, sum, xyz, xyz_min, xyz_max, M, run,
-                                                             nchunk, total);
+  if (S.cfast)
+    triplane_bwd_kernel<true><<<blocks, DVGO_BLOCK, 0, st>>>(P.a, P.b, P.c, C, grad_out, gstride, sum, xyz, xyz_min, xyz_max, M, S.run,
+                                                             S.nchunk, S.lanes);
   else
-    triplane_bwd_kernel<false><<<blocks, DVGO_BLOCK, 0, st>>>(P.a, P.b, P.c, C, grad_out, gstride, sum, xyz, xyz_min, xyz_max, M, run,
-                                                              nchunk, total);
+    triplane_bwd_kernel<false><<<blocks, DVGO_BLOCK, 0, st>>>(P.a, P.b, P.c, C, grad_out, gstride, sum, xyz, xyz_min, xyz_max, M, S.run,
+                                                              S.nchunk, S.lanes);
   DVGO_LAUNCH_CHECK();
   return 0;
 }

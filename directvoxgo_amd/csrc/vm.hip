@@ -209,33 +209,21 @@ vm_bwd_kernel(TpPlane PA, TpPlane PB, TpPlane PC, VmLine LA, VmLine LB, VmLine L
   }
 }
 
-static bool vm_plane_ok(const TpPlane& q) { return q.H >= 1 && q.W >= 1; }
-static bool vm_plane_vec(const TpPlane& q) {
-  return q.sC == 1 && (q.sH % 4 == 0 || q.H == 1) && (q.sW % 4 == 0 || q.W == 1) && ((((uintptr_t)q.p) & 15) == 0);
-}
 static bool vm_line_vec(const VmLine& q) { return q.sC == 1 && (q.sN % 4 == 0 || q.N == 1) && ((((uintptr_t)q.p) & 15) == 0); }
 
-struct VmArgs { TpPlane pa, pb, pc; VmLine la, lb, lc; };
+struct VmLines { VmLine a, b, c; };
 
-// < 0: the error; 1: nothing to do; 0: launch
-static int vm_check(const VmArgs& A, int R, const void* xyz, const void* mn, const void* mx, int64_t M, const void* io) {
-  if (M < 0 || R < 0 || !vm_plane_ok(A.pa) || !vm_plane_ok(A.pb) || !vm_plane_ok(A.pc) || A.la.N < 1 || A.lb.N < 1 ||
-      A.lc.N < 1)
-    return DVGO_EINVAL;
-  if (M == 0 || R == 0) return 1;
-  if (!A.pa.p || !A.pb.p || !A.pc.p || !A.la.p || !A.lb.p || !A.lc.p || !xyz || !mn || !mx || !io) return DVGO_EINVAL;
-  if (!dvgo_fits(M * 3 * (int64_t)R)) return DVGO_ERANGE;
-  return 0;
+// the three lines of an entry point from its 12 line scalars
+#define VM_LINES()                                                      \
+  VmLines{VmLine{const_cast<float*>(l_xy), N_xy, lC_xy, lN_xy},         \
+          VmLine{const_cast<float*>(l_yz), N_yz, lC_yz, lN_yz},         \
+          VmLine{const_cast<float*>(l_zx), N_zx, lC_zx, lN_zx}}
+
+// tp_check with the lines' lengths among the shapes and their pointers among the pointers
+static int vm_check(const TpPlanes& P, const VmLines& L, int R, int64_t M, const void* xyz, const void* mn, const void* mx,
+                    const void* io) {
+  return tp_check(P, R, M, L.a.N >= 1 && L.b.N >= 1 && L.c.N >= 1, xyz, mn, mx, {L.a.p, L.b.p, L.c.p, io}, 3, R);
 }
-
-#define VM_ARGS()                                                                              \
-  VmArgs A;                                                                                    \
-  A.pa = TpPlane{const_cast<float*>(xy), H_xy, W_xy, sC_xy, sH_xy, sW_xy};                     \
-  A.pb = TpPlane{const_cast<float*>(yz), H_yz, W_yz, sC_yz, sH_yz, sW_yz};                     \
-  A.pc = TpPlane{const_cast<float*>(zx), H_zx, W_zx, sC_zx, sH_zx, sW_zx};                     \
-  A.la = VmLine{const_cast<float*>(l_xy), N_xy, lC_xy, lN_xy};                                 \
-  A.lb = VmLine{const_cast<float*>(l_yz), N_yz, lC_yz, lN_yz};                                 \
-  A.lc = VmLine{const_cast<float*>(l_zx), N_zx, lC_zx, lN_zx}
 
 extern "C" {
 
@@ -246,19 +234,19 @@ int dvgo_vm_fwd(const float* xy, int H_xy, int W_xy, int64_t sC_xy, int64_t sH_x
                 const float* l_yz, int N_yz, int64_t lC_yz, int64_t lN_yz,
                 const float* l_zx, int N_zx, int64_t lC_zx, int64_t lN_zx,
                 int R, const float* xyz, const float* xyz_min, const float* xyz_max, int64_t M, float* out, void* stream) {
-  VM_ARGS();
-  const int rc = vm_check(A, R, xyz, xyz_min, xyz_max, M, out);
-  if (rc < 0) return rc;
-  if (rc == 1) return 0;
+  const TpPlanes P = TP_PLANES(xy, yz, zx);
+  const VmLines L = VM_LINES();
+  const int rc = vm_check(P, L, R, M, xyz, xyz_min, xyz_max, out);
+  if (rc) return rc < 0 ? rc : 0;
   hipStream_t st = (hipStream_t)stream;
-  const bool vec = (R % 4 == 0) && vm_plane_vec(A.pa) && vm_plane_vec(A.pb) && vm_plane_vec(A.pc) && vm_line_vec(A.la) &&
-                   vm_line_vec(A.lb) && vm_line_vec(A.lc) && ((((uintptr_t)out) & 15) == 0);
+  const bool vec = (R % 4 == 0) && tp_planes_vec(P, 4) && vm_line_vec(L.a) && vm_line_vec(L.b) && vm_line_vec(L.c) &&
+                   ((((uintptr_t)out) & 15) == 0);
   const unsigned int total = (unsigned int)(M * 3 * (int64_t)R / (vec ? 4 : 1));
   const int blocks = dvgo_blocks(total, DVGO_BLOCK);
   if (vec)
-    vm_fwd_kernel<4><<<blocks, DVGO_BLOCK, 0, st>>>(A.pa, A.pb, A.pc, A.la, A.lb, A.lc, R, xyz, xyz_min, xyz_max, total, out);
+    vm_fwd_kernel<4><<<blocks, DVGO_BLOCK, 0, st>>>(P.a, P.b, P.c, L.a, L.b, L.c, R, xyz, xyz_min, xyz_max, total, out);
   else
-    vm_fwd_kernel<1><<<blocks, DVGO_BLOCK, 0, st>>>(A.pa, A.pb, A.pc, A.la, A.lb, A.lc, R, xyz, xyz_min, xyz_max, total, out);
+    vm_fwd_kernel<1><<<blocks, DVGO_BLOCK, 0, st>>>(P.a, P.b, P.c, L.a, L.b, L.c, R, xyz, xyz_min, xyz_max, total, out);
   DVGO_LAUNCH_CHECK();
   return 0;
 }
@@ -273,29 +261,27 @@ int dvgo_vm_bwd(const float* grad_out,
                 float* g_xy, float* g_yz, float* g_zx, float* gl_xy, float* gl_yz, float* gl_zx,
                 int R, const float* xyz, const float* xyz_min, const float* xyz_max, int64_t M, int run, int mode,
                 void* stream) {
-  VM_ARGS();
+  const TpPlanes P = TP_PLANES(xy, yz, zx);
+  const VmLines L = VM_LINES();
   if (run < 0 || mode < 0 || mode > 2) return DVGO_EINVAL;
-  const int rc = vm_check(A, R, xyz, xyz_min, xyz_max, M, grad_out);
-  if (rc < 0) return rc;
-  if (rc == 1) return 0;
+  const int rc = vm_check(P, L, R, M, xyz, xyz_min, xyz_max, grad_out);
+  if (rc) return rc < 0 ? rc : 0;
   if (!g_xy || !g_yz || !g_zx || !gl_xy || !gl_yz || !gl_zx) return DVGO_EINVAL;
   const int64_t tab_bytes = ((int64_t)N_xy + N_yz + N_zx) * R * (int64_t)sizeof(float);
   if (mode == 2 && tab_bytes > VM_LDS_BYTES) return DVGO_EINVAL;
   if (mode == 0) mode = (VM_MODE_DEFAULT == 2 && tab_bytes <= VM_LDS_BYTES) ? 2 : 1;
   hipStream_t st = (hipStream_t)stream;
-  if (run == 0) run = VM_RUN_DEFAULT;
-  const int64_t nchunk = (M + run - 1) / run;
-  const int64_t total = nchunk * 3 * R;
+  const TpScatter S = tp_scatter(P, R, M, run, VM_RUN_DEFAULT, 3 * R);
   const VmGrads GP{g_xy, g_yz, g_zx}, GL{gl_xy, gl_yz, gl_zx};
-  const bool cfast = A.pa.sC == 1 && A.pb.sC == 1 && A.pc.sC == 1 && A.la.sC == 1 && A.lb.sC == 1 && A.lc.sC == 1 && R > 1;
-  int64_t blocks = dvgo_blocks(total, DVGO_BLOCK), share = DVGO_BLOCK;
+  const bool cfast = S.cfast && L.a.sC == 1 && L.b.sC == 1 && L.c.sC == 1;          // the lines channels-last as well
+  int64_t blocks = dvgo_blocks(S.lanes, DVGO_BLOCK), share = DVGO_BLOCK;
   if (mode == 2 && blocks > VM_LDS_GRID) {
     share = ((blocks + VM_LDS_GRID - 1) / VM_LDS_GRID) * DVGO_BLOCK;
-    blocks = (total + share - 1) / share;
+    blocks = (S.lanes + share - 1) / share;
   }
 #define VM_LAUNCH(CF, LDS, bytes)                                                                                          \
-  vm_bwd_kernel<CF, LDS><<<(int)blocks, DVGO_BLOCK, bytes, st>>>(A.pa, A.pb, A.pc, A.la, A.lb, A.lc, GP, GL, R, grad_out, xyz, \
-                                                                 xyz_min, xyz_max, M, run, nchunk, total, share)
+  vm_bwd_kernel<CF, LDS><<<(int)blocks, DVGO_BLOCK, bytes, st>>>(P.a, P.b, P.c, L.a, L.b, L.c, GP, GL, R, grad_out, xyz,   \
+                                                                 xyz_min, xyz_max, M, S.run, S.nchunk, S.lanes, share)
   if (mode == 2) {
     if (cfast) VM_LAUNCH(true, true, (size_t)tab_bytes); else VM_LAUNCH(false, true, (size_t)tab_bytes);
   } else {

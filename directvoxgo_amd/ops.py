@@ -29,7 +29,7 @@ import torch.nn.functional as F
 
 from . import _lib as L
 from . import render_utils as render_utils_hip
-from ._lib import _flt, _i64, _int, check_f32, check_input, ptr, stream_of
+from ._lib import check_f32, check_input, stream_of
 
 
 class Raw2Alpha(torch.autograd.Function):
@@ -92,8 +92,7 @@ class _GridSample(torch.autograd.Function):
         M = xyz.shape[0]
         out = torch.empty((M, C), dtype=torch.float32, device=xyz.device)
         with L.device_of(xyz):
-            L.call('dvgo_grid_sample_fwd', ptr(grid), _int(C), _int(X), _int(Y), _int(Z), _i64(sC), _i64(sX),
-                   _i64(sY), _i64(sZ), ptr(xyz), ptr(xyz_min), ptr(xyz_max), _i64(M), ptr(out), stream_of(xyz))
+            L.call('dvgo_grid_sample_fwd', grid, C, X, Y, Z, sC, sX, sY, sZ, xyz, xyz_min, xyz_max, M, out, stream_of(xyz))
         if ctx.needs_input_grad[1]:       # the position gradient reads the grid's values, not only its geometry
             ctx.save_for_backward(xyz, xyz_min, xyz_max, grid)
         else:
@@ -106,25 +105,22 @@ class _GridSample(torch.autograd.Function):
     @torch.autograd.function.once_differentiable
     def backward(ctx, grad_out):
         xyz, xyz_min, xyz_max = ctx.saved_tensors[:3]
-        C, X, Y, Z, sC, sX, sY, sZ = ctx.geom
         grad_grid = grad_xyz = None
         if ctx.needs_input_grad[1]:
             grid = ctx.saved_tensors[3]
             grad_out = grad_out.contiguous()
             grad_xyz = torch.empty_like(xyz)                 # every row is written by the kernel
             with L.device_of(xyz):
-                L.call('dvgo_grid_sample_bwd_xyz', ptr(grid), _int(C), _int(X), _int(Y), _int(Z), _i64(sC), _i64(sX),
-                       _i64(sY), _i64(sZ), ptr(grad_out), ptr(xyz), ptr(xyz_min), ptr(xyz_max), _i64(xyz.shape[0]),
-                       ptr(grad_xyz), stream_of(xyz))
+                L.call('dvgo_grid_sample_bwd_xyz', grid, *ctx.geom, grad_out, xyz, xyz_min, xyz_max, xyz.shape[0], grad_xyz,
+                       stream_of(xyz))
         if ctx.needs_input_grad[0]:
             grad_out = grad_out.contiguous()
             # zero-filled, same strides as the parameter (F.grid_sample's backward does the same)
             grad_grid = torch.zeros_like(ctx.grid_meta, memory_format=torch.preserve_format)
             assert grad_grid.stride() == ctx.grid_meta.stride()
             with L.device_of(xyz):
-                L.call('dvgo_grid_sample_bwd', ptr(grad_out), _int(C), _int(X), _int(Y), _int(Z), _i64(sC),
-                       _i64(sX), _i64(sY), _i64(sZ), ptr(xyz), ptr(xyz_min), ptr(xyz_max), _i64(xyz.shape[0]),
-                       ptr(grad_grid), stream_of(xyz))
+                L.call('dvgo_grid_sample_bwd', grad_out, *ctx.geom, xyz, xyz_min, xyz_max, xyz.shape[0], grad_grid,
+                       stream_of(xyz))
         return grad_grid, grad_xyz, None, None
 
 
@@ -146,7 +142,8 @@ PLANE_KEYS = ('xy', 'yz', 'zx')
 # Planes that are not channels-last are handed to the kernels as channels-last copies (and their gradients scattered
 # into channels-last buffers) once the samples outnumber the largest plane's texels: the copies are three passes over a
 # few MB, and the kernels' 16-byte texel loads and contiguous atomic runs need that layout.  Below it the kernels run on
-# the strides as given (they take either layout); tests set it to run a given layout through them.
+# the strides as given (they take either layout).  False keeps them on the given strides at every size
+# (tests/test_gpu_plane_ops.py runs the strided branch that way).
 TRIPLANE_RELAYOUT = True
 
 
@@ -171,22 +168,58 @@ def _plane_list(planes):
     return planes
 
 
-def triplane_fwd(planes, xyz, xyz_min, xyz_max, aggregation='concat'):
-    """dvgo_triplane_fwd on the planes' strides as they are: xyz [M,3] -> [M,3C] (concat) or [M,C] (sum).  No autograd."""
+def _plane_pack(planes):
+    """the three planes -> the flat [tensor, H, W, sC, sH, sW] * 3 every plane entry point of the library takes"""
+    pack = []
+    for p, k in zip(planes, PLANE_KEYS):
+        pack += [p, *_plane_geom(p, k)]
+    return pack
+
+
+def _check_aggregation(aggregation):
     if aggregation not in ('concat', 'sum'):
         raise ValueError(f"aggregation must be 'concat' or 'sum', got {aggregation!r}")
+
+
+def _is_channels_last(p):
+    return p.stride(1) == 1 or p.shape[1] == 1
+
+
+def _kernel_tensors(ctx, tensors, M):
+    """The forward half of the plane ops' autograd functions: the relayout rule (TRIPLANE_RELAYOUT), keyed on the three
+    planes that lead `tensors`, for M samples.  Records on ctx which tensors the kernel gets as channels-last copies
+    (ctx.relayout) and the tensors themselves (ctx.meta), and returns what the kernel gets."""
+    relayout = TRIPLANE_RELAYOUT and M >= max(p.shape[2] * p.shape[3] for p in tensors[:3])
+    ctx.relayout = [relayout and not _is_channels_last(t) for t in tensors]
+    ctx.meta = tensors
+    return [t.contiguous(memory_format=torch.channels_last) if r else t for t, r in zip(tensors, ctx.relayout)]
+
+
+def _scatter_grads(ctx, needs, scatter):
+    """The backward half: zero-filled buffers with the strides of each tensor of ctx.meta (or channels-last where the kernel
+    was handed a copy), `scatter(buffers)` -- one launch into all of them, so a tensor that wants no gradient still gets a
+    buffer -- and None for the tensors that `needs` says want none."""
+    if not any(needs):
+        return [None] * len(needs)
+    grads = [torch.zeros_like(t, memory_format=torch.channels_last if r else torch.preserve_format)
+             for t, r in zip(ctx.meta, ctx.relayout)]
+    scatter(grads)
+    return [g if need else None for g, need in zip(grads, needs)]
+
+
+def triplane_fwd(planes, xyz, xyz_min, xyz_max, aggregation='concat'):
+    """dvgo_triplane_fwd on the planes' strides as they are: xyz [M,3] -> [M,3C] (concat) or [M,C] (sum).  No autograd."""
+    _check_aggregation(aggregation)
     planes = _plane_list(planes)
-    geoms = [_plane_geom(p, k) for p, k in zip(planes, PLANE_KEYS)]
+    pack = _plane_pack(planes)
     C = planes[0].shape[1]
     if any(p.shape[1] != C for p in planes):
         raise RuntimeError('the three planes must share their channel count')
     check_input(xyz, 'xyz'); check_f32(xyz, 'xyz')
     M = xyz.shape[0]
     out = torch.empty((M, C if aggregation == 'sum' else 3 * C), dtype=torch.float32, device=xyz.device)
-    (Ha, Wa, ca, ha, wa), (Hb, Wb, cb, hb, wb), (Hc, Wc, cc, hc, wc) = geoms
     with L.device_of(xyz):
-        L.call('dvgo_triplane_fwd', planes[0], Ha, Wa, ca, ha, wa, planes[1], Hb, Wb, cb, hb, wb, planes[2], Hc, Wc, cc, hc, wc,
-               C, xyz, xyz_min, xyz_max, M, 1 if aggregation == 'sum' else 0, out, stream_of(xyz))
+        L.call('dvgo_triplane_fwd', *pack, C, xyz, xyz_min, xyz_max, M, 1 if aggregation == 'sum' else 0, out, stream_of(xyz))
     return out
 
 
@@ -194,34 +227,23 @@ def triplane_bwd(grad_out, grads, xyz, xyz_min, xyz_max, aggregation='concat', r
     """dvgo_triplane_bwd: accumulates into the three buffers `grads` (shaped and strided like planes) in place.
     `run`: samples a lane merges before its atomics (0: the library's default)."""
     grads = _plane_list(grads)
-    geoms = [_plane_geom(p, k) for p, k in zip(grads, PLANE_KEYS)]
+    pack = _plane_pack(grads)
     C = grads[0].shape[1]
     check_input(grad_out, 'grad_out'); check_f32(grad_out, 'grad_out')
     M = xyz.shape[0]
     if tuple(grad_out.shape) != (M, C if aggregation == 'sum' else 3 * C):
         raise RuntimeError('grad_out has the wrong shape')
-    (Ha, Wa, ca, ha, wa), (Hb, Wb, cb, hb, wb), (Hc, Wc, cc, hc, wc) = geoms
     with L.device_of(xyz):
-        L.call('dvgo_triplane_bwd', grad_out, grads[0], Ha, Wa, ca, ha, wa, grads[1], Hb, Wb, cb, hb, wb, grads[2], Hc, Wc, cc,
-               hc, wc, C, xyz, xyz_min, xyz_max, M, 1 if aggregation == 'sum' else 0, int(run), stream_of(xyz))
+        L.call('dvgo_triplane_bwd', grad_out, *pack, C, xyz, xyz_min, xyz_max, M, 1 if aggregation == 'sum' else 0, int(run),
+               stream_of(xyz))
     return grads
-
-
-def _is_channels_last(p):
-    return p.stride(1) == 1 or p.shape[1] == 1
 
 
 class _TriPlaneSample(torch.autograd.Function):
     @staticmethod
     def forward(ctx, xy, yz, zx, xyz, xyz_min, xyz_max, aggregation):
-        planes = [xy, yz, zx]
-        M = xyz.shape[0]
-        relayout = TRIPLANE_RELAYOUT and M >= max(p.shape[2] * p.shape[3] for p in planes)
-        ctx.relayout = [relayout and not _is_channels_last(p) for p in planes]
-        kp = [p.contiguous(memory_format=torch.channels_last) if r else p for p, r in zip(planes, ctx.relayout)]
-        out = triplane_fwd(kp, xyz, xyz_min, xyz_max, aggregation)
+        out = triplane_fwd(_kernel_tensors(ctx, [xy, yz, zx], xyz.shape[0]), xyz, xyz_min, xyz_max, aggregation)
         ctx.save_for_backward(xyz, xyz_min, xyz_max)
-        ctx.meta = planes
         ctx.aggregation = aggregation
         return out
 
@@ -229,15 +251,9 @@ class _TriPlaneSample(torch.autograd.Function):
     @torch.autograd.function.once_differentiable
     def backward(ctx, grad_out):
         xyz, xyz_min, xyz_max = ctx.saved_tensors
-        grads = [None, None, None]
-        if any(ctx.needs_input_grad[:3]):
-            # zero-filled, with the strides of the plane (or channels-last where the kernel was handed a copy); a plane
-            # that wants no gradient still gets a buffer: the launch scatters into all three
-            grads = [torch.zeros_like(p, memory_format=torch.channels_last if r else torch.preserve_format)
-                     for p, r in zip(ctx.meta, ctx.relayout)]
-            triplane_bwd(grad_out.contiguous(), grads, xyz, xyz_min, xyz_max, ctx.aggregation)
-            grads = [g if need else None for g, need in zip(grads, ctx.needs_input_grad[:3])]
-        return grads[0], grads[1], grads[2], None, None, None, None
+        grads = _scatter_grads(ctx, ctx.needs_input_grad[:3],
+                               lambda g: triplane_bwd(grad_out.contiguous(), g, xyz, xyz_min, xyz_max, ctx.aggregation))
+        return (*grads, None, None, None, None)
 
 
 def triplane_sample(planes, xyz, xyz_min, xyz_max, aggregation='concat'):
@@ -246,8 +262,7 @@ def triplane_sample(planes, xyz, xyz_min, xyz_max, aggregation='concat'):
     coordinates -> [...,3C] ('concat': xy, yz, zx) or [...,C] ('sum': (xy + yz) + zx).  Plane xy has its rows along world
     y and its columns along z, yz rows x / columns y, zx rows z / columns x (the reference's flipped ind_norm).
     Differentiable w.r.t. the planes only."""
-    if aggregation not in ('concat', 'sum'):
-        raise ValueError(f"aggregation must be 'concat' or 'sum', got {aggregation!r}")
+    _check_aggregation(aggregation)
     xy, yz, zx = _plane_list(planes)
     for p, k in zip((xy, yz, zx), PLANE_KEYS):
         _plane_geom(p, k)
@@ -274,9 +289,7 @@ def _vm_args(planes, lines, xyz):
     R = planes[0].shape[1]
     if any(t.dim() != 4 or t.shape[1] != R for t in planes + lines):
         raise RuntimeError('the three planes [1,R,H,W] and the three lines [1,R,N,1] must share their component count')
-    geom = []
-    for p, k in zip(planes, PLANE_KEYS):
-        geom += [p, *_plane_geom(p, k)]
+    geom = _plane_pack(planes)
     for ln, k in zip(lines, PLANE_KEYS):
         geom += [ln, *_line_geom(ln, k + '_line')]
     check_input(xyz, 'xyz'); check_f32(xyz, 'xyz')
@@ -317,26 +330,17 @@ def vm_bwd(grad_out, planes, lines, grad_planes, grad_lines, xyz, xyz_min, xyz_m
 class _VMSample(torch.autograd.Function):
     @staticmethod
     def forward(ctx, xyz, xyz_min, xyz_max, *tensors):
-        M = xyz.shape[0]
-        relayout = TRIPLANE_RELAYOUT and M >= max(p.shape[2] * p.shape[3] for p in tensors[:3])
-        ctx.relayout = [relayout and not _is_channels_last(t) for t in tensors]
-        kt = [t.contiguous(memory_format=torch.channels_last) if r else t for t, r in zip(tensors, ctx.relayout)]
+        kt = _kernel_tensors(ctx, tensors, xyz.shape[0])           # the rule looks at the three planes only
         out = vm_fwd(kt[:3], kt[3:], xyz, xyz_min, xyz_max)
         ctx.save_for_backward(xyz, xyz_min, xyz_max, *kt)          # the gradient of a product reads the other factor
-        ctx.meta = tensors
         return out
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, grad_out):
         xyz, xyz_min, xyz_max, *kt = ctx.saved_tensors
-        grads = [None] * 6
-        if any(ctx.needs_input_grad[3:]):
-            # as _TriPlaneSample.backward: zero-filled buffers with the strides the kernel saw, one launch into all six
-            grads = [torch.zeros_like(t, memory_format=torch.channels_last if r else torch.preserve_format)
-                     for t, r in zip(ctx.meta, ctx.relayout)]
-            vm_bwd(grad_out.contiguous(), kt[:3], kt[3:], grads[:3], grads[3:], xyz, xyz_min, xyz_max)
-            grads = [g if need else None for g, need in zip(grads, ctx.needs_input_grad[3:])]
+        grads = _scatter_grads(ctx, ctx.needs_input_grad[3:],
+                               lambda g: vm_bwd(grad_out.contiguous(), kt[:3], kt[3:], g[:3], g[3:], xyz, xyz_min, xyz_max))
         return (None, None, None, *grads)
 
 
@@ -463,9 +467,9 @@ def hash_sample(table, xyz, xyz_min, xyz_max, res, offsets=None):
 
 # ---------------------------------------------------------------------------------------------- LIIF plane decoder
 def _liif_args(planes, xyz, world_size):
-    """-> (planes, the 15 plane-geometry scalars in call order split per plane, C, M, (Wx, Wy, Wz))"""
+    """-> (planes, their _plane_pack, C, M, (Wx, Wy, Wz))"""
     planes = _plane_list(planes)
-    geoms = [_plane_geom(p, k) for p, k in zip(planes, PLANE_KEYS)]
+    pack = _plane_pack(planes)
     C = planes[0].shape[1]
     if any(p.shape[1] != C for p in planes):
         raise RuntimeError('the three planes must share their channel count')
@@ -475,37 +479,33 @@ def _liif_args(planes, xyz, world_size):
     ws = tuple(int(v) for v in world_size)
     if len(ws) != 3 or min(ws) < 1:
         raise ValueError(f'world_size must be three extents >= 1, got {ws}')
-    return planes, geoms, C, xyz.shape[0], ws
+    return planes, pack, C, xyz.shape[0], ws
 
 
 def liif_gather_fwd(planes, xyz, xyz_min, xyz_max, world_size, cell_decode=True, local_ensemble=True):
     """dvgo_liif_gather on the planes' strides as they are: xyz [M,3] -> inp [3,E,M,D], wgt [3,E,M] (E = 4 with
     local_ensemble, else 1; D = C + 4 with cell_decode, else C + 2).  No autograd."""
-    planes, geoms, C, M, (Wx, Wy, Wz) = _liif_args(planes, xyz, world_size)
+    planes, pack, C, M, ws = _liif_args(planes, xyz, world_size)
     E, D = (4 if local_ensemble else 1), C + (4 if cell_decode else 2)
     inp = torch.empty((3, E, M, D), dtype=torch.float32, device=xyz.device)
     wgt = torch.empty((3, E, M), dtype=torch.float32, device=xyz.device)
-    (Ha, Wa, ca, ha, wa), (Hb, Wb, cb, hb, wb), (Hc, Wc, cc, hc, wc) = geoms
     with L.device_of(xyz):
-        L.call('dvgo_liif_gather', planes[0], Ha, Wa, ca, ha, wa, planes[1], Hb, Wb, cb, hb, wb, planes[2], Hc, Wc, cc, hc, wc,
-               C, xyz, xyz_min, xyz_max, M, Wx, Wy, Wz, int(bool(cell_decode)), int(bool(local_ensemble)), inp, wgt,
-               stream_of(xyz))
+        L.call('dvgo_liif_gather', *pack, C, xyz, xyz_min, xyz_max, M, *ws, int(bool(cell_decode)), int(bool(local_ensemble)),
+               inp, wgt, stream_of(xyz))
     return inp, wgt
 
 
 def liif_gather_bwd(grad_inp, grads, xyz, xyz_min, xyz_max, world_size, cell_decode=True, local_ensemble=True, run=0):
     """dvgo_liif_scatter: accumulates the first C columns of grad_inp [3,E,M,D] into the three buffers `grads` (shaped
     and strided like planes) in place.  `run`: samples a lane merges before its atomic (0: the library's default)."""
-    grads, geoms, C, M, (Wx, Wy, Wz) = _liif_args(grads, xyz, world_size)
+    grads, pack, C, M, ws = _liif_args(grads, xyz, world_size)
     E, D = (4 if local_ensemble else 1), C + (4 if cell_decode else 2)
     check_input(grad_inp, 'grad_inp'); check_f32(grad_inp, 'grad_inp')
     if tuple(grad_inp.shape) != (3, E, M, D):
         raise RuntimeError('grad_inp has the wrong shape')
-    (Ha, Wa, ca, ha, wa), (Hb, Wb, cb, hb, wb), (Hc, Wc, cc, hc, wc) = geoms
     with L.device_of(xyz):
-        L.call('dvgo_liif_scatter', grad_inp, grads[0], Ha, Wa, ca, ha, wa, grads[1], Hb, Wb, cb, hb, wb, grads[2], Hc, Wc, cc,
-               hc, wc, C, xyz, xyz_min, xyz_max, M, Wx, Wy, Wz, int(bool(cell_decode)), int(bool(local_ensemble)), int(run),
-               stream_of(xyz))
+        L.call('dvgo_liif_scatter', grad_inp, *pack, C, xyz, xyz_min, xyz_max, M, *ws, int(bool(cell_decode)),
+               int(bool(local_ensemble)), int(run), stream_of(xyz))
     return grads
 
 
@@ -518,8 +518,7 @@ def _blend_shape(pred, wgt):
 
 def liif_blend_fwd(pred, wgt, aggregation='concat'):
     """dvgo_liif_blend_fwd: pred [3,E,M,C], wgt [3,E,M] -> [M,3C] (concat) or [M,C] (sum).  No autograd."""
-    if aggregation not in ('concat', 'sum'):
-        raise ValueError(f"aggregation must be 'concat' or 'sum', got {aggregation!r}")
+    _check_aggregation(aggregation)
     E, M, C = _blend_shape(pred, wgt)
     out = torch.empty((M, C if aggregation == 'sum' else 3 * C), dtype=torch.float32, device=pred.device)
     with L.device_of(pred):
@@ -542,14 +541,9 @@ def liif_blend_bwd(grad_out, wgt, C, aggregation='concat'):
 class _LiifGather(torch.autograd.Function):
     @staticmethod
     def forward(ctx, xy, yz, zx, xyz, xyz_min, xyz_max, world_size, cell_decode, local_ensemble):
-        planes = [xy, yz, zx]
-        M = xyz.shape[0]
-        relayout = TRIPLANE_RELAYOUT and M >= max(p.shape[2] * p.shape[3] for p in planes)
-        ctx.relayout = [relayout and not _is_channels_last(p) for p in planes]
-        kp = [p.contiguous(memory_format=torch.channels_last) if r else p for p, r in zip(planes, ctx.relayout)]
-        inp, wgt = liif_gather_fwd(kp, xyz, xyz_min, xyz_max, world_size, cell_decode, local_ensemble)
+        inp, wgt = liif_gather_fwd(_kernel_tensors(ctx, [xy, yz, zx], xyz.shape[0]), xyz, xyz_min, xyz_max, world_size, cell_decode,
+                                   local_ensemble)
         ctx.save_for_backward(xyz, xyz_min, xyz_max)
-        ctx.meta = planes
         ctx.geometry = (world_size, cell_decode, local_ensemble)
         ctx.mark_non_differentiable(wgt)
         return inp, wgt
@@ -558,14 +552,9 @@ class _LiifGather(torch.autograd.Function):
     @torch.autograd.function.once_differentiable
     def backward(ctx, grad_inp, _grad_wgt):
         xyz, xyz_min, xyz_max = ctx.saved_tensors
-        grads = [None, None, None]
-        if any(ctx.needs_input_grad[:3]):
-            # as _TriPlaneSample.backward: zero-filled buffers with the strides the kernel saw, one launch into all three
-            grads = [torch.zeros_like(p, memory_format=torch.channels_last if r else torch.preserve_format)
-                     for p, r in zip(ctx.meta, ctx.relayout)]
-            liif_gather_bwd(grad_inp.contiguous(), grads, xyz, xyz_min, xyz_max, *ctx.geometry)
-            grads = [g if need else None for g, need in zip(grads, ctx.needs_input_grad[:3])]
-        return grads[0], grads[1], grads[2], None, None, None, None, None, None
+        grads = _scatter_grads(ctx, ctx.needs_input_grad[:3],
+                               lambda g: liif_gather_bwd(grad_inp.contiguous(), g, xyz, xyz_min, xyz_max, *ctx.geometry))
+        return (*grads, None, None, None, None, None, None)
 
 
 class _LiifBlend(torch.autograd.Function):
@@ -598,8 +587,7 @@ def liif_gather(planes, xyz, xyz_min, xyz_max, world_size, cell_decode=True, loc
 def liif_blend(pred, wgt, aggregation='concat'):
     """pred [3,E,M,C] blended over the shifts by wgt [3,E,M] and aggregated over the planes: [M,3C] ('concat') or [M,C]
     ('sum': (xy + yz) + zx).  Differentiable w.r.t. pred only."""
-    if aggregation not in ('concat', 'sum'):
-        raise ValueError(f"aggregation must be 'concat' or 'sum', got {aggregation!r}")
+    _check_aggregation(aggregation)
     return _LiifBlend.apply(pred.contiguous(), wgt, aggregation)
 
 
@@ -624,42 +612,33 @@ def _rows_width(C, n_freq, cell_decode):
 def plane_rows_fwd(planes, xyz, xyz_min, xyz_max, world_size, n_freq, cell_decode=True):
     """dvgo_plane_rows_fwd on the planes' strides as they are: xyz [M,3] -> inp [3,M,D], D = C + 2 + 4 * n_freq (+ 2 with
     cell_decode).  No autograd."""
-    planes, geoms, C, M, (Wx, Wy, Wz) = _liif_args(planes, xyz, world_size)
+    planes, pack, C, M, ws = _liif_args(planes, xyz, world_size)
     P, D = _rows_width(C, n_freq, cell_decode)
     inp = torch.empty((3, M, D), dtype=torch.float32, device=xyz.device)
-    (Ha, Wa, ca, ha, wa), (Hb, Wb, cb, hb, wb), (Hc, Wc, cc, hc, wc) = geoms
     with L.device_of(xyz):
-        L.call('dvgo_plane_rows_fwd', planes[0], Ha, Wa, ca, ha, wa, planes[1], Hb, Wb, cb, hb, wb, planes[2], Hc, Wc, cc, hc, wc,
-               C, xyz, xyz_min, xyz_max, M, Wx, Wy, Wz, P, int(bool(cell_decode)), inp, stream_of(xyz))
+        L.call('dvgo_plane_rows_fwd', *pack, C, xyz, xyz_min, xyz_max, M, *ws, P, int(bool(cell_decode)), inp, stream_of(xyz))
     return inp
 
 
 def plane_rows_bwd(grad_inp, grads, xyz, xyz_min, xyz_max, world_size, n_freq, cell_decode=True, run=0):
     """dvgo_plane_rows_bwd: accumulates w * (the first C columns of grad_inp [3,M,D]) into the three buffers `grads` (shaped
     and strided like planes) in place.  `run`: samples a lane merges before its atomics (0: the library's default)."""
-    grads, geoms, C, M, (Wx, Wy, Wz) = _liif_args(grads, xyz, world_size)
+    grads, pack, C, M, ws = _liif_args(grads, xyz, world_size)
     P, D = _rows_width(C, n_freq, cell_decode)
     check_input(grad_inp, 'grad_inp'); check_f32(grad_inp, 'grad_inp')
     if tuple(grad_inp.shape) != (3, M, D):
         raise RuntimeError('grad_inp has the wrong shape')
-    (Ha, Wa, ca, ha, wa), (Hb, Wb, cb, hb, wb), (Hc, Wc, cc, hc, wc) = geoms
     with L.device_of(xyz):
-        L.call('dvgo_plane_rows_bwd', grad_inp, grads[0], Ha, Wa, ca, ha, wa, grads[1], Hb, Wb, cb, hb, wb, grads[2], Hc, Wc, cc,
-               hc, wc, C, xyz, xyz_min, xyz_max, M, Wx, Wy, Wz, P, int(bool(cell_decode)), int(run), stream_of(xyz))
+        L.call('dvgo_plane_rows_bwd', grad_inp, *pack, C, xyz, xyz_min, xyz_max, M, *ws, P, int(bool(cell_decode)), int(run),
+               stream_of(xyz))
     return grads
 
 
 class _PlaneRows(torch.autograd.Function):
     @staticmethod
     def forward(ctx, xy, yz, zx, xyz, xyz_min, xyz_max, world_size, n_freq, cell_decode):
-        planes = [xy, yz, zx]
-        M = xyz.shape[0]
-        relayout = TRIPLANE_RELAYOUT and M >= max(p.shape[2] * p.shape[3] for p in planes)
-        ctx.relayout = [relayout and not _is_channels_last(p) for p in planes]
-        kp = [p.contiguous(memory_format=torch.channels_last) if r else p for p, r in zip(planes, ctx.relayout)]
-        inp = plane_rows_fwd(kp, xyz, xyz_min, xyz_max, world_size, n_freq, cell_decode)
+        inp = plane_rows_fwd(_kernel_tensors(ctx, [xy, yz, zx], xyz.shape[0]), xyz, xyz_min, xyz_max, world_size, n_freq, cell_decode)
         ctx.save_for_backward(xyz, xyz_min, xyz_max)
-        ctx.meta = planes
         ctx.geometry = (world_size, n_freq, cell_decode)
         return inp
 
@@ -667,14 +646,9 @@ class _PlaneRows(torch.autograd.Function):
     @torch.autograd.function.once_differentiable
     def backward(ctx, grad_inp):
         xyz, xyz_min, xyz_max = ctx.saved_tensors
-        grads = [None, None, None]
-        if any(ctx.needs_input_grad[:3]):
-            # as _TriPlaneSample.backward: zero-filled buffers with the strides the kernel saw, one launch into all three
-            grads = [torch.zeros_like(p, memory_format=torch.channels_last if r else torch.preserve_format)
-                     for p, r in zip(ctx.meta, ctx.relayout)]
-            plane_rows_bwd(grad_inp.contiguous(), grads, xyz, xyz_min, xyz_max, *ctx.geometry)
-            grads = [g if need else None for g, need in zip(grads, ctx.needs_input_grad[:3])]
-        return grads[0], grads[1], grads[2], None, None, None, None, None, None
+        grads = _scatter_grads(ctx, ctx.needs_input_grad[:3],
+                               lambda g: plane_rows_bwd(grad_inp.contiguous(), g, xyz, xyz_min, xyz_max, *ctx.geometry))
+        return (*grads, None, None, None, None, None, None)
 
 
 def plane_rows(planes, xyz, xyz_min, xyz_max, world_size, n_freq, cell_decode=True):
@@ -694,8 +668,7 @@ def interp_decode(planes, nets, xyz, xyz_min, xyz_max, world_size, n_freq, cell_
     """interpolate: rows, the decoders, aggregation.  `nets`: {'xy': module, 'yz': module}; plane zx is decoded by
     nets['yz'] as in the reference (lib/tri_dvgo.py:170-174), so the MLPs run twice -- once on the M rows of plane xy, once
     on the 2M rows of planes yz and zx.  -> [M, 3 * out] ('concat': xy, yz, zx) or [M, out] ('sum': (xy + yz) + zx)."""
-    if aggregation not in ('concat', 'sum'):
-        raise ValueError(f"aggregation must be 'concat' or 'sum', got {aggregation!r}")
+    _check_aggregation(aggregation)
     inp = plane_rows(planes, xyz, xyz_min, xyz_max, world_size, n_freq, cell_decode)
     _, M, D = inp.shape
     p_xy = nets['xy'](inp[0])
@@ -752,8 +725,7 @@ class _SegmentSum(torch.autograd.Function):
         C = 1 if squeeze else src.shape[1]
         res = out.clone().contiguous()
         with L.device_of(src):
-            L.call('dvgo_segment_sum', ptr(src), ptr(index), _i64(src.shape[0]), _int(C), _i64(res.shape[0]),
-                   ptr(res), stream_of(src))
+            L.call('dvgo_segment_sum', src, index, src.shape[0], C, res.shape[0], res, stream_of(src))
         ctx.save_for_backward(index)
         return res
 
@@ -775,7 +747,7 @@ def segment_coo(src, index, out, reduce='sum'):
 def _segment_sum3(src, ray_id, n):
     out = torch.zeros((n, 3), dtype=torch.float32, device=src.device)
     with L.device_of(src):
-        L.call('dvgo_segment_sum', ptr(src), ptr(ray_id), _i64(src.shape[0]), _int(3), _i64(n), ptr(out), stream_of(src))
+        L.call('dvgo_segment_sum', src, ray_id, src.shape[0], 3, n, out, stream_of(src))
     return out
 
 
@@ -825,9 +797,8 @@ def total_variation_add_grad(param, grad, wx, wy, wz, dense_mode, x_range=None):
     C, X, Y, Z, sC, sX, sY, sZ = _grid_geom(param)
     lo, hi = (0, X) if x_range is None else x_range
     with L.device_of(param):
-        L.call('dvgo_total_variation_add_grad_slab', ptr(param), ptr(grad), _flt(float(wx)), _flt(float(wy)),
-               _flt(float(wz)), _i64(C), _i64(X), _i64(Y), _i64(Z), _i64(sC), _i64(sX), _i64(sY), _i64(sZ),
-               _int(1 if dense_mode else 0), _i64(lo), _i64(hi), stream_of(param))
+        L.call('dvgo_total_variation_add_grad_slab', param, grad, float(wx), float(wy), float(wz), C, X, Y, Z, sC, sX, sY, sZ,
+               1 if dense_mode else 0, lo, hi, stream_of(param))
 
 
 def plane_reg_add_grad(params, grads, weights, dense_mode):
