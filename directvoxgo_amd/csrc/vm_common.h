@@ -1,0 +1,227 @@
+// What the two vector-matrix translation units share (vm.hip: the [M, 3R] feature sampler; vm_density.hip: the sampler
+// that sums the 3R products on chip).  Device: the line descriptor, the line value, the node-sum flush, one lane's walk of
+// the gradient scatter and the scatter's kernel body (lane decode, the LDS table of mode 2).  Host: the pack of the 12 line
+// scalars of an entry point, the vector-load predicate, the argument check and the launch shape of the scatter.
+// include/dvgo_hip.h (the VM block) states the arithmetic.
+#pragma once
+#include "common.h"
+#include "plane2d.h"
+
+// mode 0's choice and the run length a lane merges by default, from the A/B of profiles/vm/README.md: at R = 16, planes
+// 160^2, lines 160 and 2 097 152 samples mode 2 took 0.86 ms against mode 1's 1.31 ms, both at run 8, the best run of
+// {1, 2, 4, 8} in every case measured.  Where mode 2's table does not fit, mode 0 is mode 1.
+#define VM_MODE_DEFAULT 2
+#define VM_RUN_DEFAULT 8
+#define VM_LDS_BYTES (64 * 1024)
+// workgroups of a mode-2 launch at the most: each adds its whole table once
+#define VM_LDS_GRID 1024
+
+struct VmLine {
+  float* p;
+  int N;
+  int64_t sC, sN;
+};
+
+struct VmGrads { float *a, *b, *c; };
+
+// line s of the three and the world axis it follows: the one plane s does not see
+__device__ __forceinline__ VmLine vm_pick(const VmLine A, const VmLine B, const VmLine D, int s, int& al) {
+  al = (s == 0) ? 0 : (s == 1) ? 2 : 1;
+  VmLine q;
+  q.p = (s == 0) ? A.p : (s == 1) ? B.p : D.p;
+  q.N = (s == 0) ? A.N : (s == 1) ? B.N : D.N;
+  q.sC = (s == 0) ? A.sC : (s == 1) ? B.sC : D.sC;
+  q.sN = (s == 0) ? A.sN : (s == 1) ? B.sN : D.sN;
+  return q;
+}
+
+__device__ __forceinline__ float* vm_pick(const VmGrads G, int s) { return (s == 0) ? G.a : (s == 1) ? G.b : G.c; }
+
+// VEC components from c on of line q in the interval (n0, n0 + 1) with the weights (w0, w1)
+template <int VEC>
+__device__ __forceinline__ TpVal<VEC> vm_line(const VmLine& q, int c, int n0, float w0, float w1) {
+  const int n1 = n0 + 1;
+  const bool ok0 = (n0 >= 0) & (n0 < q.N), ok1 = (n1 >= 0) & (n1 < q.N);
+  const float* base = q.p + (int64_t)c * q.sC;
+  const TpVal<VEC> v0 = tp_load<VEC>(base + (int64_t)min(max(n0, 0), q.N - 1) * q.sN, q.sC);
+  const TpVal<VEC> v1 = tp_load<VEC>(base + (int64_t)min(max(n1, 0), q.N - 1) * q.sN, q.sC);
+  TpVal<VEC> r;
+#pragma unroll
+  for (int i = 0; i < VEC; ++i) {
+    float l = 0.f;
+    l = ok0 ? fmaf(v0.v[i], w0, l) : l;
+    l = ok1 ? fmaf(v1.v[i], w1, l) : l;
+    r.v[i] = l;
+  }
+  return r;
+}
+
+// the two node sums of the interval (n0, n0 + 1) -> the line gradient (or the workgroup's table), nodes out of range dropped
+__device__ __forceinline__ void vm_line_flush(float* __restrict__ base, int64_t sN, int N, int n0, float s0, float s1) {
+  const int n1 = n0 + 1;
+  if ((n0 >= 0) & (n0 < N)) atomicAdd(base + (int64_t)n0 * sN, s0);
+  if ((n1 >= 0) & (n1 < N)) atomicAdd(base + (int64_t)n1 * sN, s1);
+}
+
+// One lane's walk: samples [chunk * run, min(+run, M)) of plane / line s, component r.  `lbase` / `lsN`: where the node
+// sums go -- the line gradient of (s, r) with the line's node stride, or the table row of (s, r) with stride R.
+// SKIP0: a sample whose incoming gradient is exactly 0 is passed over before anything else of it is read: it adds
+// nothing, and the cell and the interval the lane is in stay what they were.
+template <bool SKIP0>
+__device__ __forceinline__ void vm_walk(const TpPlane& q, int ah, int aw, const VmLine& ln, int al, int r, float* __restrict__ gbase,
+                                        float* __restrict__ lbase, int64_t lsN, const float* __restrict__ g, int64_t gstride,
+                                        const float* __restrict__ xyz, const float* __restrict__ mn,
+                                        const float* __restrict__ mx, int64_t m0, int64_t m1) {
+  int ch = INT_MIN, cw = INT_MIN, cn = INT_MIN;
+  float a00 = 0.f, a01 = 0.f, a10 = 0.f, a11 = 0.f, s0 = 0.f, s1 = 0.f;
+  for (int64_t m = m0; m < m1; ++m) {
+    float gv = 0.f;
+    if constexpr (SKIP0) {
+      gv = g[m * gstride];
+      if (gv == 0.f) continue;
+    }
+    const BiSetup b = tp_setup(xyz, mn, mx, m, ah, aw, q.H, q.W);
+    int n0;
+    float w0, w1;
+    tp_axis(dvgo_src_index(xyz[3 * m + al], mn[al], mx[al], ln.N), n0, w0, w1);
+    const float l = vm_line<1>(ln, r, n0, w0, w1).v[0];
+    const float p = tp_sample<1>(q, ah, aw, r, xyz, mn, mx, m).v[0];
+    if constexpr (!SKIP0) gv = g[m * gstride];
+    if ((b.h0 != ch) | (b.w0 != cw)) {
+      if (ch != INT_MIN) tp_flush(q, gbase, ch, cw, a00, a01, a10, a11);
+      ch = b.h0; cw = b.w0;
+      a00 = a01 = a10 = a11 = 0.f;
+    }
+    if (n0 != cn) {
+      if (cn != INT_MIN) vm_line_flush(lbase, lsN, ln.N, cn, s0, s1);
+      cn = n0;
+      s0 = s1 = 0.f;
+    }
+    const float tl = l * gv, tp = p * gv;
+    a00 += (b.wh0 * b.ww0) * tl;
+    a01 += (b.wh0 * b.ww1) * tl;
+    a10 += (b.wh1 * b.ww0) * tl;
+    a11 += (b.wh1 * b.ww1) * tl;
+    s0 += w0 * tp;
+    s1 += w1 * tp;
+  }
+  if (ch != INT_MIN) tp_flush(q, gbase, ch, cw, a00, a01, a10, a11);
+  if (cn != INT_MIN) vm_line_flush(lbase, lsN, ln.N, cn, s0, s1);
+}
+
+// The body of a scatter kernel.  total = nchunk * 3R lanes, nchunk = ceil(M / run); workgroup b walks the lanes
+// [b * share, (b + 1) * share), share a multiple of the workgroup size (mode 1: the workgroup size itself).  CFAST:
+// component fastest, else sample fastest.  LDS: the node sums go through the table `tab` [Na + Nb + Nc][R] (dynamic LDS).
+// The lane of (s, r) reads its incoming gradient at grad_out[s * goff_s + r + m * gstride] when PER_COMP ([M, 3R]: R, 3R)
+// and at grad_out[m] otherwise, where it also passes over exact zeros (vm_walk's SKIP0).
+template <bool CFAST, bool LDS, bool PER_COMP>
+__device__ __forceinline__ void vm_scatter_body(float* tab, TpPlane PA, TpPlane PB, TpPlane PC, VmLine LA, VmLine LB, VmLine LC,
+                                                VmGrads GP, VmGrads GL, int R, const float* __restrict__ grad_out,
+                                                const float* __restrict__ xyz, const float* __restrict__ mn,
+                                                const float* __restrict__ mx, int64_t M, int run, int64_t nchunk,
+                                                int64_t total, int64_t share) {
+  const int rows = LA.N + LB.N + LC.N;
+  if (LDS) {
+    for (int i = threadIdx.x; i < rows * R; i += DVGO_BLOCK) tab[i] = 0.f;
+    __syncthreads();
+  }
+  const int64_t first = (int64_t)blockIdx.x * share;
+  const int64_t last = (first + share < total) ? first + share : total;
+  for (int64_t tid = first + threadIdx.x; tid < last; tid += DVGO_BLOCK) {
+    int64_t chunk;
+    int s, r;
+    if (CFAST) {
+      chunk = tid / (3 * R);
+      const int j = (int)(tid - chunk * (3 * R));
+      s = j / R;
+      r = j - s * R;
+    } else {
+      const int sr = (int)(tid / nchunk);
+      chunk = tid - (int64_t)sr * nchunk;
+      s = sr / R;
+      r = sr - s * R;
+    }
+    int ah, aw, al;
+    const TpPlane q = tp_pick(PA, PB, PC, s, ah, aw);
+    const VmLine ln = vm_pick(LA, LB, LC, s, al);
+    float* gbase = vm_pick(GP, s) + (int64_t)r * q.sC;
+    float* lbase;
+    int64_t lsN;
+    if (LDS) {
+      const int row0 = (s == 0) ? 0 : (s == 1) ? LA.N : LA.N + LB.N;
+      lbase = tab + row0 * R + r;
+      lsN = R;
+    } else {
+      lbase = vm_pick(GL, s) + (int64_t)r * ln.sC;
+      lsN = ln.sN;
+    }
+    const int64_t m0 = chunk * run;
+    const int64_t m1 = (m0 + run < M) ? m0 + run : M;
+    if constexpr (PER_COMP)
+      vm_walk<false>(q, ah, aw, ln, al, r, gbase, lbase, lsN, grad_out + (int64_t)s * R + r, 3 * (int64_t)R, xyz, mn, mx, m0, m1);
+    else
+      vm_walk<true>(q, ah, aw, ln, al, r, gbase, lbase, lsN, grad_out, 1, xyz, mn, mx, m0, m1);
+  }
+  if (LDS) {
+    __syncthreads();
+    for (int i = threadIdx.x; i < rows * R; i += DVGO_BLOCK) {
+      const float v = tab[i];
+      if (v == 0.f) continue;
+      const int row = i / R, r = i - row * R;
+      const int s = (row < LA.N) ? 0 : (row < LA.N + LB.N) ? 1 : 2;
+      const int n = row - ((s == 0) ? 0 : (s == 1) ? LA.N : LA.N + LB.N);
+      int al;
+      const VmLine ln = vm_pick(LA, LB, LC, s, al);
+      atomicAdd(vm_pick(GL, s) + (int64_t)r * ln.sC + (int64_t)n * ln.sN, v);
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------------------------- host side
+static bool vm_line_vec(const VmLine& q) { return q.sC == 1 && (q.sN % 4 == 0 || q.N == 1) && ((((uintptr_t)q.p) & 15) == 0); }
+
+struct VmLines { VmLine a, b, c; };
+
+// the three lines of an entry point from its 12 line scalars
+#define VM_LINES()                                                      \
+  VmLines{VmLine{const_cast<float*>(l_xy), N_xy, lC_xy, lN_xy},         \
+          VmLine{const_cast<float*>(l_yz), N_yz, lC_yz, lN_yz},         \
+          VmLine{const_cast<float*>(l_zx), N_zx, lC_zx, lN_zx}}
+
+// tp_check with the lines' lengths among the shapes and their pointers among the pointers
+static int vm_check(const TpPlanes& P, const VmLines& L, int R, int64_t M, const void* xyz, const void* mn, const void* mx,
+                    const void* io) {
+  return tp_check(P, R, M, L.a.N >= 1 && L.b.N >= 1 && L.c.N >= 1, xyz, mn, mx, {L.a.p, L.b.p, L.c.p, io}, 3, R);
+}
+
+// The argument check and the launch shape of a scatter entry, after `vm_check` semantics: < 0 the error, 1 nothing to do,
+// 0 launch with what `S` holds.  `io`: the incoming gradient.
+struct VmScatter {
+  TpScatter S;
+  int mode;
+  bool cfast;
+  int64_t blocks, share;
+  size_t tab_bytes;
+};
+
+static int vm_scatter(const TpPlanes& P, const VmLines& L, int R, int64_t M, const void* xyz, const void* mn, const void* mx,
+                      const void* io, const VmGrads& GP, const VmGrads& GL, int run, int mode, VmScatter& V) {
+  if (run < 0 || mode < 0 || mode > 2) return DVGO_EINVAL;
+  const int rc = vm_check(P, L, R, M, xyz, mn, mx, io);
+  if (rc) return rc;
+  if (!GP.a || !GP.b || !GP.c || !GL.a || !GL.b || !GL.c) return DVGO_EINVAL;
+  const int64_t tab_bytes = ((int64_t)L.a.N + L.b.N + L.c.N) * R * (int64_t)sizeof(float);
+  if (mode == 2 && tab_bytes > VM_LDS_BYTES) return DVGO_EINVAL;
+  if (mode == 0) mode = (VM_MODE_DEFAULT == 2 && tab_bytes <= VM_LDS_BYTES) ? 2 : 1;
+  V.S = tp_scatter(P, R, M, run, VM_RUN_DEFAULT, 3 * R);
+  V.mode = mode;
+  V.cfast = V.S.cfast && L.a.sC == 1 && L.b.sC == 1 && L.c.sC == 1;          // the lines channels-last as well
+  V.blocks = dvgo_blocks(V.S.lanes, DVGO_BLOCK);
+  V.share = DVGO_BLOCK;
+  if (mode == 2 && V.blocks > VM_LDS_GRID) {
+    V.share = ((V.blocks + VM_LDS_GRID - 1) / VM_LDS_GRID) * DVGO_BLOCK;
+    V.blocks = (V.S.lanes + V.share - 1) / V.share;
+  }
+  V.tab_bytes = (mode == 2) ? (size_t)tab_bytes : 0;
+  return 0;
+}

@@ -118,14 +118,18 @@ class DirectVoxGO(VoxelModel):
     def maskout_near_cam_vox(self, cam_o, near):
         """lib/dvgo.py:215-226: density = -100 wherever a training camera is within `near` (one kernel over the voxels,
         csrc/maintain.hip; the voxel centres are the reference's torch.linspace coordinates)."""
-        dev = self.density.device
-        X, Y, Z = (int(v) for v in self.density.shape[2:])
+        self._maskout_near_cam(self.density, cam_o, near)
+
+    def _maskout_near_cam(self, grid, cam_o, near):
+        """dvgo_maskout_near_cam on `grid` [1,1,X,Y,Z]: -100 at the lattice points of the box within `near` of a camera."""
+        dev = grid.device
+        X, Y, Z = (int(v) for v in grid.shape[2:])
         gx, gy, gz = (torch.linspace(float(self._xyz_min_cpu[a]), float(self._xyz_max_cpu[a]), n, device=dev)
                       for a, n in enumerate((X, Y, Z)))
         cams = torch.as_tensor(cam_o, dtype=torch.float32).reshape(-1, 3).to(dev).contiguous()
-        with L.device_of(self.density):
-            L.call('dvgo_maskout_near_cam', ptr(self.density), ptr(gx), ptr(gy), ptr(gz), _int(X), _int(Y), _int(Z),
-                   ptr(cams), _int(cams.shape[0]), _flt(float(near)), _flt(-100.0), stream_of(self.density))
+        with L.device_of(grid):
+            L.call('dvgo_maskout_near_cam', ptr(grid), ptr(gx), ptr(gy), ptr(gz), _int(X), _int(Y), _int(Z),
+                   ptr(cams), _int(cams.shape[0]), _flt(float(near)), _flt(-100.0), stream_of(grid))
 
     @torch.no_grad()
     def scale_volume_grid(self, num_voxels):

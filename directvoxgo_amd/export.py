@@ -33,6 +33,8 @@ Mesh.__doc__ = """vertices [V,3] f32 world coordinates, faces [F,3] int32 (right
 def export_volume(model):
     """run.py:538-539: {'alpha': activate_density(density) [X,Y,Z], 'rgb': sigmoid(k0) [X,Y,Z,C]} as float32 numpy arrays
     (any k0 layout)."""
+    if getattr(model, 'density_planes', None) is not None:
+        raise NotImplementedError(f'export_volume: {type(model).__name__} has neither a dense density grid nor a k0 to export')
     alpha = model.activate_density(model.density).squeeze()
     rgb = torch.sigmoid(model.k0).squeeze().permute(1, 2, 3, 0)
     return {'alpha': np.ascontiguousarray(alpha.cpu().numpy()), 'rgb': np.ascontiguousarray(rgb.cpu().numpy())}
@@ -158,6 +160,9 @@ def _check_model(model):
     from .dmpigo import DirectMPIGO
     from .dvgo import DirectVoxGO
     from .triplane import TriPlaneVoxGO
+    if getattr(model, 'density_planes', None) is not None:
+        raise NotImplementedError(f'extract_mesh: {type(model).__name__} has no dense density grid for the iso-surface kernels '
+                                  'to read; only DirectVoxGO is supported')
     if getattr(model, 'hash_table', None) is not None:
         raise NotImplementedError(f'extract_mesh: colouring the vertices of a {type(model).__name__} (features from a hash '
                                   'table, no k0) is not built; only DirectVoxGO is supported')

@@ -3,11 +3,11 @@
 
   * occupancy refresh every 1000 steps at (step + 500) % 1000 == 0                   run.py:329-332
   * progressive grid growth at `pg_scale` steps: scale_volume_grid, NEW optimizer,
-    density -= 1                                                                      run.py:334-345
+    density -= 1 (TensoRFVoxGO, no grid: density_offset -= 1)                         run.py:334-345
   * batch draw from a permutation stream of the training rays                        run.py:348-353
   * TrainStep (forward, loss, backward, DP reduction, TV, MaskedAdam, lr decay)       run.py:372-406
     (TV: weight_tv_density / weight_tv_k0, and on the tri-plane models the optional keys weight_tv_planes /
-    weight_tv_lines / weight_l1_lines, train.PLANE_REG_KEYS)
+    weight_tv_lines / weight_l1_lines, train.PLANE_REG_KEYS, and on TensoRFVoxGO train.DENSITY_REG_KEYS)
 
 No CLI, config files, logging to disk or dataset I/O: those are out of scope.
 """
@@ -46,6 +46,9 @@ def fit_stage(model, rays_o, rays_d, viewdirs, target, cfg_train, render_kwargs,
     if cfg_train.get('pervoxel_lr', False) and isinstance(model, DirectContractedVoxGO):
         raise ValueError("cfg_train['pervoxel_lr']: voxel_count_views is not built for the contracted space of "
                          'DirectContractedVoxGO; train it with pervoxel_lr=False')
+    if cfg_train.get('pervoxel_lr', False) and getattr(model, 'density_planes', None) is not None:
+        raise ValueError(f"cfg_train['pervoxel_lr']: {type(model).__name__} has no per-voxel parameters for voxel_count_views "
+                         'to weigh; train it with pervoxel_lr=False')
     n_iters = n_iters or cfg_train['N_iters']
     n_rand = cfg_train['N_rand']
     pg_scale = list(cfg_train.get('pg_scale', []))
@@ -71,7 +74,10 @@ def fit_stage(model, rays_o, rays_d, viewdirs, target, cfg_train, render_kwargs,
             _scale_volume_grid(model, int(num_voxels_final / (2 ** n_rest)))
             step = TrainStep(model, cfg_train, render_kwargs, track_mse=True,
                              optimizer=create_optimizer_or_freeze_model(model, cfg_train, global_step=0))
-            model.density.data.sub_(1)
+            if getattr(model, 'density_planes', None) is not None:
+                model.density_offset -= 1.0            # a sum of products has no constant to lower: the activation's shift
+            else:
+                model.density.data.sub_(1)
         sel = next(batches).to(rays_o.device)
         step(rays_o[sel], rays_d[sel], viewdirs[sel], target[sel], global_step)
         mses.append(step.last_mse)
@@ -127,12 +133,14 @@ def compute_bbox_by_cam_frustrm_unbounded(HW, Ks, poses, near_clip, inner_r=1.0,
 @torch.no_grad()
 def compute_bbox_by_coarse_geo(model, thres):
     """Tight box around the voxels the coarse model considers occupied (run.py:175-196)."""
-    ws = model.density.shape[2:]
-    dev = model.density.device
+    decomposed = getattr(model, 'density_planes', None) is not None      # no grid: the density at its world_size lattice
+    density = model.dense_density() if decomposed else model.density
+    ws = density.shape[2:]
+    dev = density.device
     interp = torch.stack(torch.meshgrid(*[torch.linspace(0, 1, int(n), device=dev) for n in ws], indexing='ij'), -1)
     xyz_min, xyz_max = model.xyz_min.to(dev), model.xyz_max.to(dev)
     dense_xyz = xyz_min * (1 - interp) + xyz_max * interp
-    alpha = model.activate_density(model.grid_sampler(dense_xyz, model.density))
+    alpha = model.activate_density(density[0, 0] if decomposed else model.grid_sampler(dense_xyz, density))
     active = dense_xyz[alpha > thres]
     return active.amin(0), active.amax(0)
 

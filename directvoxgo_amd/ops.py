@@ -14,6 +14,8 @@ saved-tensor conventions) on top of the HIP kernels:
                               encoding as one MLP input row per plane, + backward; the Interp_MLPs stay torch modules)
   vm_sample                   TensoRF's vector-matrix features (no counterpart in the reference): per component a plane's
                               bilinear value times a line's linear value, + backward into planes and lines
+  vm_density                  TensoRF's vector-matrix density (no counterpart in the reference): the same 3R products summed
+                              on chip into one float per sample, + backward from one float of gradient per sample
   hash_sample                 Instant-NGP's multiresolution hash-grid features (no counterpart in the reference): L trilinear
                               levels, dense or hashed, in one table, + backward into the table
   segment_coo                 torch_scatter.segment_coo(src, index, out, reduce='sum')
@@ -361,6 +363,86 @@ def vm_sample(planes, lines, xyz, xyz_min, xyz_max):
     flat = xyz.reshape(-1, 3).contiguous()
     out = _VMSample.apply(flat, xyz_min.contiguous(), xyz_max.contiguous(), *tensors)
     return out.reshape(*shape, out.shape[-1])
+
+
+def vm_density_fwd(planes, lines, xyz, xyz_min, xyz_max):
+    """dvgo_vm_density_fwd on the strides as they are: planes [1,R,H,W], lines [1,R,N,1], xyz [M,3] -> [M], the sum of
+    `vm_fwd`'s 3R products as one fma chain in the order xy, yz, zx, component upwards (include/dvgo_hip.h).  No autograd."""
+    planes, lines, g, R, M = _vm_args(planes, lines, xyz)
+    out = torch.empty((M,), dtype=torch.float32, device=xyz.device)
+    with L.device_of(xyz):
+        L.call('dvgo_vm_density_fwd', g[0], g[1], g[2], g[3], g[4], g[5], g[6], g[7], g[8], g[9], g[10], g[11], g[12], g[13],
+               g[14], g[15], g[16], g[17], g[18], g[19], g[20], g[21], g[22], g[23], g[24], g[25], g[26], g[27], g[28], g[29],
+               R, xyz, xyz_min, xyz_max, M, out, stream_of(xyz))
+    return out
+
+
+def vm_density_bwd(grad_out, planes, lines, grad_planes, grad_lines, xyz, xyz_min, xyz_max, run=0, mode=0):
+    """dvgo_vm_density_bwd: `vm_bwd` with one float of incoming gradient per sample, grad_out [M]; samples whose gradient
+    is exactly 0 are passed over.  Accumulates into the six buffers in place; `run` and `mode` as in `vm_bwd`."""
+    planes, lines, g, R, M = _vm_args(planes, lines, xyz)
+    gp, gl = _plane_list(grad_planes), _plane_list(grad_lines)
+    for t, b in zip(planes + lines, gp + gl):
+        if b.shape != t.shape or b.dtype != torch.float32 or b.device != t.device or \
+                any(x != y for x, y, n in zip(b.stride(), t.stride(), t.shape) if n > 1):
+            raise RuntimeError('a gradient buffer must have the shape, strides, dtype and device of the tensor it belongs to')
+    check_input(grad_out, 'grad_out'); check_f32(grad_out, 'grad_out')
+    if tuple(grad_out.shape) != (M,):
+        raise RuntimeError('grad_out has the wrong shape')
+    with L.device_of(xyz):
+        L.call('dvgo_vm_density_bwd', grad_out, g[0], g[1], g[2], g[3], g[4], g[5], g[6], g[7], g[8], g[9], g[10], g[11],
+               g[12], g[13], g[14], g[15], g[16], g[17], g[18], g[19], g[20], g[21], g[22], g[23], g[24], g[25], g[26], g[27],
+               g[28], g[29], gp[0], gp[1], gp[2], gl[0], gl[1], gl[2], R, xyz, xyz_min, xyz_max, M, int(run), int(mode),
+               stream_of(xyz))
+    return gp, gl
+
+
+class _VMDensity(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, xyz, xyz_min, xyz_max, *tensors):
+        kt = _kernel_tensors(ctx, tensors, xyz.shape[0])           # the rule looks at the three planes only
+        out = vm_density_fwd(kt[:3], kt[3:], xyz, xyz_min, xyz_max)
+        ctx.save_for_backward(xyz, xyz_min, xyz_max, *kt)          # the gradient of a product reads the other factor
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        xyz, xyz_min, xyz_max, *kt = ctx.saved_tensors
+        needs = ctx.needs_input_grad[3:]
+        if not any(needs):
+            return (None,) * 9
+        # `_scatter_grads` with one zero fill instead of six: the buffers are views of one allocation, each with the
+        # strides of the tensor the kernel read (256-byte aligned).  On a sparse batch the op's backward is bound by its
+        # launches, not by the scatter (profiles/vm_density/README.md).
+        if all(t.is_contiguous() or t.is_contiguous(memory_format=torch.channels_last) for t in kt):
+            offs, top = [], 0
+            for t in kt:
+                offs.append(top)
+                top += (t.numel() + 63) // 64 * 64
+            flat = torch.zeros(top, dtype=torch.float32, device=xyz.device)
+            grads = [flat.as_strided(t.shape, t.stride(), o) for t, o in zip(kt, offs)]
+        else:
+            grads = [torch.zeros_like(t, memory_format=torch.preserve_format) for t in kt]
+        vm_density_bwd(grad_out.contiguous(), kt[:3], kt[3:], grads[:3], grads[3:], xyz, xyz_min, xyz_max)
+        return (None, None, None, *[g if need else None for g, need in zip(grads, needs)])
+
+
+def vm_density(planes, lines, xyz, xyz_min, xyz_max):
+    """TensoRF's vector-matrix density as one HIP op: `planes` and `lines` as in `vm_sample`; xyz [...,3] world coordinates
+    -> [...]: the sum over the three planes and their R components of plane value times line value, summed on chip (no
+    [M, 3R] intermediate, forward or backward).  Differentiable w.r.t. planes and lines only."""
+    tensors = _plane_list(planes) + _plane_list(lines)
+    for ln, k in zip(tensors[3:], PLANE_KEYS):             # shapes before devices
+        if ln.dim() != 4 or ln.shape[0] != 1 or ln.shape[3] != 1:
+            raise RuntimeError(f'{k}_line must be [1,R,N,1]')
+    for p, k in zip(tensors[:3], PLANE_KEYS):
+        _plane_geom(p, k)
+    for ln, k in zip(tensors[3:], PLANE_KEYS):
+        _line_geom(ln, k + '_line')
+    shape = xyz.shape[:-1]
+    flat = xyz.reshape(-1, 3).contiguous()
+    return _VMDensity.apply(flat, xyz_min.contiguous(), xyz_max.contiguous(), *tensors).reshape(shape)
 
 
 # ---------------------------------------------------------------------------------------------- hash grid

@@ -42,6 +42,10 @@ FINE_TRAIN = dict(COARSE_TRAIN, N_iters=20000, pervoxel_lr=False, weight_entropy
 # (model.plane_regularizers_add_grad); read with cfg.get(key, 0.0), inside the tv_after / tv_before / tv_every window,
 # divided by the global ray count like weight_tv_density / weight_tv_k0.  No config here sets them: no weight has been tuned
 PLANE_REG_KEYS = ('weight_tv_planes', 'weight_tv_lines', 'weight_l1_lines')
+# the same for the density planes and lines of a model whose density is decomposed (tensorf.TensoRFVoxGO): total variation
+# and L1 on either, read and scaled like PLANE_REG_KEYS and applied by the same method in a second launch
+DENSITY_REG_KEYS = ('weight_tv_density_planes', 'weight_tv_density_lines', 'weight_l1_density_planes',
+                    'weight_l1_density_lines')
 
 
 def create_optimizer_or_freeze_model(model, cfg_train, global_step):
@@ -198,6 +202,9 @@ class TrainStep:
         if getattr(model, 'hash_table', None) is not None and self.world > 1:
             raise NotImplementedError(f'data-parallel training of {type(model).__name__} (hash-grid features, a model without '
                                       'k0) is not built: train it on one GPU')
+        if getattr(model, 'density_planes', None) is not None and self.world > 1:
+            raise NotImplementedError(f'data-parallel training of {type(model).__name__} (decomposed density, no grid to shard '
+                                      'or all-reduce) is not built: train it on one GPU')
         if no_k0 and self.world > 1:
             raise NotImplementedError('data-parallel training of a model without k0 (TriPlaneVoxGO) is not built: train it on '
                                       'one GPU')
@@ -221,6 +228,12 @@ class TrainStep:
             if not hasattr(model, 'lines') and (self.plane_reg['weight_tv_lines'] > 0 or self.plane_reg['weight_l1_lines'] > 0):
                 raise ValueError(f'weight_tv_lines / weight_l1_lines: {type(model).__name__} has no lines (they belong to '
                                  'VMTriPlaneVoxGO)')
+        self.density_reg = {k: float(cfg_train.get(k, 0.0)) for k in DENSITY_REG_KEYS}
+        self.density_reg_on = any(w > 0 for w in self.density_reg.values())
+        if self.density_reg_on and getattr(model, 'density_planes', None) is None:
+            on = [k for k, w in self.density_reg.items() if w > 0]
+            raise ValueError(f'{", ".join(on)}: {type(model).__name__} has no density planes or lines (they belong to '
+                             'TensoRFVoxGO)')
         self.decay_factor = 0.1 ** (1 / (cfg_train['lrate_decay'] * 1000))
         # every collective of the step outside fused.brick_union; None on one GPU
         self.dp = None if self.world == 1 else GridReducer(
@@ -333,7 +346,7 @@ class TrainStep:
 
     def _tv_weighted(self):
         """Some regulariser of `_tv_add_grad` has a positive weight."""
-        return bool(self.cfg['weight_tv_density'] > 0 or self.cfg['weight_tv_k0'] > 0 or self.plane_reg_on)
+        return bool(self.cfg['weight_tv_density'] > 0 or self.cfg['weight_tv_k0'] > 0 or self.plane_reg_on or self.density_reg_on)
 
     def _plan(self, rays_o, global_step):
         cfg, model, opt = self.cfg, self.model, self.optimizer
@@ -435,5 +448,7 @@ class TrainStep:
             self.model.density_total_variation_add_grad(cfg['weight_tv_density'] / n_global, dense, **x_range)
         if cfg['weight_tv_k0'] > 0:
             self.model.k0_total_variation_add_grad(cfg['weight_tv_k0'] / n_global, dense, **x_range)
-        if self.plane_reg_on:                                    # planes and lines, one launch (one GPU: no slab)
+        if self.density_reg_on:                                  # colour planes and lines, then the density's: two launches
+            self.model.plane_regularizers_add_grad(dense, **{k: w / n_global for k, w in {**self.plane_reg, **self.density_reg}.items()})
+        elif self.plane_reg_on:                                  # planes and lines, one launch (one GPU: no slab)
             self.model.plane_regularizers_add_grad(dense, **{k: w / n_global for k, w in self.plane_reg.items()})

@@ -93,7 +93,7 @@ class TriPlaneVoxGO(DirectVoxGO):
         self.act_shift = np.log(1 / (1 - alpha_init) - 1)
         self._set_grid_resolution(num_voxels)
         ws = [int(v) for v in self.world_size]
-        self.density = nn.Parameter(torch.zeros([1, 1, *ws]))
+        self.density = self._alloc_density(ws)
 
         self.tri_aggregation = tri_aggregation
         self.rgbnet_dim = int(rgbnet_dim)
@@ -115,6 +115,11 @@ class TriPlaneVoxGO(DirectVoxGO):
     def _init_head(self, mlp_feat_dim, viewbase_pe, rgbnet_width, rgbnet_depth):
         self.register_buffer('viewfreq', _freqs(viewbase_pe))
         self.rgbnet = make_rgbnet(mlp_feat_dim + (3 + 3 * viewbase_pe * 2), rgbnet_width, rgbnet_depth)
+
+    def _alloc_density(self, ws):
+        """What the constructor assigns to `density`: the dense grid [1,1,X,Y,Z] (a subclass whose density is not a grid
+        creates its own parameters here and returns None)."""
+        return nn.Parameter(torch.zeros([1, 1, *ws]))
 
     def _feature_width(self):
         """What `sample_planes` emits per sample (a subclass with another feature pipeline says its own)."""
@@ -143,7 +148,7 @@ class TriPlaneVoxGO(DirectVoxGO):
         with align_corners=True, when they take their sizes from world_size; left alone under a fixed `plane_size`."""
         self._set_grid_resolution(num_voxels)
         ws = tuple(int(v) for v in self.world_size)
-        self.density = nn.Parameter(F.interpolate(self.density.data, size=ws, mode='trilinear', align_corners=True))
+        self._resize_density(ws)
         if self.plane_size is None:
             for k in PLANE_KEYS:
                 p = F.interpolate(self.planes[k].data.contiguous(), size=self._plane_hw(k), mode='bilinear', align_corners=True)
@@ -152,8 +157,12 @@ class TriPlaneVoxGO(DirectVoxGO):
                 self.planes[k] = nn.Parameter(p)
         mask = self._alpha_mask()
         if self.mask_cache_path:
-            mask = self._coarse_mask(ws, self.density.device) & mask
+            mask = self._coarse_mask(ws, self.xyz_min.device) & mask
         self._set_mask_cache(mask)
+
+    def _resize_density(self, ws):
+        """The density at the new `world_size` (the counterpart of `_alloc_density`)."""
+        self.density = nn.Parameter(F.interpolate(self.density.data, size=ws, mode='trilinear', align_corners=True))
 
     def k0_total_variation_add_grad(self, weight, dense_mode, x_range=None):
         raise NotImplementedError('k0_total_variation_add_grad: the tri-plane model has no k0 (the reference method reads an '
@@ -179,7 +188,11 @@ class TriPlaneVoxGO(DirectVoxGO):
         texels whose gradient is non-zero are touched, and a plane without a `.grad` is skipped; True: every texel, and a
         missing `.grad` is created as zeros with the parameter's strides first.  This class has no lines: a non-zero
         line weight is a ValueError.  Planes handed to `render(feats=...)` belong to the caller and are not touched."""
-        items = self._plane_reg_items(weight_tv_planes, weight_tv_lines, weight_l1_lines)
+        self._plane_reg_launch(self._plane_reg_items(weight_tv_planes, weight_tv_lines, weight_l1_lines), dense_mode)
+
+    @staticmethod
+    def _plane_reg_launch(items, dense_mode):
+        """One launch of ops.plane_reg_add_grad for `items` [(parameter, (wh, ww, wl1))], at most 8 of them."""
         params, grads, weights = [], [], []
         for p, w in items:
             if not p.requires_grad:                 # frozen by a zero learning rate: nothing reads its gradient
@@ -224,11 +237,21 @@ class TriPlaneVoxGO(DirectVoxGO):
             if render_depth:
                 ret['depth'] = composite_depth(weights.detach(), step_id, off3, N)
             return ret
+        return self._render_unfused(feats, rays_o, rays_d, viewdirs, global_step, **render_kwargs)
+
+    def _raw_density(self, pts, feats):
+        """The raw density at `pts` on the op-by-op path (a subclass whose density is not a grid says its own)."""
+        return self.grid_sampler(pts, self.density)
+
+    def _render_unfused(self, feats, rays_o, rays_d, viewdirs, global_step=None, **render_kwargs):
+        """The reference's op sequence on the drop-in ops (`fused=False`)."""
+        N = len(rays_o)
+        bg, render_depth = render_kwargs['bg'], render_kwargs.get('render_depth', False)
         pts, ray_id, step_id = self.sample_ray(rays_o=rays_o, rays_d=rays_d, is_train=global_step is not None, **render_kwargs)
         if self.mask_cache is not None:                      # skip known free space
             mask = self.mask_cache(pts)
             pts, ray_id, step_id = pts[mask], ray_id[mask], step_id[mask]
-        alpha = self.activate_density(self.grid_sampler(pts, self.density), render_kwargs['stepsize'] * self.voxel_size_ratio)
+        alpha = self.activate_density(self._raw_density(pts, feats), render_kwargs['stepsize'] * self.voxel_size_ratio)
         if self.fast_color_thres > 0:
             mask = alpha > self.fast_color_thres
             pts, ray_id, step_id, alpha = pts[mask], ray_id[mask], step_id[mask], alpha[mask]

@@ -12,7 +12,8 @@ matmul is torch's.  Density stays the dense 3-D grid on the fused march, as in t
 implementation is claimed: the contract is INTEGRATION.md section 6d, held by tests/vm_oracle.py.
 
 Everything the base leaves out stays out: extract_mesh, data-parallel training, pose refinement, the plane decoders'
-options and the encoder's keys.  Not built either: a VM-decomposed density, the basis matmul fused into the sampler.
+options and the encoder's keys.  Not built either: the basis matmul fused into the sampler.  (The VM-decomposed density is
+tensorf.TensoRFVoxGO.)
 
 Regularisers (TensoRF trains its VM model with them): `plane_regularizers_add_grad` adds total variation on the planes,
 total variation on the lines and L1 on the lines to the six gradients in one HIP launch (ops.plane_reg_add_grad,

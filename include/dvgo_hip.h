@@ -41,7 +41,7 @@ extern "C" {
 /* version of this ABI; bumped on any signature change (6: the positional-encoding colour head; 7: the contracted
  * sampler and the distortion loss of unbounded scenes; 8: the tri-plane sampler; 9: the trilinear sample's gradient
  * with respect to the position; 10: the LIIF plane decoder; 11: the fused march's gradient with respect to its rays).
- * The two dvgo_plane_rows_*, the two dvgo_vm_* and the two dvgo_hash_* entries were added without a bump, unlike the additions before them: an
+ * The two dvgo_plane_rows_*, the two dvgo_vm_*, the two dvgo_hash_* and the two dvgo_vm_density_* entries were added without a bump, unlike the additions before them: an
  * existing test pins the value 11, and a library built before them is still caught at load, by the check that every declared entry is exported. */
 #define DVGO_ABI_VERSION 11
 int dvgo_abi_version(void);
@@ -858,6 +858,41 @@ int dvgo_vm_bwd(const float* grad_out,
                 float* g_xy, float* g_yz, float* g_zx, float* gl_xy, float* gl_yz, float* gl_zx,
                 int R, const float* xyz, const float* xyz_min, const float* xyz_max, int64_t M, int run, int mode,
                 void* stream);
+
+/* ---------------------------------------------------------------------------------
+ * Vector-matrix (VM) decomposed density (csrc/vm_density.hip): the 3R
+ * products of the VM block above summed into one float per sample, with no [M, 3R] buffer anywhere.  Planes, lines, the
+ * axis table and the float32 arithmetic of p (plane value) and l (line value) are those of dvgo_vm_fwd, bit for bit.
+ * dvgo_vm_density_fwd: out[m] = sum over s in (xy, yz, zx) and r < R of p_{s,r}(m) * l_{s,r}(m), in float32, as ONE fma
+ *   chain in a fixed order: acc = 0; for s = xy, yz, zx: for r = 0 .. R - 1: acc = fmaf(p_{s,r}, l_{s,r}, acc); out[m] =
+ *   acc.  The order does not depend on the layout or alignment of planes and lines.  Bitwise repeatable.
+ * dvgo_vm_density_bwd: dvgo_vm_bwd's contract with grad_out[m, s * R + r] replaced by grad_out[m] ([M]):
+ *     g_s[r, ih, iw] += k_corner * (l * grad_out[m])       gl_s[r, n] += w_node * (p * grad_out[m])
+ *   with float atomics; run and mode 0 / 1 / 2 as in dvgo_vm_bwd (same defaults, same 64 KB table rule).  A sample whose
+ *   grad_out[m] is exactly 0 (either sign) issues no atomic and does not end the run a lane is merging: it is passed over
+ *   as if it were not there.  No gradient for xyz.
+ * M == 0 or R == 0: no-op, no pointer is looked at.  DVGO_EINVAL: negative M, R or run, a plane axis or line length < 1,
+ * a mode outside 0..2, null pointers, an explicit mode 2 whose table exceeds 64 KB.  DVGO_ERANGE: M * 3R >= 2^31 (the
+ * lanes of the scatter at run 1; the forward, M lanes, is held to the same).  All of it is answered before any launch.
+ * --------------------------------------------------------------------------------- */
+int dvgo_vm_density_fwd(const float* xy, int H_xy, int W_xy, int64_t sC_xy, int64_t sH_xy, int64_t sW_xy,
+                        const float* yz, int H_yz, int W_yz, int64_t sC_yz, int64_t sH_yz, int64_t sW_yz,
+                        const float* zx, int H_zx, int W_zx, int64_t sC_zx, int64_t sH_zx, int64_t sW_zx,
+                        const float* l_xy, int N_xy, int64_t lC_xy, int64_t lN_xy,
+                        const float* l_yz, int N_yz, int64_t lC_yz, int64_t lN_yz,
+                        const float* l_zx, int N_zx, int64_t lC_zx, int64_t lN_zx,
+                        int R, const float* xyz, const float* xyz_min, const float* xyz_max, int64_t M, float* out,
+                        void* stream);
+int dvgo_vm_density_bwd(const float* grad_out,
+                        const float* xy, int H_xy, int W_xy, int64_t sC_xy, int64_t sH_xy, int64_t sW_xy,
+                        const float* yz, int H_yz, int W_yz, int64_t sC_yz, int64_t sH_yz, int64_t sW_yz,
+                        const float* zx, int H_zx, int W_zx, int64_t sC_zx, int64_t sH_zx, int64_t sW_zx,
+                        const float* l_xy, int N_xy, int64_t lC_xy, int64_t lN_xy,
+                        const float* l_yz, int N_yz, int64_t lC_yz, int64_t lN_yz,
+                        const float* l_zx, int N_zx, int64_t lC_zx, int64_t lN_zx,
+                        float* g_xy, float* g_yz, float* g_zx, float* gl_xy, float* gl_yz, float* gl_zx,
+                        int R, const float* xyz, const float* xyz_min, const float* xyz_max, int64_t M, int run, int mode,
+                        void* stream);
 
 /* ---------------------------------------------------------------------------------
  * Total-variation and L1 regularisers of plane-shaped parameters, added to their gradients (csrc/plane_tv.hip; DESIGN.md
