@@ -1,4 +1,5 @@
-// What the samplers over three 2-D feature planes share (triplane.hip, plane_rows.hip, liif.hip, vm.hip).
+// What the samplers over three 2-D feature planes share (triplane.hip, plane_rows.hip, liif.hip, vm.hip, vm_density.hip,
+// march_vm.hip).
 // Device: the plane descriptor, the per-axis floor and weights, the four-corner fma chain, the four-corner atomic flush
 // and the run-merging walk of the gradient scatter (include/dvgo_hip.h, the tri-plane block, states the arithmetic).
 // Host, below: the pack of the 18 plane scalars of an entry point, the vector-load predicate, the staged argument check,
@@ -56,6 +57,15 @@ __device__ __forceinline__ BiSetup tp_setup(const float* __restrict__ xyz, const
   return b;
 }
 
+// the same from values: the sample's coordinates along the rows' and the columns' world axis and the box on those two axes
+// (march_vm.hip forms its positions in registers and gets the box as kernel arguments)
+__device__ __forceinline__ BiSetup tp_setup(float ph, float pw, float mnh, float mxh, float mnw, float mxw, int H, int W) {
+  BiSetup b;
+  tp_axis(dvgo_src_index(ph, mnh, mxh, H), b.h0, b.wh0, b.wh1);
+  tp_axis(dvgo_src_index(pw, mnw, mxw, W), b.w0, b.ww0, b.ww1);
+  return b;
+}
+
 template <int VEC> struct TpVal { float v[VEC]; };
 
 template <int VEC>
@@ -91,6 +101,33 @@ template <int VEC>
 __device__ __forceinline__ TpVal<VEC> tp_sample(const TpPlane& q, int ah, int aw, int c, const float* __restrict__ xyz,
                                                 const float* __restrict__ mn, const float* __restrict__ mx, int64_t m) {
   const BiSetup b = tp_setup(xyz, mn, mx, m, ah, aw, q.H, q.W);
+  const int h1 = b.h0 + 1, w1 = b.w0 + 1;
+  const bool okh0 = (b.h0 >= 0) & (b.h0 < q.H), okh1 = (h1 >= 0) & (h1 < q.H);
+  const bool okw0 = (b.w0 >= 0) & (b.w0 < q.W), okw1 = (w1 >= 0) & (w1 < q.W);
+  const int64_t oh0 = (int64_t)min(max(b.h0, 0), q.H - 1) * q.sH, oh1 = (int64_t)min(max(h1, 0), q.H - 1) * q.sH;
+  const int64_t ow0 = (int64_t)min(max(b.w0, 0), q.W - 1) * q.sW, ow1 = (int64_t)min(max(w1, 0), q.W - 1) * q.sW;
+  const float* base = q.p + (int64_t)c * q.sC;
+  const TpVal<VEC> v00 = tp_load<VEC>(base + oh0 + ow0, q.sC), v01 = tp_load<VEC>(base + oh0 + ow1, q.sC);
+  const TpVal<VEC> v10 = tp_load<VEC>(base + oh1 + ow0, q.sC), v11 = tp_load<VEC>(base + oh1 + ow1, q.sC);
+  const float k00 = b.wh0 * b.ww0, k01 = b.wh0 * b.ww1, k10 = b.wh1 * b.ww0, k11 = b.wh1 * b.ww1;
+  TpVal<VEC> r;
+#pragma unroll
+  for (int i = 0; i < VEC; ++i) {
+    float acc = 0.f;
+    acc = (okh0 & okw0) ? fmaf(v00.v[i], k00, acc) : acc;
+    acc = (okh0 & okw1) ? fmaf(v01.v[i], k01, acc) : acc;
+    acc = (okh1 & okw0) ? fmaf(v10.v[i], k10, acc) : acc;
+    acc = (okh1 & okw1) ? fmaf(v11.v[i], k11, acc) : acc;
+    r.v[i] = acc;
+  }
+  return r;
+}
+
+// the same from values (tp_setup's second form): the same loads, weights and fma chain, hence the same bits
+template <int VEC>
+__device__ __forceinline__ TpVal<VEC> tp_sample(const TpPlane& q, int c, float ph, float pw, float mnh, float mxh, float mnw,
+                                                float mxw) {
+  const BiSetup b = tp_setup(ph, pw, mnh, mxh, mnw, mxw, q.H, q.W);
   const int h1 = b.h0 + 1, w1 = b.w0 + 1;
   const bool okh0 = (b.h0 >= 0) & (b.h0 < q.H), okh1 = (h1 >= 0) & (h1 < q.H);
   const bool okw0 = (b.w0 >= 0) & (b.w0 < q.W), okw1 = (w1 >= 0) & (w1 < q.W);

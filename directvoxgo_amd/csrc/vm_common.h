@@ -1,5 +1,6 @@
-// What the two vector-matrix translation units share (vm.hip: the [M, 3R] feature sampler; vm_density.hip: the sampler
-// that sums the 3R products on chip).  Device: the line descriptor, the line value, the node-sum flush, one lane's walk of
+// What the vector-matrix translation units share (vm.hip: the [M, 3R] feature sampler; vm_density.hip: the sampler
+// that sums the 3R products on chip; march_vm.hip: the ray march over that sum, which uses the line descriptor and value,
+// the pack of the line scalars and the vector-load predicate).  Device: the line descriptor, the line value, the node-sum flush, one lane's walk of
 // the gradient scatter and the scatter's kernel body (lane decode, the LDS table of mode 2).  Host: the pack of the 12 line
 // scalars of an entry point, the vector-load predicate, the argument check and the launch shape of the scatter.
 // include/dvgo_hip.h (the VM block) states the arithmetic.

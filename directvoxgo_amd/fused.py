@@ -12,6 +12,10 @@ Two autograd Functions wrap the kernels of csrc/march.hip:
 
 One host sync per forward (the survivor count M3, needed to size the outputs); the reference
 needs five.
+
+  fused_march_vm(...)  `fused_march(..., positions=True)` for TensoRFVoxGO, whose density is a sum of plane
+                     times line products and not a grid (csrc/march_vm.hip); the backward leaves one
+                     gradient per record and hands the scatter to ops.vm_density_bwd.
 """
 import math
 
@@ -476,6 +480,104 @@ def fused_march(density, k0, rays_o, rays_d, cfg, capacity=False, positions=Fals
         raise NotImplementedError('fused_march: rays that require grad are not differentiated through '
                                   + ('the positional-encoding head\'s position input' if positions else 'NDC sampling'))
     return _FusedMarch.apply(density, k0, rays_o.contiguous(), rays_d.contiguous(), cfg, capacity, positions)
+
+
+class _FusedMarchVM(torch.autograd.Function):
+    """csrc/march_vm.hip: the march over TensoRFVoxGO's decomposed density.  Two host-visible counts, read together: M3
+    (kept samples, sizes the outputs) and M2 (records, sizes the backward's per-record gradient)."""
+
+    @staticmethod
+    def forward(ctx, rays_o, rays_d, cfg, stride, *tensors):
+        from .ops import PLANE_KEYS, _kernel_tensors, _line_geom, _plane_pack
+        from .shade import march_positions
+        for x, n in ((rays_o, 'rays_o'), (rays_d, 'rays_d')):
+            check_input(x, n); check_f32(x, n)
+        dev = rays_o.device
+        N = rays_o.shape[0]
+        cap = stride * N
+        kt = _kernel_tensors(ctx, list(tensors), cap)        # the rule looks at the three planes; cap: the steps a launch may take
+        R = kt[0].shape[1]
+        if any(t.dim() != 4 or t.shape[1] != R for t in kt):
+            raise RuntimeError('the three planes [1,R,H,W] and the three lines [1,R,N,1] must share their component count')
+        g = _plane_pack(kt[:3])
+        for ln, k in zip(kt[3:], PLANE_KEYS):
+            g += [ln, *_line_geom(ln, k + '_line')]
+        st = stream_of(rays_o)
+        n_steps = torch.empty(N, dtype=torch.int64, device=dev)
+        start = torch.empty((N, 3), dtype=torch.float32, device=dev)
+        dirs = torch.empty((N, 3), dtype=torch.float32, device=dev)
+        n2 = torch.empty(N, dtype=torch.int32, device=dev)
+        n3 = torch.empty(N, dtype=torch.int32, device=dev)
+        last = torch.empty(N, dtype=torch.float32, device=dev)
+        off3 = torch.empty(N + 1, dtype=torch.int64, device=dev)
+        off2 = torch.zeros(N + 1, dtype=torch.int64, device=dev)
+        rec2 = torch.empty((max(cap, 1), 4), dtype=torch.float32, device=dev)
+        mask = cfg.mask
+        mshape = mask.shape if mask is not None else (0, 0, 0)
+        with L.device_of(rays_o):
+            L.call('dvgo_march_vm_density', start, dirs, n_steps, stride, N, cfg.xyz_min_h, cfg.xyz_max_h, cfg.stepdist, mask,
+                   mshape[0], mshape[1], mshape[2], cfg.scale_h, cfg.shift_h, g[0], g[1], g[2], g[3], g[4], g[5], g[6], g[7],
+                   g[8], g[9], g[10], g[11], g[12], g[13], g[14], g[15], g[16], g[17], g[18], g[19], g[20], g[21], g[22], g[23],
+                   g[24], g[25], g[26], g[27], g[28], g[29], R, cfg.act_shift, cfg.interval, cfg.thres, rec2, n2, n3, last,
+                   rays_o, rays_d, cfg.near, cfg.far, st)
+            L.call('dvgo_exclusive_scan_i32', n3, N, off3, st)
+            torch.cumsum(n2, 0, dtype=torch.int64, out=off2[1:])
+            M3, M2 = torch.stack((off3[N], off2[N])).tolist()          # the one host read: both counts
+            ray_id = torch.empty(M3, dtype=torch.int64, device=dev)
+            step_id = torch.empty(M3, dtype=torch.int64, device=dev)
+            weights = torch.empty(M3, dtype=torch.float32, device=dev)
+            alpha = torch.empty(M3, dtype=torch.float32, device=dev)
+            # no feature grid: zero channels of a 1 x 1 x 1 lattice
+            L.call('dvgo_march_gather', rec2, n2, n_steps, None, stride, off3, N, M3, start, dirs, cfg.stepdist, cfg.xyz_min_h,
+                   cfg.xyz_max_h, None, 0, 1, 1, 1, 1, 1, 1, 1, ray_id, step_id, weights, alpha, None, st)
+            pts = march_positions(start, dirs, ray_id, step_id, cfg.stepdist)
+        ctx.cfg, ctx.counts = cfg, (stride, N, M2, M3)
+        ctx.save_for_backward(rec2, n2, n_steps, off3, off2, start, dirs, last, *kt)
+        ctx.mark_non_differentiable(alpha, pts, ray_id, step_id, off3)
+        ctx.set_materialize_grads(False)
+        return weights, alpha, last, pts, ray_id, step_id, off3
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_w, _g_alpha, g_last, _g_pts, _g_rid, _g_sid, _g_off):
+        from .ops import _vm_grad_buffers, vm_density_bwd
+        rec2, n2, n_steps, off3, off2, start, dirs, last, *kt = ctx.saved_tensors
+        stride, N, M2, M3 = ctx.counts
+        cfg = ctx.cfg
+        needs = ctx.needs_input_grad[4:]
+        if not any(needs):
+            return (None,) * 10
+        dev = start.device
+        grads = _vm_grad_buffers(kt)                  # one zero fill for the six
+        if M2 > 0:
+            gw = g_w.contiguous() if g_w is not None else torch.zeros(M3, dtype=torch.float32, device=dev)
+            gl = g_last.contiguous() if g_last is not None else None
+            g_raw = torch.empty(M2, dtype=torch.float32, device=dev)
+            xyz2 = torch.empty((M2, 3), dtype=torch.float32, device=dev)
+            with L.device_of(start):
+                L.call('dvgo_march_vm_density_bwd', rec2, n2, n_steps, stride, off3, off2, N, start, dirs, cfg.stepdist, last,
+                       cfg.interval, gw, gl, g_raw, xyz2, stream_of(start))
+            vm_density_bwd(g_raw, kt[:3], kt[3:], grads[:3], grads[3:], xyz2, cfg.xyz_min_t, cfg.xyz_max_t)
+        return (None, None, None, None, *[b if need else None for b, need in zip(grads, needs)])
+
+
+def fused_march_vm(density_planes, density_lines, rays_o, rays_d, cfg):
+    """`fused_march(..., positions=True)` over a vector-matrix decomposed density (csrc/march_vm.hip) -> weights [M3],
+    raw_alpha [M3], alphainv_last [N], pts [M3,3], ray_id, step_id [M3], off3 [N+1].  `density_planes` / `density_lines`: as
+    `ops.vm_density` takes them; gradients flow into the six tensors (the per-record gradient of the raw density, then
+    ops.vm_density_bwd).  The result does not depend on their layout.
+    Returns None when no fixed record stride exists for `cfg` (`_rec_stride`: an infinite `far`, or scratch over the
+    budget): the caller then takes its op-by-op path.  NDC sampling and rays that require grad are refused."""
+    from .ops import _plane_list
+    if cfg.ndc_samples > 0:
+        raise NotImplementedError('fused_march_vm: NDC sampling is not built for the decomposed density')
+    if torch.is_grad_enabled() and (rays_o.requires_grad or rays_d.requires_grad):
+        raise NotImplementedError('fused_march_vm: rays that require grad are not differentiated through the decomposed density')
+    stride = _rec_stride(cfg, rays_o.shape[0])
+    if stride == 0:
+        return None
+    return _FusedMarchVM.apply(rays_o.contiguous(), rays_d.contiguous(), cfg, stride,
+                               *_plane_list(density_planes), *_plane_list(density_lines))
 
 
 class _Composite(torch.autograd.Function):

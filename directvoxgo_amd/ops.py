@@ -397,6 +397,20 @@ def vm_density_bwd(grad_out, planes, lines, grad_planes, grad_lines, xyz, xyz_mi
     return gp, gl
 
 
+def _vm_grad_buffers(kt):
+    """Zero-filled gradient buffers for the six tensors `kt` a VM kernel read, each with its tensor's shape and strides:
+    `_scatter_grads` with one zero fill instead of six -- views of one allocation (256-byte aligned).  On a sparse batch the
+    backward is bound by its launches, not by the scatter (profiles/vm_density/README.md)."""
+    if not all(t.is_contiguous() or t.is_contiguous(memory_format=torch.channels_last) for t in kt):
+        return [torch.zeros_like(t, memory_format=torch.preserve_format) for t in kt]
+    offs, top = [], 0
+    for t in kt:
+        offs.append(top)
+        top += (t.numel() + 63) // 64 * 64
+    flat = torch.zeros(top, dtype=torch.float32, device=kt[0].device)
+    return [flat.as_strided(t.shape, t.stride(), o) for t, o in zip(kt, offs)]
+
+
 class _VMDensity(torch.autograd.Function):
     @staticmethod
     def forward(ctx, xyz, xyz_min, xyz_max, *tensors):
@@ -412,18 +426,7 @@ class _VMDensity(torch.autograd.Function):
         needs = ctx.needs_input_grad[3:]
         if not any(needs):
             return (None,) * 9
-        # `_scatter_grads` with one zero fill instead of six: the buffers are views of one allocation, each with the
-        # strides of the tensor the kernel read (256-byte aligned).  On a sparse batch the op's backward is bound by its
-        # launches, not by the scatter (profiles/vm_density/README.md).
-        if all(t.is_contiguous() or t.is_contiguous(memory_format=torch.channels_last) for t in kt):
-            offs, top = [], 0
-            for t in kt:
-                offs.append(top)
-                top += (t.numel() + 63) // 64 * 64
-            flat = torch.zeros(top, dtype=torch.float32, device=xyz.device)
-            grads = [flat.as_strided(t.shape, t.stride(), o) for t, o in zip(kt, offs)]
-        else:
-            grads = [torch.zeros_like(t, memory_format=torch.preserve_format) for t in kt]
+        grads = _vm_grad_buffers(kt)
         vm_density_bwd(grad_out.contiguous(), kt[:3], kt[3:], grads[:3], grads[3:], xyz, xyz_min, xyz_max)
         return (None, None, None, *[g if need else None for g, need in zip(grads, needs)])
 

@@ -14,9 +14,15 @@ and its Adam moments are 3 GB.
 every `pg_scale` step (run.py:345), which a sum of products cannot absorb; fit_stage lowers `density_offset` by 1 instead,
 as DVGO v2 does through its act_shift.  It costs no launch.
 
-One render path, op by op: sample_ray -> occupancy lookup -> raw_density -> alpha filter -> Alphas2Weights -> weight
-filter -> sample_planes -> the HIP colour head -> fused.composite / composite_depth.  The fused march reads a dense grid and
-is not used; `can_keep_count_on_device()` and `TrainStep.can_capture()` are False.
+Two render paths give the same dict, bit for bit in everything but the float atomics of the gradient scatter:
+  fused_march=False (the default)  op by op: sample_ray -> occupancy lookup -> raw_density -> alpha filter -> Alphas2Weights
+      -> weight filter -> sample_planes -> the HIP colour head -> fused.composite / composite_depth.  Every step of every ray
+      is materialised, the density is evaluated at every occupied sample, and three boolean compactions each read a count.
+  fused_march=True  fused.fused_march_vm (csrc/march_vm.hip: the march of DirectVoxGO with the density taken from planes
+      times lines, one wavefront per ray, chunks without an occupied step skipped, nothing behind the ray's stop visited)
+      -> sample_planes -> the colour head -> composite.  One host read of two counts (kept samples, records).  Where the
+      march has no fixed record stride (an infinite `far`, scratch over the budget) the render takes the first path.
+`can_keep_count_on_device()` and `TrainStep.can_capture()` are False on both.
 
 Occupancy goes through `dense_density()`, the op evaluated at the world_size lattice in chunks: `_pooled_alpha`,
 `_alpha_mask`, `scale_volume_grid` and fit.compute_bbox_by_coarse_geo read it; it is a temporary, never a parameter.
@@ -24,15 +30,18 @@ Occupancy goes through `dense_density()`, the op evaluated at the world_size lat
 
 Refused, each naming this class: voxel_count_views / pervoxel_lr, density_total_variation_add_grad (the regularisers of the
 density are the config keys train.DENSITY_REG_KEYS), export_volume, extract_mesh, refine_poses, data-parallel training,
-and everything the bases refuse.  Not built: a fused march over the decomposed density, a coarse stage (per-voxel
-learning rates), PSNR against a dense density (no quality claim is made).  INTEGRATION.md section 6g is the contract.
+rays that require grad, and everything the bases refuse.  Not built: a coarse stage (per-voxel learning rates), PSNR
+against a dense density (no quality claim is made), a device-side sample count for the fused march (its forward reads two
+counts).  INTEGRATION.md section 6g is the contract.
 """
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from .fused import MarchConfig, composite, composite_depth, fused_march_vm
 from .ops import PLANE_KEYS, MaskCache, Raw2Alpha, vm_density
 from .triplane import PLANE_AXES
+from .voxel_model import _result
 from .vm import LINE_AXIS, VM_FINE_TRAIN, VMTriPlaneVoxGO
 
 # VM_FINE_TRAIN with TensoRF's published rate for its grids, 2e-2, on the density planes and lines as well.  The paper's
@@ -46,11 +55,11 @@ DENSE_CHUNK = 1 << 22
 class TensoRFVoxGO(VMTriPlaneVoxGO):
     """VMTriPlaneVoxGO whose density is `vm_density(density_planes, density_lines, pts)`.  Takes the base's arguments plus
     `density_n_comp` (components per density plane), `density_plane_size` ((H, W) of all three; None: each plane follows
-    `world_size` and is resized with it), `density_line_size` (likewise for the three lines) and `density_offset` (added
-    to act_shift; see the module docstring)."""
+    `world_size` and is resized with it), `density_line_size` (likewise for the three lines), `density_offset` (added
+    to act_shift; see the module docstring) and `fused_march` (True: `render` runs on fused.fused_march_vm; default False)."""
 
     def __init__(self, xyz_min, xyz_max, density_n_comp=16, density_plane_size=None, density_line_size=None,
-                 density_offset=0.0, **kwargs):
+                 density_offset=0.0, fused_march=False, **kwargs):
         if int(density_n_comp) < 1:
             raise ValueError(f'density_n_comp must be at least 1, got {density_n_comp}')
         if density_line_size is not None and int(density_line_size) < 1:
@@ -62,6 +71,7 @@ class TensoRFVoxGO(VMTriPlaneVoxGO):
         object.__setattr__(self, 'density_line_size', None if density_line_size is None else int(density_line_size))
         object.__setattr__(self, 'density_offset', float(density_offset))
         super().__init__(xyz_min, xyz_max, **kwargs)
+        self.fused_march = bool(fused_march)
 
     # ------------------------------------------------------------------ construction
     def _density_plane_hw(self, key):
@@ -88,20 +98,26 @@ class TensoRFVoxGO(VMTriPlaneVoxGO):
     def get_kwargs(self):
         kw = super().get_kwargs()
         kw.update(density_n_comp=self.density_n_comp, density_plane_size=self.density_plane_size,
-                  density_line_size=self.density_line_size, density_offset=self.density_offset)
+                  density_line_size=self.density_line_size, density_offset=self.density_offset, fused_march=self.fused_march)
         return kw
 
     def _refuse(self, what, why):
         raise NotImplementedError(f'{what}: {type(self).__name__} {why}')
 
     # ------------------------------------------------------------------ density
+    def _density_tensors(self, feats):
+        """(planes, lines) of a render: the caller's under 'xy_density', ... and 'xy_density_line', ... in `feats`, else the
+        model's own."""
+        feats = {} if feats is None else feats
+        planes = {k: feats[k + '_density'] if k + '_density' in feats else self.density_planes[k] for k in PLANE_KEYS}
+        lines = {k: feats[k + '_density_line'] if k + '_density_line' in feats else self.density_lines[k] for k in PLANE_KEYS}
+        return planes, lines
+
     def raw_density(self, pts, feats=None):
         """[...]: the decomposed density at `pts` [..., 3], before the activation.  `feats`: optionally the caller's density
         tensors under 'xy_density', 'yz_density', 'zx_density' and 'xy_density_line', ...; a missing key means the
         model's own tensor.  Gradients flow into whichever is used."""
-        feats = {} if feats is None else feats
-        planes = {k: feats[k + '_density'] if k + '_density' in feats else self.density_planes[k] for k in PLANE_KEYS}
-        lines = {k: feats[k + '_density_line'] if k + '_density_line' in feats else self.density_lines[k] for k in PLANE_KEYS}
+        planes, lines = self._density_tensors(feats)
         return vm_density(planes, lines, pts, self.xyz_min, self.xyz_max)
 
     def _raw_density(self, pts, feats):
@@ -192,8 +208,36 @@ class TensoRFVoxGO(VMTriPlaneVoxGO):
                                                        weight_l1_density_planes, weight_l1_density_lines), dense_mode)
 
     # ------------------------------------------------------------------ forward
+    def _march_vm_cfg(self, near, far, stepsize):
+        """The base's MarchConfig (`_march_cfg`, which `hit_coarse_geo` keeps using) with the shift of `activate_density`,
+        act_shift + density_offset, formed as it forms it (one float64 sum, narrowed once at the library boundary: the
+        same float32).  Cached per (near, far, stepsize, density_offset); `_set_mask_cache` empties the cache."""
+        key = ('vm', float(near), float(far), float(stepsize), self.density_offset)
+        cfg = self._cfg_cache.get(key)
+        if cfg is None or cfg.mask is not self.mask_cache.mask:
+            mc = self.mask_cache
+            cfg = MarchConfig(self.xyz_min, self.xyz_max, stepdist=float(stepsize * self.voxel_size),
+                              act_shift=self.act_shift + self.density_offset, interval=float(stepsize * self.voxel_size_ratio),
+                              fast_color_thres=self.fast_color_thres, near=near, far=far, mask=mc.mask,
+                              xyz2ijk_scale=mc.xyz2ijk_scale, xyz2ijk_shift=mc.xyz2ijk_shift)
+            self._cfg_cache[key] = cfg
+        return cfg
+
     def render(self, feats, rays_o, rays_d, viewdirs, global_step=None, **render_kwargs):
-        """The base's result dict from the one path of this model (module docstring).  `feats`: the colour planes and
+        """The base's result dict from either path of this model (module docstring).  `feats`: the colour planes and
         lines as in the base and, beside them, density tensors under the keys of `raw_density`."""
         assert len(rays_o.shape) == 2 and rays_o.shape[-1] == 3, 'Only suuport point queries in [N, 3] format'
+        if self.fused_march:
+            if torch.is_grad_enabled() and (rays_o.requires_grad or rays_d.requires_grad):
+                self._refuse('rays that require grad', 'has no derivative of its density with respect to the sample positions')
+            cfg = self._march_vm_cfg(render_kwargs['near'], render_kwargs['far'], render_kwargs['stepsize'])
+            march = fused_march_vm(*self._density_tensors(feats), rays_o, rays_d, cfg)
+            if march is not None:                   # None: no fixed record stride for these render_kwargs -> op by op
+                weights, alpha, alphainv_last, pts, ray_id, step_id, off3 = march
+                rgb = self._shade(self._head_features(pts, feats), viewdirs, ray_id)
+                ret = _result(alphainv_last, weights, composite(weights, rgb, alphainv_last, ray_id, off3, render_kwargs['bg']),
+                              alpha, rgb, ray_id)
+                if render_kwargs.get('render_depth', False):
+                    ret['depth'] = composite_depth(weights.detach(), step_id, off3, len(rays_o))
+                return ret
         return self._render_unfused(feats, rays_o, rays_d, viewdirs, global_step, **render_kwargs)

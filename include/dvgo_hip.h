@@ -41,7 +41,7 @@ extern "C" {
 /* version of this ABI; bumped on any signature change (6: the positional-encoding colour head; 7: the contracted
  * sampler and the distortion loss of unbounded scenes; 8: the tri-plane sampler; 9: the trilinear sample's gradient
  * with respect to the position; 10: the LIIF plane decoder; 11: the fused march's gradient with respect to its rays).
- * The two dvgo_plane_rows_*, the two dvgo_vm_*, the two dvgo_hash_* and the two dvgo_vm_density_* entries were added without a bump, unlike the additions before them: an
+ * The two dvgo_plane_rows_*, the two dvgo_vm_*, the two dvgo_hash_*, the two dvgo_vm_density_* and the two dvgo_march_vm_density* entries were added without a bump, unlike the additions before them: an
  * existing test pins the value 11, and a library built before them is still caught at load, by the check that every declared entry is exported. */
 #define DVGO_ABI_VERSION 11
 int dvgo_abi_version(void);
@@ -893,6 +893,64 @@ int dvgo_vm_density_bwd(const float* grad_out,
                         float* g_xy, float* g_yz, float* g_zx, float* gl_xy, float* gl_yz, float* gl_zx,
                         int R, const float* xyz, const float* xyz_min, const float* xyz_max, int64_t M, int run, int mode,
                         void* stream);
+
+/* ---------------------------------------------------------------------------------
+ * Fused ray march over the VM decomposed density (csrc/march_vm.hip):
+ * dvgo_march_density and dvgo_march_density_bwd with the dense grid replaced by the planes and lines of the block above.
+ * Added without a bump of DVGO_ABI_VERSION, as that block was.
+ * dvgo_march_vm_density: dvgo_march_density's contract -- one wavefront per ray, the same box test, occupancy lookup, alpha
+ *   and weight filters, transmittance recurrence and stop, the same rec2 records, n2, n3 and alphainv_last, which
+ *   dvgo_march_gather reads as they are -- with these differences:
+ *     planes, lines, R in the argument order of dvgo_vm_density_fwd take the place of density, X, Y, Z;
+ *     the ray setup always happens in this launch: rays_o, rays_d [N,3], near, far are inputs, rays_start, rays_dir [N,3] and
+ *       n_steps [N] are OUTPUTS; records are at r * rec_stride only (rec_stride >= max n_steps; a ray whose step count
+ *       exceeds it is marched up to rec_stride steps, never past its slice);
+ *     stepdist must be > 0: NDC spacing is refused;
+ *     no brick counters and no tail.
+ *   xyz_min, xyz_max, xyz2ijk_scale, xyz2ijk_shift are HOST pointers, as in dvgo_march_density.  mask may be NULL.
+ *   Per step s of ray r, all in float32, no contraction but where fmaf is written:
+ *     p = fmaf(dir, stepdist * (float)s, start) per axis;  dropped when outside [xyz_min, xyz_max] or when its occupancy
+ *       byte (index roundf(fmaf(p, scale, shift)) per axis, as dvgo_march_density) is 0;
+ *     raw = dvgo_vm_density_fwd's chain at p: acc = 0; for s = xy, yz, zx: for r = 0 .. R - 1: acc = fmaf(p_{s,r}, l_{s,r},
+ *       acc) -- the same bits as that entry gives for the same position, whatever the layout or alignment (16-byte loads
+ *       under its rule, element loads otherwise);
+ *     exp_d = expf(raw + act_shift), alpha = 1 - (1 + exp_d)^(-interval) (the power of dvgo_raw2alpha);
+ *     T, the stop at T < 1e-3, the two filters and bit 31 of the record's step: as dvgo_march_density.
+ *   A chunk of 64 steps none of which passes box and mask reads no plane or line, and no chunk behind the ray's stop is
+ *   visited.  Bitwise repeatable.
+ * dvgo_march_vm_density_bwd: rec2, n2, n_steps, rec_stride, off3, rays_start, rays_dir, stepdist, alphainv_last, interval,
+ *   grad_weights, grad_last as dvgo_march_density_bwd, from the same forward (n_steps is not read: the records are at
+ *   r * rec_stride); off2 [N + 1] the exclusive scan of n2, M2 = off2[N].  The walk is dvgo_march_density_bwd's, expression
+ *   for expression: chunks of 64 records from the far end, rank of a flagged record from off3, the suffix sum of g_w * w over
+ *   the lanes above by a shuffle tree, acc += the chunk's total, then
+ *     g_alpha = (float)((double)(g_w * T) - (double)(acc + suffix) / ((double)(1 - alpha) + 1e-10))
+ *     g_raw   = (float)(min((double)exp_d, 1e10) * (double)pow(1 + exp_d, -interval - 1) * interval * g_alpha)
+ *   Record i of ray r writes g_raw[off2[r] + i] and its position xyz2[off2[r] + i] (the forward's expression: the same bits).
+ *   Nothing is scattered: no atomics, no LDS, bitwise repeatable; every one of the M2 rows is written.  The gradients of
+ *   planes and lines are dvgo_vm_density_bwd(g_raw, ..., xyz2, M2, ...), which passes over rows whose g_raw is exactly 0.
+ * n_rays == 0: no-op.  DVGO_EINVAL: negative n_rays, R < 1, a plane axis or line length < 1, stepdist <= 0, rec_stride <= 0,
+ * null pointers (grad_weights and grad_last may be NULL), a mask without its scale, shift or positive sizes.  DVGO_ERANGE:
+ * n_rays * 64 or rec_stride >= 2^31.  All of it is answered before any launch.
+ * --------------------------------------------------------------------------------- */
+int dvgo_march_vm_density(float* rays_start, float* rays_dir, int64_t* n_steps, int64_t rec_stride, int64_t n_rays,
+                          const float* xyz_min, const float* xyz_max, float stepdist,
+                          const uint8_t* mask, int mX, int mY, int mZ,
+                          const float* xyz2ijk_scale, const float* xyz2ijk_shift,
+                          const float* xy, int H_xy, int W_xy, int64_t sC_xy, int64_t sH_xy, int64_t sW_xy,
+                          const float* yz, int H_yz, int W_yz, int64_t sC_yz, int64_t sH_yz, int64_t sW_yz,
+                          const float* zx, int H_zx, int W_zx, int64_t sC_zx, int64_t sH_zx, int64_t sW_zx,
+                          const float* l_xy, int N_xy, int64_t lC_xy, int64_t lN_xy,
+                          const float* l_yz, int N_yz, int64_t lC_yz, int64_t lN_yz,
+                          const float* l_zx, int N_zx, int64_t lC_zx, int64_t lN_zx,
+                          int R, float act_shift, float interval, float fast_color_thres,
+                          dvgo_rec2_t* rec2, int32_t* n2, int32_t* n3, float* alphainv_last,
+                          const float* rays_o, const float* rays_d, float near, float far, void* stream);
+int dvgo_march_vm_density_bwd(const dvgo_rec2_t* rec2, const int32_t* n2, const int64_t* n_steps, int64_t rec_stride,
+                              const int64_t* off3, const int64_t* off2, int64_t n_rays,
+                              const float* rays_start, const float* rays_dir, float stepdist,
+                              const float* alphainv_last, float interval,
+                              const float* grad_weights /* [M3] */, const float* grad_last /* [N] or NULL */,
+                              float* g_raw /* [M2] */, float* xyz2 /* [M2,3] */, void* stream);
 
 /* ---------------------------------------------------------------------------------
  * Total-variation and L1 regularisers of plane-shaped parameters, added to their gradients (csrc/plane_tv.hip; DESIGN.md
