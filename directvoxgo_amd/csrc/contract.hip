@@ -5,29 +5,9 @@
 // CVPR 2022) for the distortion loss in its O(n) per-ray form.  The order of operations below is the contract that
 // tests/unbounded_oracle.py restates in float32; the library is built with -ffp-contract=off and HIP's correctly
 // rounded fp32 division and square root, so sampler outputs are bit-identical to that oracle.
-#include "common.h"
+#include "contract_common.h"      // the ray setup, the point, the segment and the occupancy lookup: shared with march_contract.hip
 
 #define DVGO_CONTRACT_BLOCK 64    // one wave per workgroup: a training batch (8192 rays) spreads over 128 CUs
-
-struct ContractRay {
-  float ox, oy, oz, dx, dy, dz;
-};
-
-// o' = (o - c) / r ; u = d / r ; d' = u / ||u||_2
-__device__ __forceinline__ ContractRay contract_ray(const float* __restrict__ rays_o, const float* __restrict__ rays_d,
-                                                    int64_t r, float cx, float cy, float cz, float rx, float ry,
-                                                    float rz) {
-  ContractRay R;
-  R.ox = (rays_o[3 * r + 0] - cx) / rx;
-  R.oy = (rays_o[3 * r + 1] - cy) / ry;
-  R.oz = (rays_o[3 * r + 2] - cz) / rz;
-  const float ux = rays_d[3 * r + 0] / rx, uy = rays_d[3 * r + 1] / ry, uz = rays_d[3 * r + 2] / rz;
-  const float nu = sqrtf(ux * ux + uy * uy + uz * uz);
-  R.dx = ux / nu;
-  R.dy = uy / nu;
-  R.dz = uz / nu;
-  return R;
-}
 
 // One step of the per-ray walk: point, contraction, thinning, occupancy.  Returns whether sample k is kept.
 // State carried between steps: the previous contracted point and the accumulated distance.
@@ -41,31 +21,17 @@ __device__ __forceinline__ bool contract_step(const ContractRay& R, float t, int
                                               float thres, const uint8_t* __restrict__ mask, int mi, int mj, int mk,
                                               const float* __restrict__ msc, const float* __restrict__ msh,
                                               ContractWalk& W) {
-  const float px = R.ox + R.dx * t, py = R.oy + R.dy * t, pz = R.oz + R.dz * t;
-  const float n = l2 ? sqrtf(px * px + py * py + pz * pz) : fmaxf(fmaxf(fabsf(px), fabsf(py)), fabsf(pz));
-  const bool inner = n <= 1.0f;
-  if (inner) {
-    W.qx = px; W.qy = py; W.qz = pz;
-  } else {
-    const float s = one_b - b / n;
-    W.qx = (px / n) * s; W.qy = (py / n) * s; W.qz = (pz / n) * s;
-  }
+  const bool inner = contract_point(R, t, b, one_b, l2, W.qx, W.qy, W.qz);
   bool over = false;
   if (k > 0) {
-    const float ex = W.qx - W.px_, ey = W.qy - W.py_, ez = W.qz - W.pz_;
-    W.acc = W.acc + sqrtf(ex * ex + ey * ey + ez * ez);
+    W.acc = W.acc + contract_segment(W.qx, W.qy, W.qz, W.px_, W.py_, W.pz_);
     over = W.acc > thres;
     if (over) W.acc = 0.0f;
   }
   W.px_ = W.qx; W.py_ = W.qy; W.pz_ = W.qz;
   bool keep = inner || over;
-  if (keep && mask != nullptr) {     // MaskCache lookup, as maskcache_lookup_kernel computes it
-    const int i = (int)roundf(fmaf(W.qx, msc[0], msh[0]));
-    const int j = (int)roundf(fmaf(W.qy, msc[1], msh[1]));
-    const int kk = (int)roundf(fmaf(W.qz, msc[2], msh[2]));
-    keep = 0 <= i && i < mi && 0 <= j && j < mj && 0 <= kk && kk < mk &&
-           mask[(int64_t)i * mj * mk + (int64_t)j * mk + kk] != 0;
-  }
+  if (keep && mask != nullptr)
+    keep = contract_occupied(W.qx, W.qy, W.qz, mask, mi, mj, mk, msc[0], msc[1], msc[2], msh[0], msh[1], msh[2]);
   return keep;
 }
 

@@ -16,25 +16,8 @@
 //
 // The records, dvgo_march_gather, dvgo_march_composite and their backward are march.hip's, unchanged.  The transmittance
 // carry is march_density_kernel's plain ballot / readlane walk (its FAST == false body), restated.
+#include "march_records.h"      // the lane mask, the suffix sum and the backward walk: shared with march_contract.hip
 #include "vm_common.h"
-
-__device__ __forceinline__ unsigned long long mvm_lanemask_lt(int lane) {
-  return (lane == 0) ? 0ull : (~0ull >> (64 - lane));
-}
-
-// exclusive suffix sum across the wave: sum of v over lanes > lane (march.hip: wave_suffix_excl, the same shuffles and adds)
-__device__ __forceinline__ float mvm_suffix_excl(float v, int lane, float& total) {
-  float inc = v;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const float o = __shfl_down(inc, d);
-    if (lane + d < 64) inc += o;
-  }
-  total = dvgo_readlane_f(inc, 0);
-  float ex = __shfl_down(inc, 1);
-  if (lane == 63) ex = 0.0f;
-  return ex;
-}
 
 struct MarchVmParams {
   float mnx, mny, mnz, mxx, mxy, mxz;
@@ -164,43 +147,15 @@ march_vm_density_bwd_kernel(const dvgo_rec2_t* __restrict__ rec2, const int32_t*
   if (c2 == 0) return;
   const int64_t cs0 = ray * rec_stride;
   const int64_t o3 = off3[ray], o2 = off2[ray];
-  int c3_rem = (int)(off3[ray + 1] - o3);
+  const int c3_rem = (int)(off3[ray + 1] - o3);
   const float sx = rays_start[3 * ray], sy = rays_start[3 * ray + 1], sz = rays_start[3 * ray + 2];
   const float dx = rays_dir[3 * ray], dy = rays_dir[3 * ray + 1], dz = rays_dir[3 * ray + 2];
-  const unsigned long long lt = mvm_lanemask_lt(lane);
-  float acc = (grad_last ? grad_last[ray] : 0.0f) * alphainv_last[ray];
-  for (int hi = c2; hi > 0; hi -= 64) {
-    const int lo = max(0, hi - 64);
-    const int n = hi - lo;
-    const bool act = lane < n;
-    dvgo_rec2_t rec;
-    rec.step = 0; rec.exp_d = 0.f; rec.alpha = 0.f; rec.T = 0.f;
-    if (act) rec = rec2[cs0 + lo + lane];
-    const bool flag = act && (rec.step < 0);
-    const int step = rec.step & 0x7fffffff;
-    const unsigned long long m = __ballot(flag);
-    const int cnt = __popcll(m);
-    const int rank = c3_rem - cnt + __popcll(m & lt);
-    c3_rem -= cnt;
-    const float gw = flag ? grad_weights[o3 + rank] : 0.0f;
-    const float w = rec.T * rec.alpha;
-    float total;
-    const float suffix = mvm_suffix_excl(gw * w, lane, total);   // inactive lanes contribute 0
-    const float my_acc = acc + suffix;
-    acc += total;
-    if (act) {
-      const float gt = gw * rec.T;
-      const float one_minus = 1.0f - rec.alpha;
-      const float g_alpha = (float)((double)gt - (double)my_acc / ((double)one_minus + 1e-10));
-      double v = fmin((double)rec.exp_d, 1e10) * (double)dvgo_pow_neg(1.0f + rec.exp_d, -interval - 1.0f);
-      v = v * (double)interval;
-      v = v * (double)g_alpha;
-      const float dist = march_dist(stepdist, step);
-      const int64_t i = o2 + lo + lane;
-      g_raw[i] = (float)v;
-      xyz2[3 * i] = fmaf(dx, dist, sx); xyz2[3 * i + 1] = fmaf(dy, dist, sy); xyz2[3 * i + 2] = fmaf(dz, dist, sz);
-    }
-  }
+  const float acc = (grad_last ? grad_last[ray] : 0.0f) * alphainv_last[ray];
+  march_records_bwd(rec2, c2, cs0, o3, c3_rem, o2, lane, acc, interval, grad_weights, g_raw, xyz2,
+                    [&](int step, float& x, float& y, float& z) {
+                      const float dist = march_dist(stepdist, step);
+                      x = fmaf(dx, dist, sx); y = fmaf(dy, dist, sy); z = fmaf(dz, dist, sz);
+                    });
 }
 
 extern "C" {

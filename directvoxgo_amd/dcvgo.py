@@ -17,6 +17,16 @@ the sample distances are a fixed table (`contracted_t_table`) in normalised unit
 The result carries, besides DirectVoxGO's keys, `step_id`, `t`, `s = 1 - 1/(1+t)` (per kept sample) and `n_max`;
 `depth` (render_depth) is sum_i w_i t_i in normalised units (the foreground box has half-size 1 on every axis).
 NDC rays, posbase_pe, voxel_count_views / maskout_near_cam_vox and mesh extraction are not supported.
+
+`fused_march=True` (constructor option, default False; a plain attribute like DirectVoxGO.fused_raygrad: `get_kwargs` keeps
+the key set its checkpoints have always had, so pass it to the constructor or to `load_model(..., fused_march=True)`):
+`forward` runs fused.fused_march_contract (csrc/march_contract.hip: sampler, thinning, occupancy, density, alpha, both
+filters and the transmittance in one launch, one wavefront per ray, nothing evaluated behind a ray's stop) -> k0 trilinear
+at the kept positions -> colour -> the same composite.  Same result keys, same expressions for `s` and `depth`, and the
+same bits as the op-by-op path in every key, with one documented exception shared with DirectVoxGO's fused march: with
+fast_color_thres == 0 the op-by-op path also lists the samples behind a ray's stop, with weight exactly 0, which the march
+never visits.  When the march's fixed-stride records would exceed fused._MAX_STRIDE_SCRATCH_BYTES the forward goes op by op.
+Rays that require grad are refused.  INTEGRATION.md section 5b is the contract.
 """
 import numpy as np
 import torch
@@ -25,7 +35,7 @@ import torch.nn.functional as F
 
 from . import _lib as L
 from ._lib import _flt, _i64, _int, check_f32, check_input, ptr, stream_of
-from .fused import composite
+from .fused import ContractMarchConfig, composite, fused_march_contract
 from .voxel_model import VoxelModel, _as_f32, _result
 
 
@@ -96,13 +106,14 @@ class DirectContractedVoxGO(VoxelModel):
     def __init__(self, xyz_min, xyz_max, num_voxels=0, num_voxels_base=0, alpha_init=None,
                  mask_cache_world_size=None, fast_color_thres=0, bg_len=0.2, contracted_norm='inf',
                  rgbnet_dim=0, rgbnet_direct=True, rgbnet_depth=3, rgbnet_width=128, viewbase_pe=4, fused=True,
-                 posbase_pe=0):
+                 posbase_pe=0, fused_march=False):
         super().__init__()
         if posbase_pe:
             raise NotImplementedError('posbase_pe is not supported by DirectContractedVoxGO')
         if contracted_norm not in ('inf', 'l2'):
             raise ValueError(f"contracted_norm must be 'inf' or 'l2', got {contracted_norm!r}")
         self.fused = bool(fused)
+        self.fused_march = bool(fused_march)      # forward on fused.fused_march_contract; not in get_kwargs (module docstring)
         self.fused_shade = True
         self.channels_last = True
         self.posbase_pe = 0
@@ -193,11 +204,37 @@ class DirectContractedVoxGO(VoxelModel):
                                                   self.mask_cache)
         return q, ray_id, step_id, t, n_max
 
+    def _march_contract_cfg(self, stepsize, device):
+        """The fused march's constants for this step size, cached until the grids, the mask or the device change."""
+        key = (float(stepsize), str(device))
+        cfg = self._cfg_cache.get(key)
+        if cfg is None or cfg.mask is not self.mask_cache.mask:
+            t_tab, _, thres = self._table(stepsize, device)
+            mc = self.mask_cache
+            cfg = self._cfg_cache[key] = ContractMarchConfig(
+                self.scene_center, self.scene_radius, t_tab, self.bg_len, self.contracted_norm, thres, self.xyz_min,
+                self.xyz_max, self.act_shift, float(stepsize * self.voxel_size_ratio), self.fast_color_thres,
+                mask=mc.mask, xyz2ijk_scale=mc.xyz2ijk_scale, xyz2ijk_shift=mc.xyz2ijk_shift)
+        return cfg
+
     def forward(self, rays_o, rays_d, viewdirs, global_step=None, **render_kwargs):
         """Volume rendering in contracted space; see the module docstring for the order and the extra keys.
         `near` / `far` in render_kwargs are ignored; `ndc` rays are not supported."""
         assert len(rays_o.shape) == 2 and rays_o.shape[-1] == 3, 'Only suuport point queries in [N, 3] format'
         stepsize = render_kwargs['stepsize']
+        if self.fused_march:
+            if torch.is_grad_enabled() and (rays_o.requires_grad or rays_d.requires_grad):
+                raise NotImplementedError('DirectContractedVoxGO(fused_march=True): rays that require grad are not '
+                                          'differentiated through the contraction')
+            cfg = self._march_contract_cfg(stepsize, self.density.device)
+            march = fused_march_contract(self.density, rays_o, rays_d, cfg)
+            if march is not None:
+                weights, alpha, alphainv_last, q, ray_id, step_id, t, _ = march
+                rgb = self._shade(self.grid_sampler(q, self.k0), viewdirs, ray_id)
+                ret = self._sum_rays(len(rays_o), weights, alpha, alphainv_last, rgb, ray_id, render_kwargs['bg'],
+                                     render_kwargs.get('render_depth', False), step_id, t)
+                ret['n_max'] = cfg.n_max
+                return ret
         q, ray_id, step_id, t, n_max = self.sample_ray(rays_o, rays_d, stepsize)
         ret = self._forward_unfused(len(rays_o), viewdirs, stepsize, render_kwargs['bg'],
                                     render_kwargs.get('render_depth', False), q, ray_id, step_id, t)

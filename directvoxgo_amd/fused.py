@@ -16,6 +16,9 @@ needs five.
   fused_march_vm(...)  `fused_march(..., positions=True)` for TensoRFVoxGO, whose density is a sum of plane
                      times line products and not a grid (csrc/march_vm.hip); the backward leaves one
                      gradient per record and hands the scatter to ops.vm_density_bwd.
+  fused_march_contract(...)  the march of DirectContractedVoxGO over its table of sample distances in contracted space
+                     (csrc/march_contract.hip): sampler, thinning, occupancy, density, alpha and weights in one launch;
+                     the backward leaves one gradient per record and hands the scatter to dvgo_grid_sample_bwd.
 """
 import math
 
@@ -578,6 +581,120 @@ def fused_march_vm(density_planes, density_lines, rays_o, rays_d, cfg):
         return None
     return _FusedMarchVM.apply(rays_o.contiguous(), rays_d.contiguous(), cfg, stride,
                                *_plane_list(density_planes), *_plane_list(density_lines))
+
+
+class ContractMarchConfig:
+    """Host-side constants of one DirectContractedVoxGO render setting, beside `MarchConfig`: the foreground box as centre and
+    radius, the distance table `t_tab` [n_max] (device, float32) and the thinning distance `thin_thres` of
+    dcvgo.contracted_t_table / thinning_threshold, `bg_len`, the norm ('inf' | 'l2'), the CONTRACTED bounds of the grids,
+    the activation's constants and the occupancy mask with its scale / shift.  Model constants travel to the kernels as
+    arguments, so they are kept as host arrays; the device tensors serve the existing ops of the backward."""
+
+    def __init__(self, center, radius, t_tab, bg_len, contracted_norm, thin_thres, xyz_min, xyz_max, act_shift, interval,
+                 fast_color_thres, mask=None, xyz2ijk_scale=None, xyz2ijk_shift=None):
+        if contracted_norm not in ('inf', 'l2'):
+            raise ValueError(f"contracted_norm must be 'inf' or 'l2', got {contracted_norm!r}")
+        if t_tab.dim() != 1 or t_tab.dtype != torch.float32 or not t_tab.is_contiguous():
+            raise RuntimeError('t_tab must be a contiguous float32 vector')
+        self.center_h, self.radius_h = f3(center), f3(radius)
+        self.t_tab, self.n_max = t_tab, int(t_tab.shape[0])
+        self.bg_len, self.l2 = float(bg_len), 1 if contracted_norm == 'l2' else 0
+        self.thin_thres = float(thin_thres)
+        self.xyz_min_t, self.xyz_max_t = xyz_min, xyz_max          # device tensors (dvgo_grid_sample_bwd)
+        self.xyz_min_h, self.xyz_max_h = f3(xyz_min), f3(xyz_max)
+        self.act_shift = float(act_shift)
+        self.interval = float(interval)
+        self.thres = float(fast_color_thres)
+        self.mask = mask
+        self.scale_h = f3(xyz2ijk_scale) if mask is not None else f3([0, 0, 0])
+        self.shift_h = f3(xyz2ijk_shift) if mask is not None else f3([0, 0, 0])
+
+
+class _FusedMarchContract(torch.autograd.Function):
+    """csrc/march_contract.hip: the march of DirectContractedVoxGO.  Two host-visible counts, read together: M3 (kept samples,
+    sizes the outputs) and M2 (records, sizes the backward's per-record gradient)."""
+
+    @staticmethod
+    def forward(ctx, density, rays_o, rays_d, cfg):
+        for x, n in ((rays_o, 'rays_o'), (rays_d, 'rays_d'), (density, 'density'), (cfg.t_tab, 't_tab')):
+            check_input(x, n); check_f32(x, n)
+        C, X, Y, Z = _grid_geom(density)[:4]
+        if C != 1:
+            raise RuntimeError('density must be [1,1,X,Y,Z]')
+        dev = rays_o.device
+        N, stride = rays_o.shape[0], cfg.n_max
+        st = stream_of(rays_o)
+        n2 = torch.empty(N, dtype=torch.int32, device=dev)
+        n3 = torch.empty(N, dtype=torch.int32, device=dev)
+        last = torch.empty(N, dtype=torch.float32, device=dev)
+        off3 = torch.empty(N + 1, dtype=torch.int64, device=dev)
+        off2 = torch.zeros(N + 1, dtype=torch.int64, device=dev)
+        rec2 = torch.empty((max(stride * N, 1), 4), dtype=torch.float32, device=dev)
+        mask = cfg.mask
+        mshape = mask.shape if mask is not None else (0, 0, 0)
+        with L.device_of(rays_o):
+            L.call('dvgo_march_contract_density', rays_o, rays_d, N, cfg.center_h, cfg.radius_h, cfg.t_tab, cfg.n_max, cfg.bg_len,
+                   cfg.l2, cfg.thin_thres, mask, mshape[0], mshape[1], mshape[2], cfg.scale_h, cfg.shift_h, density, X, Y, Z,
+                   cfg.xyz_min_h, cfg.xyz_max_h, cfg.act_shift, cfg.interval, cfg.thres, stride, rec2, n2, n3, last, st)
+            L.call('dvgo_exclusive_scan_i32', n3, N, off3, st)
+            torch.cumsum(n2, 0, dtype=torch.int64, out=off2[1:])
+            M3, M2 = torch.stack((off3[N], off2[N])).tolist()          # the one host read: both counts
+            ray_id = torch.empty(M3, dtype=torch.int64, device=dev)
+            step_id = torch.empty(M3, dtype=torch.int64, device=dev)
+            weights = torch.empty(M3, dtype=torch.float32, device=dev)
+            alpha = torch.empty(M3, dtype=torch.float32, device=dev)
+            q = torch.empty((M3, 3), dtype=torch.float32, device=dev)
+            t = torch.empty(M3, dtype=torch.float32, device=dev)
+            # no feature grid: zero channels of a 1 x 1 x 1 lattice.  In that mode the gather forms a uniform-step position from
+            # the start and direction it is given and uses it for nothing (rays_o / rays_d stand in: any [N,3] floats), and
+            # with a fixed stride it never reads n_steps (off3 stands in: any non-null int64 pointer).
+            L.call('dvgo_march_gather', rec2, n2, off3, None, stride, off3, N, M3, rays_o, rays_d, 1.0, cfg.xyz_min_h,
+                   cfg.xyz_max_h, None, 0, 1, 1, 1, 1, 1, 1, 1, ray_id, step_id, weights, alpha, None, st)
+            L.call('dvgo_contract_positions', rays_o, rays_d, N, cfg.center_h, cfg.radius_h, cfg.t_tab, cfg.n_max, cfg.bg_len,
+                   cfg.l2, ray_id, step_id, M3, q, t, st)
+        ctx.cfg, ctx.counts, ctx.geom = cfg, (stride, N, M2, M3), (X, Y, Z)
+        ctx.save_for_backward(rec2, n2, off3, off2, last, rays_o, rays_d, density)
+        ctx.mark_non_differentiable(alpha, q, ray_id, step_id, t, off3)
+        ctx.set_materialize_grads(False)
+        return weights, alpha, last, q, ray_id, step_id, t, off3
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_w, _g_alpha, g_last, _g_q, _g_rid, _g_sid, _g_t, _g_off):
+        if not ctx.needs_input_grad[0]:
+            return None, None, None, None
+        rec2, n2, off3, off2, last, rays_o, rays_d, density = ctx.saved_tensors
+        stride, N, M2, M3 = ctx.counts
+        cfg, (X, Y, Z) = ctx.cfg, ctx.geom
+        dev = rays_o.device
+        grad_density = torch.zeros_like(density, memory_format=torch.contiguous_format)
+        if M2 > 0 and (g_w is not None or g_last is not None):
+            gw = g_w.contiguous() if g_w is not None else torch.zeros(M3, dtype=torch.float32, device=dev)
+            gl = g_last.contiguous() if g_last is not None else None
+            g_raw = torch.empty(M2, dtype=torch.float32, device=dev)
+            q2 = torch.empty((M2, 3), dtype=torch.float32, device=dev)
+            with L.device_of(rays_o):
+                st = stream_of(rays_o)
+                L.call('dvgo_march_contract_density_bwd', rec2, n2, stride, off3, off2, N, rays_o, rays_d, cfg.center_h,
+                       cfg.radius_h, cfg.t_tab, cfg.n_max, cfg.bg_len, cfg.l2, last, cfg.interval, gw, gl, g_raw, q2, st)
+                L.call('dvgo_grid_sample_bwd', g_raw, 1, X, Y, Z, X * Y * Z, Y * Z, Z, 1, q2, cfg.xyz_min_t, cfg.xyz_max_t, M2,
+                       grad_density, st)
+        return grad_density, None, None, None
+
+
+def fused_march_contract(density, rays_o, rays_d, cfg):
+    """The fused march of DirectContractedVoxGO (csrc/march_contract.hip) -> weights [M3], raw_alpha [M3], alphainv_last [N],
+    q [M3,3] (contracted positions), ray_id, step_id [M3], t [M3], off3 [N+1].  `density` [1,1,X,Y,Z]; `cfg` a
+    `ContractMarchConfig`.  One launch marches, `dvgo_march_gather` (no feature grid) and `dvgo_contract_positions` write the
+    kept samples; one host read (M3 and M2 together).  The gradient flows into `density` only: one raw-density gradient per
+    record, then the existing trilinear scatter `dvgo_grid_sample_bwd`.
+    Returns None when the fixed-stride records (n_max * N * 16 B) exceed `_MAX_STRIDE_SCRATCH_BYTES`: the caller then takes its
+    op-by-op path.  Rays that require grad are refused."""
+    if torch.is_grad_enabled() and (rays_o.requires_grad or rays_d.requires_grad):
+        raise NotImplementedError('fused_march_contract: rays that require grad are not differentiated through the contraction')
+    if cfg.n_max * rays_o.shape[0] * 16 > _MAX_STRIDE_SCRATCH_BYTES:
+        return None
+    return _FusedMarchContract.apply(density.contiguous(), rays_o.contiguous(), rays_d.contiguous(), cfg)
 
 
 class _Composite(torch.autograd.Function):

@@ -211,8 +211,9 @@ class TrainStep:
         if self.k0_idle and self.world > 1:
             raise NotImplementedError('data-parallel training of a posbase_pe model (positional-encoding colour head) is not '
                                       'built: train it on one GPU')
-        # the contracted model of unbounded scenes (dcvgo.py) has no fused march: dense grid gradients from the
-        # grid_sample backward, then MaskedAdam; no graph capture, no data parallelism
+        # the contracted model of unbounded scenes (dcvgo.py) trains on dense grid gradients, op by op or, with its
+        # fused_march option, from csrc/march_contract.hip (one raw-density gradient per record, then the grid_sample
+        # backward's scatter), and MaskedAdam either way: no brick scatter, no graph capture, no data parallelism
         from .dcvgo import DirectContractedVoxGO
         self.contracted = isinstance(model, DirectContractedVoxGO)
         if self.contracted and self.world > 1:

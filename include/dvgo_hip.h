@@ -41,7 +41,7 @@ extern "C" {
 /* version of this ABI; bumped on any signature change (6: the positional-encoding colour head; 7: the contracted
  * sampler and the distortion loss of unbounded scenes; 8: the tri-plane sampler; 9: the trilinear sample's gradient
  * with respect to the position; 10: the LIIF plane decoder; 11: the fused march's gradient with respect to its rays).
- * The two dvgo_plane_rows_*, the two dvgo_vm_*, the two dvgo_hash_*, the two dvgo_vm_density_* and the two dvgo_march_vm_density* entries were added without a bump, unlike the additions before them: an
+ * The two dvgo_plane_rows_*, the two dvgo_vm_*, the two dvgo_hash_*, the two dvgo_vm_density_*, the two dvgo_march_vm_density*, the two dvgo_march_contract_density* and the dvgo_contract_positions entries were added without a bump, unlike the additions before them: an
  * existing test pins the value 11, and a library built before them is still caught at load, by the check that every declared entry is exported. */
 #define DVGO_ABI_VERSION 11
 int dvgo_abi_version(void);
@@ -951,6 +951,54 @@ int dvgo_march_vm_density_bwd(const dvgo_rec2_t* rec2, const int32_t* n2, const 
                               const float* alphainv_last, float interval,
                               const float* grad_weights /* [M3] */, const float* grad_last /* [N] or NULL */,
                               float* g_raw /* [M2] */, float* xyz2 /* [M2,3] */, void* stream);
+
+/* ---------------------------------------------------------------------------------
+ * Fused ray march over the contracted space of unbounded scenes (csrc/march_contract.hip; INTEGRATION.md
+ * section 5b): dvgo_contract_count / dvgo_contract_emit and dvgo_march_density in one launch.  Added without a bump of
+ * DVGO_ABI_VERSION, as the block above was.
+ * center, radius, xyz_min, xyz_max, xyz2ijk_scale, xyz2ijk_shift are HOST pointers (3 floats each), as in dvgo_march_density;
+ * rays_o, rays_d [N,3], t_tab [n_max] and everything else are device pointers.  xyz_min / xyz_max are the CONTRACTED bounds
+ * of the grids, -(1 + b) and 1 + b per axis for DirectContractedVoxGO.  mask may be NULL (all occupied).
+ * dvgo_march_contract_density: one wavefront per ray, lanes = 64 consecutive steps k < n_max.  Per step, all in float32, no
+ *   contraction but where fmaf is written, the sampler's expressions of the unbounded-scenes block operation for operation:
+ *     o', d', p_k = o' + d' * t_tab[k], n_k, q_k = p_k if n_k <= 1 else (p_k / n_k) * ((1 + b) - b / n_k);
+ *     k >= 1: acc = acc + sqrtf(ex ex + ey ey + ez ez), e = q_k - q_{k-1};  over_k = acc > thin_thres;  acc = 0 when over_k
+ *       (acc = 0 before step 1; the adds happen in step order, across the 64 lanes of a chunk and from chunk to chunk: the
+ *       kept set is dvgo_contract_emit's exactly);
+ *     kept when (n_k <= 1 or over_k) and the occupancy byte at q_k (index roundf(fmaf(q, scale, shift)) per axis) is not 0;
+ *     raw = the trilinear sample of density [X,Y,Z] (contiguous) at q_k over [xyz_min, xyz_max]: the bits dvgo_grid_sample_fwd
+ *       gives at that position;  exp_d = expf(raw + act_shift), alpha = 1 - (1 + exp_d)^(-interval) (dvgo_raw2alpha's power,
+ *       `interval` constant: stepsize * voxel_size_ratio);
+ *     T, the stop at T < 1e-3, the two filters and bit 31 of the record's step (= k): as dvgo_march_density.
+ *   Records of ray r at rec2[r * rec_stride ...], rec_stride >= n_max.  n2, n3 [N] int32, alphainv_last [N].
+ *   A chunk in which no step is kept reads no density, and no chunk behind the ray's stop is visited (the thinning walk runs
+ *   in every chunk that is visited).  Bitwise repeatable.
+ * dvgo_march_contract_density_bwd: the walk of dvgo_march_vm_density_bwd over the same records, the same g_alpha and g_raw
+ *   expressions (csrc/march_records.h is both kernels' one copy).  Record i of ray r writes g_raw[off2[r] + i] and its
+ *   contracted position q2[off2[r] + i] = q_k of its step, the forward's bits.  off3 / off2 [N + 1]: exclusive scans of n3 /
+ *   n2.  Nothing is scattered: no atomics, no LDS, bitwise repeatable, every one of the M2 rows written.  The gradient of the
+ *   grid is dvgo_grid_sample_bwd(g_raw, C = 1, ..., q2, xyz_min, xyz_max, M2, ...).
+ * dvgo_contract_positions: elementwise over M pairs (ray_id, step_id): q [M,3] = q_k and t [M] = t_tab[k], the bits
+ *   dvgo_contract_emit writes for that ray and step.  A pair outside [0, n_rays) x [0, n_max) reads nothing and gets NaN.
+ * n_rays == 0 (M == 0): no-op.  DVGO_EINVAL: negative n_rays or M, n_max <= 0, rec_stride < n_max, X, Y or Z <= 0, null
+ * pointers (grad_weights and grad_last may be NULL), a mask without its scale, shift or positive sizes.  DVGO_ERANGE:
+ * n_rays * 64, rec_stride, X * Y * Z or M >= 2^31.  All of it is answered before any launch.
+ * --------------------------------------------------------------------------------- */
+int dvgo_march_contract_density(const float* rays_o, const float* rays_d, int64_t n_rays, const float* center,
+                                const float* radius, const float* t_tab, int n_max, float bg_len, int l2, float thin_thres,
+                                const uint8_t* mask, int mX, int mY, int mZ, const float* xyz2ijk_scale,
+                                const float* xyz2ijk_shift, const float* density, int X, int Y, int Z, const float* xyz_min,
+                                const float* xyz_max, float act_shift, float interval, float fast_color_thres,
+                                int64_t rec_stride, dvgo_rec2_t* rec2, int32_t* n2, int32_t* n3, float* alphainv_last,
+                                void* stream);
+int dvgo_march_contract_density_bwd(const dvgo_rec2_t* rec2, const int32_t* n2, int64_t rec_stride, const int64_t* off3,
+                                    const int64_t* off2, int64_t n_rays, const float* rays_o, const float* rays_d,
+                                    const float* center, const float* radius, const float* t_tab, int n_max, float bg_len,
+                                    int l2, const float* alphainv_last, float interval, const float* grad_weights,
+                                    const float* grad_last, float* g_raw, float* q2, void* stream);
+int dvgo_contract_positions(const float* rays_o, const float* rays_d, int64_t n_rays, const float* center,
+                            const float* radius, const float* t_tab, int n_max, float bg_len, int l2,
+                            const int64_t* ray_id, const int64_t* step_id, int64_t M, float* q, float* t, void* stream);
 
 /* ---------------------------------------------------------------------------------
  * Total-variation and L1 regularisers of plane-shaped parameters, added to their gradients (csrc/plane_tv.hip; DESIGN.md
