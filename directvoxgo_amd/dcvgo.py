@@ -26,7 +26,16 @@ at the kept positions -> colour -> the same composite.  Same result keys, same e
 same bits as the op-by-op path in every key, with one documented exception shared with DirectVoxGO's fused march: with
 fast_color_thres == 0 the op-by-op path also lists the samples behind a ray's stop, with weight exactly 0, which the march
 never visits.  When the march's fixed-stride records would exceed fused._MAX_STRIDE_SCRATCH_BYTES the forward goes op by op.
-Rays that require grad are refused.  INTEGRATION.md section 5b is the contract.
+Rays that require grad are refused, unless `raygrad=True`.  INTEGRATION.md section 5b is the contract.
+
+`raygrad=True` (constructor option, default False; a plain attribute like `fused_march`, not a `get_kwargs` key and not in
+checkpoints: pass it to the constructor or to `load_model(..., raygrad=True)`): with grad mode on and `rays_o` or `rays_d`
+requiring grad, `forward` differentiates the render with respect to the rays, on either path (`_forward_raygrad` states the
+stop-gradients and the tie rule).  The sample positions are wrapped in ops.contract_points, whose backward is
+csrc/contract_raygrad.hip; on the fused march the density's share comes from the march's own backward
+(fused.fused_march_contract(..., raygrad=True)).  Every result key keeps the bits of the forward without the option, and
+with rays that do not require grad nothing changes.  pose.refine_poses accepts the model only with this option;
+INTEGRATION.md section 7 is the contract.
 """
 import numpy as np
 import torch
@@ -36,6 +45,7 @@ import torch.nn.functional as F
 from . import _lib as L
 from ._lib import _flt, _i64, _int, check_f32, check_input, ptr, stream_of
 from .fused import ContractMarchConfig, composite, fused_march_contract
+from .ops import contract_points
 from .voxel_model import VoxelModel, _as_f32, _result
 
 
@@ -106,7 +116,7 @@ class DirectContractedVoxGO(VoxelModel):
     def __init__(self, xyz_min, xyz_max, num_voxels=0, num_voxels_base=0, alpha_init=None,
                  mask_cache_world_size=None, fast_color_thres=0, bg_len=0.2, contracted_norm='inf',
                  rgbnet_dim=0, rgbnet_direct=True, rgbnet_depth=3, rgbnet_width=128, viewbase_pe=4, fused=True,
-                 posbase_pe=0, fused_march=False):
+                 posbase_pe=0, fused_march=False, raygrad=False):
         super().__init__()
         if posbase_pe:
             raise NotImplementedError('posbase_pe is not supported by DirectContractedVoxGO')
@@ -114,6 +124,7 @@ class DirectContractedVoxGO(VoxelModel):
             raise ValueError(f"contracted_norm must be 'inf' or 'l2', got {contracted_norm!r}")
         self.fused = bool(fused)
         self.fused_march = bool(fused_march)      # forward on fused.fused_march_contract; not in get_kwargs (module docstring)
+        self.raygrad = bool(raygrad)              # rays that require grad are differentiated; not in get_kwargs (module docstring)
         self.fused_shade = True
         self.channels_last = True
         self.posbase_pe = 0
@@ -222,10 +233,14 @@ class DirectContractedVoxGO(VoxelModel):
         `near` / `far` in render_kwargs are ignored; `ndc` rays are not supported."""
         assert len(rays_o.shape) == 2 and rays_o.shape[-1] == 3, 'Only suuport point queries in [N, 3] format'
         stepsize = render_kwargs['stepsize']
+        ray_grad = torch.is_grad_enabled() and (rays_o.requires_grad or rays_d.requires_grad)
+        if ray_grad and self.raygrad:
+            return self._forward_raygrad(rays_o, rays_d, viewdirs, stepsize, render_kwargs['bg'],
+                                         render_kwargs.get('render_depth', False))
         if self.fused_march:
-            if torch.is_grad_enabled() and (rays_o.requires_grad or rays_d.requires_grad):
+            if ray_grad:
                 raise NotImplementedError('DirectContractedVoxGO(fused_march=True): rays that require grad are not '
-                                          'differentiated through the contraction')
+                                          'differentiated through the contraction: construct it with raygrad=True')
             cfg = self._march_contract_cfg(stepsize, self.density.device)
             march = fused_march_contract(self.density, rays_o, rays_d, cfg)
             if march is not None:
@@ -240,6 +255,55 @@ class DirectContractedVoxGO(VoxelModel):
                                     render_kwargs.get('render_depth', False), q, ray_id, step_id, t)
         ret['n_max'] = n_max
         return ret
+
+    def _forward_raygrad(self, rays_o, rays_d, viewdirs, stepsize, bg, render_depth):
+        """`forward` for rays that require grad (raygrad=True): the same launches and the same bits in every result key as
+        the forward without, on sample positions that autograd knows as the contraction of their rays (ops.contract_points;
+        csrc/contract_raygrad.hip), sampled through the position-differentiable trilinear op (csrc/grid_sample_xyz.hip).
+        Stop-gradients, by contract:
+          * the table of distances `t` is a constant (so the normalisation of rays_d IS differentiated, unlike
+            DirectVoxGO._forward_raygrad's lam);
+          * the set of kept samples is fixed: thinning, occupancy and both fast_color_thres filters select rows;
+          * `s` and `depth` carry no gradient: the distortion loss reaches the rays through `weights` only;
+          * viewdirs carries no gradient (the colour heads have no input gradient for the view embedding).
+        At an inf-norm tie the lowest axis index attaining max|p_a| carries the norm's derivative; n == 1 is the identity."""
+        rays_o, rays_d, viewdirs = rays_o.contiguous(), rays_d.contiguous(), viewdirs.detach()
+        N, dev = len(rays_o), self.density.device
+        t_tab, n_max, _ = self._table(stepsize, rays_o.device)
+        wrap = lambda q, ray_id, step_id: contract_points(      # noqa: E731
+            rays_o, rays_d, ray_id, step_id, q, self.scene_center_h, self.scene_radius_h, t_tab, self.bg_len,
+            self.contracted_norm)
+        if self.fused_march:
+            cfg = self._march_contract_cfg(stepsize, dev)
+            march = fused_march_contract(self.density, rays_o, rays_d, cfg, raygrad=True)
+            if march is not None:
+                # the density's share of the ray gradient comes from the march's own backward; k0's through the wrapped q
+                weights, alpha, alphainv_last, q, ray_id, step_id, t, _ = march
+                rgb = self._shade(self.grid_sampler(wrap(q, ray_id, step_id), self.k0), viewdirs, ray_id)
+                ret = self._sum_rays(N, weights, alpha, alphainv_last, rgb, ray_id, bg, render_depth, step_id, t)
+                ret['n_max'] = cfg.n_max
+                return ret
+        with torch.no_grad():
+            q, ray_id, step_id, t, n_max = self.sample_ray(rays_o, rays_d, stepsize)
+        ret = self._forward_unfused(N, viewdirs, stepsize, bg, render_depth, wrap(q, ray_id, step_id), ray_id, step_id, t)
+        ret['n_max'] = n_max
+        return ret
+
+    @property
+    def scene_center_h(self):
+        """The foreground box's centre as a host array (kernel argument of the ray gradient); read once per device copy."""
+        return self._host3('scene_center')
+
+    @property
+    def scene_radius_h(self):
+        return self._host3('scene_radius')
+
+    def _host3(self, name):
+        buf = getattr(self, name)
+        key = (name, buf.data_ptr())
+        if key not in self._tab_cache:
+            self._tab_cache[key] = L.f3(buf)
+        return self._tab_cache[key]
 
     def _sum_rays(self, N, weights, alpha, alphainv_last, rgb, ray_id, bg, render_depth, step_id, t):
         """Per-ray sums in fixed order (the march's composite over the ray offsets): bitwise repeatable renders."""

@@ -18,7 +18,9 @@ needs five.
                      gradient per record and hands the scatter to ops.vm_density_bwd.
   fused_march_contract(...)  the march of DirectContractedVoxGO over its table of sample distances in contracted space
                      (csrc/march_contract.hip): sampler, thinning, occupancy, density, alpha and weights in one launch;
-                     the backward leaves one gradient per record and hands the scatter to dvgo_grid_sample_bwd.
+                     the backward leaves one gradient per record and hands the scatter to dvgo_grid_sample_bwd.  With
+                     `raygrad=True` it also returns the rays' gradient: the per-record gradients through the trilinear
+                     position gradient and csrc/contract_raygrad.hip (camera-pose refinement of unbounded scenes).
 """
 import math
 
@@ -615,7 +617,7 @@ class _FusedMarchContract(torch.autograd.Function):
     sizes the outputs) and M2 (records, sizes the backward's per-record gradient)."""
 
     @staticmethod
-    def forward(ctx, density, rays_o, rays_d, cfg):
+    def forward(ctx, density, rays_o, rays_d, cfg, raygrad=False):
         for x, n in ((rays_o, 'rays_o'), (rays_d, 'rays_d'), (density, 'density'), (cfg.t_tab, 't_tab')):
             check_input(x, n); check_f32(x, n)
         C, X, Y, Z = _grid_geom(density)[:4]
@@ -653,6 +655,7 @@ class _FusedMarchContract(torch.autograd.Function):
             L.call('dvgo_contract_positions', rays_o, rays_d, N, cfg.center_h, cfg.radius_h, cfg.t_tab, cfg.n_max, cfg.bg_len,
                    cfg.l2, ray_id, step_id, M3, q, t, st)
         ctx.cfg, ctx.counts, ctx.geom = cfg, (stride, N, M2, M3), (X, Y, Z)
+        ctx.raygrad = bool(raygrad)
         ctx.save_for_backward(rec2, n2, off3, off2, last, rays_o, rays_d, density)
         ctx.mark_non_differentiable(alpha, q, ray_id, step_id, t, off3)
         ctx.set_materialize_grads(False)
@@ -661,13 +664,17 @@ class _FusedMarchContract(torch.autograd.Function):
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, g_w, _g_alpha, g_last, _g_q, _g_rid, _g_sid, _g_t, _g_off):
-        if not ctx.needs_input_grad[0]:
-            return None, None, None, None
+        # the rays' gradient (raygrad=True): wanted also when the model is frozen and `density` takes none
+        want_rays = ctx.raygrad and (ctx.needs_input_grad[1] or ctx.needs_input_grad[2])
+        want_density = ctx.needs_input_grad[0]
+        if not want_density and not want_rays:
+            return None, None, None, None, None
         rec2, n2, off3, off2, last, rays_o, rays_d, density = ctx.saved_tensors
         stride, N, M2, M3 = ctx.counts
         cfg, (X, Y, Z) = ctx.cfg, ctx.geom
         dev = rays_o.device
-        grad_density = torch.zeros_like(density, memory_format=torch.contiguous_format)
+        grad_density = torch.zeros_like(density, memory_format=torch.contiguous_format) if want_density else None
+        grad_o = grad_d = None
         if M2 > 0 and (g_w is not None or g_last is not None):
             gw = g_w.contiguous() if g_w is not None else torch.zeros(M3, dtype=torch.float32, device=dev)
             gl = g_last.contiguous() if g_last is not None else None
@@ -677,24 +684,42 @@ class _FusedMarchContract(torch.autograd.Function):
                 st = stream_of(rays_o)
                 L.call('dvgo_march_contract_density_bwd', rec2, n2, stride, off3, off2, N, rays_o, rays_d, cfg.center_h,
                        cfg.radius_h, cfg.t_tab, cfg.n_max, cfg.bg_len, cfg.l2, last, cfg.interval, gw, gl, g_raw, q2, st)
-                L.call('dvgo_grid_sample_bwd', g_raw, 1, X, Y, Z, X * Y * Z, Y * Z, Z, 1, q2, cfg.xyz_min_t, cfg.xyz_max_t, M2,
-                       grad_density, st)
-        return grad_density, None, None, None
+                if want_density:
+                    L.call('dvgo_grid_sample_bwd', g_raw, 1, X, Y, Z, X * Y * Z, Y * Z, Z, 1, q2, cfg.xyz_min_t, cfg.xyz_max_t,
+                           M2, grad_density, st)
+                if want_rays:
+                    # dL/dq2 per record through the density's trilinear sample, then the contraction and the ray (the k0 term
+                    # arrives separately: ops.contract_points on the march's q)
+                    g_q2 = torch.empty((M2, 3), dtype=torch.float32, device=dev)
+                    grad_o = torch.empty((N, 3), dtype=torch.float32, device=dev)
+                    grad_d = torch.empty((N, 3), dtype=torch.float32, device=dev)
+                    L.call('dvgo_grid_sample_bwd_xyz', density, 1, X, Y, Z, X * Y * Z, Y * Z, Z, 1, g_raw, q2, cfg.xyz_min_t,
+                           cfg.xyz_max_t, M2, g_q2, st)
+                    L.call('dvgo_contract_ray_bwd_rec', rays_o, rays_d, N, cfg.center_h, cfg.radius_h, cfg.t_tab, cfg.n_max,
+                           cfg.bg_len, cfg.l2, rec2, n2, stride, off2, g_q2, M2, grad_o, grad_d, st)
+        return (grad_density, grad_o if ctx.needs_input_grad[1] else None, grad_d if ctx.needs_input_grad[2] else None, None,
+                None)
 
 
-def fused_march_contract(density, rays_o, rays_d, cfg):
+def fused_march_contract(density, rays_o, rays_d, cfg, raygrad=False):
     """The fused march of DirectContractedVoxGO (csrc/march_contract.hip) -> weights [M3], raw_alpha [M3], alphainv_last [N],
     q [M3,3] (contracted positions), ray_id, step_id [M3], t [M3], off3 [N+1].  `density` [1,1,X,Y,Z]; `cfg` a
     `ContractMarchConfig`.  One launch marches, `dvgo_march_gather` (no feature grid) and `dvgo_contract_positions` write the
-    kept samples; one host read (M3 and M2 together).  The gradient flows into `density` only: one raw-density gradient per
+    kept samples; one host read (M3 and M2 together).  The gradient flows into `density`: one raw-density gradient per
     record, then the existing trilinear scatter `dvgo_grid_sample_bwd`.
     Returns None when the fixed-stride records (n_max * N * 16 B) exceed `_MAX_STRIDE_SCRATCH_BYTES`: the caller then takes its
-    op-by-op path.  Rays that require grad are refused."""
-    if torch.is_grad_enabled() and (rays_o.requires_grad or rays_d.requires_grad):
+    op-by-op path.
+    Rays that require grad are refused unless `raygrad=True`.  Then the forward is the same launches and the backward also
+    returns the rays' gradient through `weights` and `alphainv_last`: the per-record raw-density gradients (formed even when
+    `density` itself takes no gradient) -> `dvgo_grid_sample_bwd_xyz` (C = 1) at the records' positions -> the contraction's and
+    the ray's Jacobian summed per ray, `dvgo_contract_ray_bwd_rec` (csrc/contract_raygrad.hip).  The returned `q` stays
+    non-differentiable: a caller that samples further grids at it wraps it in `ops.contract_points`, and autograd adds the two
+    pairs of ray gradients.  The table, the kept set and `t` are constants."""
+    if not raygrad and torch.is_grad_enabled() and (rays_o.requires_grad or rays_d.requires_grad):
         raise NotImplementedError('fused_march_contract: rays that require grad are not differentiated through the contraction')
     if cfg.n_max * rays_o.shape[0] * 16 > _MAX_STRIDE_SCRATCH_BYTES:
         return None
-    return _FusedMarchContract.apply(density.contiguous(), rays_o.contiguous(), rays_d.contiguous(), cfg)
+    return _FusedMarchContract.apply(density.contiguous(), rays_o.contiguous(), rays_d.contiguous(), cfg, bool(raygrad))
 
 
 class _Composite(torch.autograd.Function):

@@ -7,6 +7,7 @@ saved-tensor conventions) on top of the HIP kernels:
   MaskCache                   lib/dvgo.py:583-613
   grid_sample                 lib/dvgo.py:312-328 (grid_sampler -> F.grid_sample + its backward, w.r.t. the grid and the positions)
   ray_points                  sample positions as a function of their rays (no counterpart: the reference's poses are constants)
+  contract_points             contracted sample positions as a function of their rays (no counterpart; csrc/contract_raygrad.hip)
   triplane_sample             lib/tri_dvgo.py:456-469 (grid_sampler2D -> three F.grid_sample, cat or sum, + backward)
   liif_gather, liif_blend,    lib/tri_dvgo.py:481-565 (liif_interpolate: nearest-texel rows, blend weights, blend, + backward;
   liif_decode                 the Interp_MLPs between them stay torch modules)
@@ -869,6 +870,60 @@ def ray_points(rays_o, rays_d, lam, ray_id, pts):
     both by dvgo_segment_sum into zero-filled [N,3] (a ray without samples gets exact zeros).  `ray_id` [M] int64 ascending,
     as every sampler here writes it.  rays_o / rays_d [N,3] float32 CUDA tensors."""
     return _RayPoints.apply(rays_o, rays_d, lam, ray_id, pts)
+
+
+class _ContractPoints(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, rays_o, rays_d, ray_id, step_id, q, center, radius, t_tab, bg_len, l2):
+        for x, name in ((rays_o, 'rays_o'), (rays_d, 'rays_d'), (q, 'q'), (t_tab, 't_tab')):
+            check_input(x, name); check_f32(x, name)
+        for x, name in ((ray_id, 'ray_id'), (step_id, 'step_id')):
+            check_input(x, name)
+            if x.dtype != torch.int64:
+                raise RuntimeError(f'{name} must be int64')
+        if q.dim() != 2 or q.shape[1] != 3 or ray_id.shape != step_id.shape or ray_id.shape != q.shape[:1]:
+            raise RuntimeError('q must be [M,3], ray_id and step_id [M]')
+        if rays_o.shape != rays_d.shape or rays_o.dim() != 2 or rays_o.shape[1] != 3:
+            raise RuntimeError('rays_o and rays_d must be [N,3]')
+        if t_tab.dim() != 1 or t_tab.shape[0] == 0:
+            raise RuntimeError('t_tab must be a non-empty vector')
+        ctx.save_for_backward(rays_o, rays_d, ray_id, step_id, t_tab)
+        ctx.consts = (L.f3(center), L.f3(radius), float(bg_len), int(l2))
+        return q.clone()
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        rays_o, rays_d, ray_id, step_id, t_tab = ctx.saved_tensors
+        center, radius, bg_len, l2 = ctx.consts
+        N, dev = rays_o.shape[0], rays_o.device
+        g = g.contiguous()
+        off = torch.searchsorted(ray_id, torch.arange(N + 1, dtype=torch.int64, device=dev))
+        grad_o = torch.empty((N, 3), dtype=torch.float32, device=dev)       # every row is written by the kernel
+        grad_d = torch.empty((N, 3), dtype=torch.float32, device=dev)
+        with L.device_of(rays_o):
+            L.call('dvgo_contract_ray_bwd', rays_o, rays_d, N, center, radius, t_tab, t_tab.shape[0], bg_len, l2, g, step_id,
+                   g.shape[0], off, grad_o, grad_d, stream_of(rays_o))
+        return (grad_o if ctx.needs_input_grad[0] else None, grad_d if ctx.needs_input_grad[1] else None, None, None, None,
+                None, None, None, None, None)
+
+
+def contract_points(rays_o, rays_d, ray_id, step_id, q, center, radius, t_tab, bg_len, contracted_norm):
+    """The contracted sampler's positions as a differentiable function of their rays: the counterpart of `ray_points` for
+    DirectContractedVoxGO.  Returns `q` [M,3] unchanged, bit for bit (what the sampling kernel wrote), and states to autograd
+    that row m is the contracted sample of ray ray_id[m] at the table's distance t_tab[step_id[m]]:
+        o' = (o - c) / r,  u = d / r,  d' = u / ||u||,  p = o' + d' * t,  q = p if n <= 1 else p * ((1 + b) / n - b / n^2),
+        n = max|p_a| ('inf') or ||p||_2 ('l2')
+    with `t_tab` a constant.  The backward is csrc/contract_raygrad.hip (dvgo_contract_ray_bwd, include/dvgo_hip.h states the
+    arithmetic): the contraction's Jacobian per sample -- at an inf-norm tie the LOWEST axis index attaining max|p_a| carries
+    the norm's derivative, and n == 1 exactly is the identity -- summed per ray in a fixed order, then the ray's own Jacobian,
+    the normalisation of d included.  A ray without samples gets exact zeros.  Once differentiable.
+    `ray_id`, `step_id` [M] int64, ray_id ascending as every sampler here writes it; rays_o / rays_d [N,3] and t_tab [n_max]
+    float32 CUDA tensors; `center`, `radius`: 3 floats each (tensor, sequence or host array)."""
+    if contracted_norm not in ('inf', 'l2'):
+        raise ValueError(f"contracted_norm must be 'inf' or 'l2', got {contracted_norm!r}")
+    return _ContractPoints.apply(rays_o, rays_d, ray_id, step_id, q, center, radius, t_tab, bg_len,
+                                 1 if contracted_norm == 'l2' else 0)
 
 
 def total_variation_add_grad(param, grad, wx, wy, wz, dense_mode, x_range=None):

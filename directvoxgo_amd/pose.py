@@ -1,4 +1,5 @@
-"""Camera-pose refinement against a DirectVoxGO model (no counterpart in the reference, whose poses are constants).
+"""Camera-pose refinement against a DirectVoxGO or, for unbounded scenes, a DirectContractedVoxGO(raygrad=True) model (no
+counterpart in the reference, whose poses are constants).
 
 Poses from structure-from-motion are off by fractions of a degree, which on a 160^3 - 256^3 grid blurs what the grids could
 hold.  This module makes the poses learnable: `CameraRefiner` holds one se(3) correction per view and turns pixels into
@@ -7,7 +8,9 @@ positions (ops.ray_points, ops.grid_sample's position gradient: csrc/grid_sample
 eager optimisation loop -- poses alone against a trained model (registration of new images included), or poses and model
 together.  `refine_poses(..., fused=True)` keeps the render on the fused march (csrc/march.hip: march_ray_bwd returns the
 ray gradients from the march's own backward) and, with `train_model`, steps the model by a train.TrainStep: the brick
-scatter with the Adam update inside it, as in any other training step.
+scatter with the Adam update inside it, as in any other training step.  For the contracted model the positions are the
+contraction of their rays (ops.contract_points; csrc/contract_raygrad.hip applies the contraction's Jacobian and sums per
+ray), on either of its render paths.
 
 Pure torch: everything but `refine_poses`' model call runs on CPU tensors too.
 """
@@ -111,8 +114,15 @@ class CameraRefiner(nn.Module):
         return rays_o.contiguous(), rays_d.contiguous(), viewdirs.contiguous()
 
 
+def _contracted(model):
+    from .dcvgo import DirectContractedVoxGO
+    return type(model) is DirectContractedVoxGO
+
+
 def _supported(model):
     from .dvgo import DirectVoxGO
+    if _contracted(model):
+        return model.raygrad
     return type(model) is DirectVoxGO and model.posbase_pe == 0
 
 
@@ -133,14 +143,24 @@ def refine_poses(model, refiner, images, cfg_train, render_kwargs, n_iters, n_ra
     `opt_pose.zero_grad()`, `loss = step(rays_o, rays_d, viewdirs, target, it + 1)`, `opt_pose.step()` -- whose backward
     updates both grids inside the brick scatter where the optimizer allows it (their `.grad` stays None).
 
+    A `DirectContractedVoxGO(raygrad=True)` (unbounded scenes) renders by its own path, fused march or op by op as it was
+    constructed, with the rays differentiated through the contraction (csrc/contract_raygrad.hip;
+    DirectContractedVoxGO._forward_raygrad states the stop-gradients).  `fused=True` then requires `model.fused_march`
+    (ValueError otherwise) and, with `train_model`, steps the model by a `train.TrainStep`, whose plan for this model is dense
+    gradients and the optimizer's own step; `cfg_train['weight_distortion']` adds the distortion loss as in training.
+
     The gradient reaches `delta` through the sample positions only (DirectVoxGO._forward_raygrad states the stop-gradients).
-    Only a plain DirectVoxGO with posbase_pe == 0 is supported: DirectMPIGO (NDC warp), DirectContractedVoxGO (contraction
-    Jacobian), TriPlaneVoxGO (plane sampler) and positional-encoding heads (position input of the head) lack their
-    derivative and raise NotImplementedError."""
+    Supported: a plain DirectVoxGO with posbase_pe == 0 and a DirectContractedVoxGO constructed with raygrad=True.
+    DirectMPIGO (NDC warp), TriPlaneVoxGO (plane sampler) and positional-encoding heads (position input of the head) lack
+    their derivative and raise NotImplementedError, as does a DirectContractedVoxGO without raygrad."""
     if not _supported(model):
         kind = type(model).__name__ + (' with posbase_pe > 0' if getattr(model, 'posbase_pe', 0) > 0 else '')
+        hint = ': construct it with raygrad=True' if _contracted(model) else ''
         raise NotImplementedError(f'refine_poses: {kind} is not supported: only a plain DirectVoxGO with posbase_pe == 0 has '
-                                  'the position derivative of its sampler')
+                                  f'the position derivative of its sampler{hint}')
+    contracted = _contracted(model)
+    if fused and contracted and not model.fused_march:
+        raise ValueError('refine_poses(fused=True) needs a DirectContractedVoxGO on the fused march (fused_march=True)')
     if fused and not getattr(model, 'fused', False):
         raise ValueError('refine_poses(fused=True) needs a model on the fused march (model.fused)')
     from .train import TrainStep, create_optimizer_or_freeze_model, render_loss
@@ -167,7 +187,8 @@ def refine_poses(model, refiner, images, cfg_train, render_kwargs, n_iters, n_ra
     opt_model = create_optimizer_or_freeze_model(model, cfg_train, 0) if (train_model and step is None) else None
     losses = []
     was = model.__dict__.get('fused_raygrad')          # (the class attribute unless somebody set it on the instance)
-    if fused:
+    fused_flag = fused and not contracted              # (the contracted model's render path is its own: fused_march)
+    if fused_flag:
         model.fused_raygrad = True
     try:
         for it in range(int(n_iters)):
@@ -196,7 +217,7 @@ def refine_poses(model, refiner, images, cfg_train, render_kwargs, n_iters, n_ra
             opt_pose.step()
             losses.append(loss.detach())
     finally:
-        if fused:
+        if fused_flag:
             if was is None:
                 del model.fused_raygrad
             else:

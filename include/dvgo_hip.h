@@ -41,7 +41,7 @@ extern "C" {
 /* version of this ABI; bumped on any signature change (6: the positional-encoding colour head; 7: the contracted
  * sampler and the distortion loss of unbounded scenes; 8: the tri-plane sampler; 9: the trilinear sample's gradient
  * with respect to the position; 10: the LIIF plane decoder; 11: the fused march's gradient with respect to its rays).
- * The two dvgo_plane_rows_*, the two dvgo_vm_*, the two dvgo_hash_*, the two dvgo_vm_density_*, the two dvgo_march_vm_density*, the two dvgo_march_contract_density* and the dvgo_contract_positions entries were added without a bump, unlike the additions before them: an
+ * The two dvgo_plane_rows_*, the two dvgo_vm_*, the two dvgo_hash_*, the two dvgo_vm_density_*, the two dvgo_march_vm_density*, the two dvgo_march_contract_density*, the dvgo_contract_positions and the two dvgo_contract_ray_bwd* entries were added without a bump, unlike the additions before them: an
  * existing test pins the value 11, and a library built before them is still caught at load, by the check that every declared entry is exported. */
 #define DVGO_ABI_VERSION 11
 int dvgo_abi_version(void);
@@ -999,6 +999,48 @@ int dvgo_march_contract_density_bwd(const dvgo_rec2_t* rec2, const int32_t* n2, 
 int dvgo_contract_positions(const float* rays_o, const float* rays_d, int64_t n_rays, const float* center,
                             const float* radius, const float* t_tab, int n_max, float bg_len, int l2,
                             const int64_t* ray_id, const int64_t* step_id, int64_t M, float* q, float* t, void* stream);
+
+/* ---------------------------------------------------------------------------------
+ * The contraction's ray gradient (csrc/contract_raygrad.hip): from dL/dq of
+ * the kept samples of the contracted space to dL/d rays_o and dL/d rays_d, summed per ray.  Camera-pose refinement of
+ * unbounded scenes.  Added without a bump of DVGO_ABI_VERSION, as the blocks above were.
+ * center, radius: HOST pointers (3 floats each); everything else is a device pointer.  rays_o, rays_d [N,3], t_tab [n_max],
+ * bg_len (b), l2: what the forward (dvgo_contract_emit, dvgo_march_contract_density) was given.
+ * The samples of ray r, in two forms that share one device body:
+ *   dvgo_contract_ray_bwd      rows off[r] .. off[r + 1] - 1 of grad_q [M,3] and step_id [M] (a ray-major list; off [N + 1]
+ *                              ascending).  off is clamped to [0, M]: no row outside grad_q is read.
+ *   dvgo_contract_ray_bwd_rec  the records of the fused march: record i < n2[r] of ray r is rec2[r * rec_stride + i], its step
+ *                              rec.step & 0x7fffffff, its row of grad_q2 [M2,3] is off2[r] + i (the rows
+ *                              dvgo_march_contract_density_bwd writes).  A ray whose rows would leave [0, M2) reads none of
+ *                              them and gets NaN.
+ * One wavefront per ray; lanes take 64 consecutive samples per chunk, chunks ascending.  Per sample with step k and row g,
+ * all in float32, no contraction, division and square root correctly rounded:
+ *     o', d', ||u||, p = o' + d' * t_tab[k], n: the forward's expressions and bits (csrc/contract_common.h), so `n <= 1` and
+ *       the arg-max axis are the forward's own choices
+ *     n <= 1 (n == 1 included):  h = g
+ *     n  > 1:  f  = ((1 + b) - b / n) / n;   f' = ((2 * b) / n - (1 + b)) / (n * n);   c = f' * ((px * gx + py * gy) + pz * gz)
+ *              l2 != 0:  h_a = f * g_a + (p_a / n) * c          for every axis a
+ *              l2 == 0:  h_a = f * g_a + (p_a < 0 ? -c : c)     for a = the LOWEST axis index with |p_a| == max|p|
+ *                        h_a = f * g_a                          for the other two
+ *     A = A + h;   B = B + t_tab[k] * h        (six accumulators per lane, carried across the chunks)
+ *   g == 0 contributes exact zeros.  After the last chunk one butterfly over the 64 lanes (v += shfl_xor(v, d), d = 32, 16,
+ *   .. 1) sums each accumulator, and one lane writes, with plain stores,
+ *     grad_o[r] = A / radius
+ *     grad_d[r] = ((B - d' * ((d'x * Bx + d'y * By) + d'z * Bz)) / ||u||) / radius      (the normalisation of d is differentiated:
+ *                                                                                        t_tab is a true constant)
+ *   A ray without samples gets exact zeros.  A step outside [0, n_max) reads nothing and makes both outputs of its ray NaN.
+ *   No atomics, no LDS, no workspace, nothing to zero beforehand: bitwise repeatable.
+ * n_rays == 0: no-op.  DVGO_EINVAL: negative n_rays, M, M2 or rec_stride, n_max <= 0, null pointers (grad_q / step_id, grad_q2 /
+ * rec2 may be NULL when M, M2 == 0).  DVGO_ERANGE: n_rays * 64 or rec_stride >= 2^31.  All of it is answered before any launch.
+ * --------------------------------------------------------------------------------- */
+int dvgo_contract_ray_bwd(const float* rays_o, const float* rays_d, int64_t n_rays, const float* center,
+                          const float* radius, const float* t_tab, int n_max, float bg_len, int l2, const float* grad_q,
+                          const int64_t* step_id, int64_t M, const int64_t* off, float* grad_o, float* grad_d,
+                          void* stream);
+int dvgo_contract_ray_bwd_rec(const float* rays_o, const float* rays_d, int64_t n_rays, const float* center,
+                              const float* radius, const float* t_tab, int n_max, float bg_len, int l2,
+                              const dvgo_rec2_t* rec2, const int32_t* n2, int64_t rec_stride, const int64_t* off2,
+                              const float* grad_q2, int64_t M2, float* grad_o, float* grad_d, void* stream);
 
 /* ---------------------------------------------------------------------------------
  * Total-variation and L1 regularisers of plane-shaped parameters, added to their gradients (csrc/plane_tv.hip; DESIGN.md
