@@ -195,6 +195,18 @@ __device__ __forceinline__ void march_pos(const float* __restrict__ start, const
   pz = fmaf(dir[3 * r + 2], dist, start[3 * r + 2]);
 }
 
+// MaskCache lookup of the fused marches and the contracted sampler, as maskcache_lookup_kernel (K8) forms it: the voxel
+// nearest to p, roundf(fmaf(p, scale, shift)), half away from 0.  Returns whether it lies inside the [mX, mY, mZ] mask and
+// leaves its byte's index in `idx`; the load is the caller's (march.hip requests the byte a chunk ahead).
+__device__ __forceinline__ bool dvgo_mask_index(float px, float py, float pz, float scx, float scy, float scz, float shx,
+                                                float shy, float shz, int mX, int mY, int mZ, int64_t& idx) {
+  const int i = (int)roundf(fmaf(px, scx, shx));
+  const int j = (int)roundf(fmaf(py, scy, shy));
+  const int k = (int)roundf(fmaf(pz, scz, shz));
+  idx = ((int64_t)i * mY + j) * mZ + k;
+  return (0 <= i) & (i < mX) & (0 <= j) & (j < mY) & (0 <= k) & (k < mZ);
+}
+
 // first index r in [0,n) with cum[r] > idx  (cum inclusive, non-decreasing)
 __device__ __forceinline__ int64_t dvgo_upper_bound(const int64_t* __restrict__ cum, int64_t n,
                                                     int64_t idx) {

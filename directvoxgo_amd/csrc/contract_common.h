@@ -65,9 +65,6 @@ __device__ __forceinline__ float contract_segment(float qx, float qy, float qz, 
 __device__ __forceinline__ bool contract_occupied(float qx, float qy, float qz, const uint8_t* __restrict__ mask, int mi,
                                                   int mj, int mk, float scx, float scy, float scz, float shx, float shy,
                                                   float shz) {
-  const int i = (int)roundf(fmaf(qx, scx, shx));
-  const int j = (int)roundf(fmaf(qy, scy, shy));
-  const int kk = (int)roundf(fmaf(qz, scz, shz));
-  return 0 <= i && i < mi && 0 <= j && j < mj && 0 <= kk && kk < mk &&
-         mask[(int64_t)i * mj * mk + (int64_t)j * mk + kk] != 0;
+  int64_t idx;
+  return dvgo_mask_index(qx, qy, qz, scx, scy, scz, shx, shy, shz, mi, mj, mk, idx) && mask[idx] != 0;
 }

@@ -18,13 +18,9 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "march_records.h"      // the lane mask, the suffix sum, the plain walk, the chunk commit and the backward chunk
 #include "scan.h"
 #include "xyz_corners.h"
-
-__device__ __forceinline__ unsigned long long lanemask_lt(int lane) {
-  return (lane == 0) ? 0ull : (~0ull >> (64 - lane));
-}
-
 
 // inclusive product scan across the wave
 __device__ __forceinline__ float wave_prod_scan(float v, int lane) {
@@ -34,20 +30,6 @@ __device__ __forceinline__ float wave_prod_scan(float v, int lane) {
     if (lane >= d) v *= o;
   }
   return v;
-}
-
-// exclusive suffix sum across the wave: sum of v over lanes > lane
-__device__ __forceinline__ float wave_suffix_excl(float v, int lane, float& total) {
-  float inc = v;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const float o = __shfl_down(inc, d);
-    if (lane + d < 64) inc += o;
-  }
-  total = dvgo_readlane_f(inc, 0);
-  float ex = __shfl_down(inc, 1);
-  if (lane == 63) ex = 0.0f;
-  return ex;
 }
 
 // Scratch records of ray r start at cum[r]-n_steps[r] (exact, ray-major M0 layout) when the
@@ -257,11 +239,9 @@ march_density_kernel(float* __restrict__ rays_start, float* __restrict__ rays_di
     bool keep = (step < ns) && !((P.mnx > px) | (P.mny > py) | (P.mnz > pz) | (P.mxx < px) | (P.mxy < py) | (P.mxz < pz));
     mb = 1;
     if (mask != nullptr && keep) {
-      const int i = (int)roundf(fmaf(px, P.scx, P.shx));
-      const int j = (int)roundf(fmaf(py, P.scy, P.shy));
-      const int k = (int)roundf(fmaf(pz, P.scz, P.shz));
-      keep = (0 <= i) & (i < P.mX) & (0 <= j) & (j < P.mY) & (0 <= k) & (k < P.mZ);
-      if (keep && !(P.experiment & 8)) mb = mask[((int64_t)i * P.mY + j) * P.mZ + k];
+      int64_t idx;
+      keep = dvgo_mask_index(px, py, pz, P.scx, P.scy, P.scz, P.shx, P.shy, P.shz, P.mX, P.mY, P.mZ, idx);
+      if (keep && !(P.experiment & 8)) mb = mask[idx];
     }
     return keep;
   };
@@ -308,17 +288,11 @@ march_density_kernel(float* __restrict__ rays_start, float* __restrict__ rays_di
         }
       }
       if (P.experiment & 2) { e = d * 0.01f; a = e * 0.5f; }
-      else {
-        e = expf(d + P.act_shift);
-        a = 1.0f - dvgo_pow_neg(1.0f + e, -P.interval);
-      }
+      else march_alpha(d, P.act_shift, P.interval, e, a);
       if (filt) keep = a > P.thres;
     }
-    // transmittance, in the reference's order and precision (K12, render_utils_kernel.cu:448-454):
-    //   T_cum = (float)((double)T_cum * (1. - alpha + 1e-10)), stop after the first sample with (double)T_cum < 1e-3.
-    // The double factor is lane-parallel; the float carry is walked over the KEPT lanes only (a dropped sample
-    // never enters compositing): each step is one exec-masked multiply on lane j and a v_readlane of the result,
-    // so T, the weights and every threshold decision are bit-identical to the serial code.
+    // transmittance (march_records.h: plain_walk states the rule): the double factor is lane-parallel, the float carry is
+    // walked over the KEPT lanes only
     const double f = 1.0 - (double)a + 1e-10;
     float T_before = 1.0f;
     int stop_lane = -1;
@@ -327,34 +301,13 @@ march_density_kernel(float* __restrict__ rays_start, float* __restrict__ rays_di
     } else if (FAST) {
       stop_lane = chain_walk(__ballot(keep), f, Tc, T_before);
     } else {
-      unsigned long long todo = __ballot(keep);
-      while (todo) {
-        const int j = __ffsll((long long)todo) - 1;
-        todo &= todo - 1;
-        float T_after = 1.0f;
-        if (lane == j) { T_before = Tc; T_after = (float)((double)Tc * f); }
-        Tc = dvgo_readlane_f(T_after, j);
-        // (double)T < 1e-3  <=>  T < 1e-3f for floats (1e-3f is the float just above the double 1e-3); T >= 0, so the
-        // ordered-unsigned compare of the bit patterns is the same test and stays on the scalar unit
-        if (__float_as_uint(Tc) < 0x3A83126Fu) { stop_lane = j; break; }
-      }
+      stop_lane = plain_walk(__ballot(keep), f, lane, Tc, T_before);
     }
-    const bool stop = stop_lane >= 0;
-    const bool valid2 = keep && (!stop || lane <= stop_lane);
-    const float w = T_before * a;
-    const bool keep3 = valid2 && (!filt || (w > P.thres));
-    const unsigned long long m2 = __ballot(valid2), m3 = __ballot(keep3);
-    const unsigned long long lt = lanemask_lt(lane);
-    if (valid2) {
-      dvgo_rec2_t r;
-      r.step = step | (keep3 ? (int32_t)0x80000000 : 0);
-      r.exp_d = e; r.alpha = a; r.T = T_before;
-      rec2[cs0 + c2 + __popcll(m2 & lt)] = r;
-    }
-    c2 += __popcll(m2);
-    c3 += __popcll(m3);
-    if (brick_cnt != nullptr) brick_emit<false>(valid2, t.i0, t.j0, t.k0, P.X, P.Y, P.Z, lane, brick_cnt, nullptr, make_int4(0, 0, 0, 0));
-    if (stop) break;
+    const MarchCommit cm = march_commit(keep, stop_lane, step, e, a, T_before, filt, P.thres, lane, lanemask_lt(lane), rec2,
+                                        cs0, c2, c3);
+    c2 = cm.c2; c3 = cm.c3;
+    if (brick_cnt != nullptr) brick_emit<false>(cm.valid2, t.i0, t.j0, t.k0, P.X, P.Y, P.Z, lane, brick_cnt, nullptr, make_int4(0, 0, 0, 0));
+    if (stop_lane >= 0) break;
   }
   if (lane == 0 && live) {
     n2[ray] = c2;
@@ -407,11 +360,9 @@ march_hit_kernel(const float* __restrict__ rays_start, const float* __restrict__
     const float px = fmaf(dx, dist, sx), py = fmaf(dy, dist, sy), pz = fmaf(dz, dist, sz);
     bool keep = (step < ns) && !((P.mnx > px) | (P.mny > py) | (P.mnz > pz) | (P.mxx < px) | (P.mxy < py) | (P.mxz < pz));
     if (keep) {
-      const int i = (int)roundf(fmaf(px, P.scx, P.shx));
-      const int j = (int)roundf(fmaf(py, P.scy, P.shy));
-      const int k = (int)roundf(fmaf(pz, P.scz, P.shz));
-      keep = (0 <= i) & (i < P.mX) & (0 <= j) & (j < P.mY) & (0 <= k) & (k < P.mZ);
-      if (keep) keep = mask[((int64_t)i * P.mY + j) * P.mZ + k] != 0;
+      int64_t idx;
+      keep = dvgo_mask_index(px, py, pz, P.scx, P.scy, P.scz, P.shx, P.shy, P.shz, P.mX, P.mY, P.mZ, idx);
+      if (keep) keep = mask[idx] != 0;
     }
     any = __ballot(keep) != 0ull;
   }
@@ -823,9 +774,8 @@ march_feat_bwd_dedup_kernel(const float* __restrict__ grad_feat, const float* __
 }
 
 // ----------------------------------------------------------------------------------
-// march_density_bwd: one wavefront per ray, rec2 chunks walked from the far end.
-//   K13 (render_utils_kernel.cu:521-530): g_alpha = g_w*T - acc/((1-alpha)+1e-10), acc += g_w*w
-//   K10 (:402-405) raw2alpha backward, then the 8-corner scatter into grad_density.
+// march_density_bwd: one wavefront per ray, rec2 chunks walked from the far end (march_records.h: march_bwd_chunk, K13 and
+// K10's raw2alpha backward), then the 8-corner scatter of g_d into grad_density.
 // ----------------------------------------------------------------------------------
 // DEDUP: the 8 x 64 corner contributions of a chunk are first merged in a per-wave LDS hash table
 // (single channel: ds_add_f32 on the slot is cheap here) and each distinct voxel is emitted once.
@@ -867,34 +817,14 @@ march_density_bwd_kernel(const dvgo_rec2_t* __restrict__ rec2, const int32_t* __
   float acc = (grad_last ? grad_last[ray] : 0.0f) * alphainv_last[ray];
   for (int hi = c2; hi > 0; hi -= 64) {
     const int lo = max(0, hi - 64);
-    const int n = hi - lo;
-    const bool act = lane < n;
-    dvgo_rec2_t rec;
-    rec.step = 0; rec.exp_d = 0.f; rec.alpha = 0.f; rec.T = 0.f;
-    if (act) rec = rec2[cs0 + lo + lane];
-    const bool flag = act && (rec.step < 0);
-    const int step = rec.step & 0x7fffffff;
-    const unsigned long long m = __ballot(flag);
-    const int cnt = __popcll(m);
-    const int rank = c3_rem - cnt + __popcll(m & lt);
-    c3_rem -= cnt;
-    const float gw = flag ? grad_weights[o3 + rank] : 0.0f;
-    const float w = rec.T * rec.alpha;
-    float total;
-    const float suffix = wave_suffix_excl(gw * w, lane, total);   // inactive lanes contribute 0
-    const float my_acc = acc + suffix;
-    acc += total;
+    const MarchBwdChunk ck = march_bwd_chunk(rec2, cs0, lo, hi - lo, lane, lt, o3, c3_rem, acc, grad_weights);
+    const bool act = ck.act, flag = ck.flag;
+    const int step = ck.step, rank = ck.rank;
     float g_d = 0.0f;
     TriSetup t;
     t.i0 = t.j0 = t.k0 = 0; t.gx = t.gy = t.gz = 0.f;
     if (act) {
-      const float gt = gw * rec.T;
-      const float one_minus = 1.0f - rec.alpha;
-      const float g_alpha = (float)((double)gt - (double)my_acc / ((double)one_minus + 1e-10));
-      double v = fmin((double)rec.exp_d, 1e10) * (double)dvgo_pow_neg(1.0f + rec.exp_d, -P.interval - 1.0f);
-      v = v * (double)P.interval;
-      v = v * (double)g_alpha;
-      g_d = (float)v;
+      g_d = ck.g_d(P.interval);
       const float dist = march_dist(P.stepdist, step);
       const float px = fmaf(dx, dist, sx), py = fmaf(dy, dist, sy), pz = fmaf(dz, dist, sz);
       t = dvgo_tri_setup(px, py, pz, P.mnx, P.mny, P.mnz, P.mxx, P.mxy, P.mxz, P.X, P.Y, P.Z);
@@ -948,8 +878,8 @@ march_density_bwd_kernel(const dvgo_rec2_t* __restrict__ rec2, const int32_t* __
 
 // ----------------------------------------------------------------------------------
 // march_ray_bwd: the derivative of the march with respect to its RAYS (camera-pose refinement, pose.py), the sibling of
-// march_density_bwd.  Same walk over the ray's rec2 records -- chunks of 64 from the far end, the same ballot, rank, suffix
-// sum and `acc`, g_d and the position p from the same expressions in the same order, hence with the same bits -- but where
+// march_density_bwd.  Same walk over the ray's rec2 records -- chunks of 64 from the far end through the same
+// march_bwd_chunk (march_records.h), the position p from the same expressions, hence the same bits -- but where
 // that kernel scatters g_d to the grid, this one keeps the record's position gradient
 //     g_p = scale * (g_d * d density / d g  +  sum_c grad_feat[kept, c] * d k0_c / d g)
 // (the corner chains of dvgo_grid_sample_bwd_xyz, xyz_corners.h: the density grid as the first channel, then, for a
@@ -996,32 +926,12 @@ march_ray_bwd_kernel(const dvgo_rec2_t* __restrict__ rec2, const int32_t* __rest
     float acc = (grad_last ? grad_last[ray] : 0.0f) * alphainv_last[ray];
     for (int hi = c2; hi > 0; hi -= 64) {
       const int lo = max(0, hi - 64);
-      const int n = hi - lo;
-      const bool act = lane < n;
-      dvgo_rec2_t rec;
-      rec.step = 0; rec.exp_d = 0.f; rec.alpha = 0.f; rec.T = 0.f;
-      if (act) rec = rec2[cs0 + lo + lane];
-      const bool flag = act && (rec.step < 0);
-      const int step = rec.step & 0x7fffffff;
-      const unsigned long long m = __ballot(flag);
-      const int cnt = __popcll(m);
-      const int rank = c3_rem - cnt + __popcll(m & lt);
-      c3_rem -= cnt;
-      const float gw = flag ? grad_weights[o3 + rank] : 0.0f;
-      const float w = rec.T * rec.alpha;
-      float total;
-      const float suffix = wave_suffix_excl(gw * w, lane, total);   // inactive lanes contribute 0
-      const float my_acc = acc + suffix;
-      acc += total;
+      const MarchBwdChunk ck = march_bwd_chunk(rec2, cs0, lo, hi - lo, lane, lt, o3, c3_rem, acc, grad_weights);
+      const bool act = ck.act, flag = ck.flag;
+      const int step = ck.step, rank = ck.rank;
       float gx = 0.f, gy = 0.f, gz = 0.f, lam = 0.f;
       if (act) {
-        const float gt = gw * rec.T;
-        const float one_minus = 1.0f - rec.alpha;
-        const float g_alpha = (float)((double)gt - (double)my_acc / ((double)one_minus + 1e-10));
-        double v = fmin((double)rec.exp_d, 1e10) * (double)dvgo_pow_neg(1.0f + rec.exp_d, -P.interval - 1.0f);
-        v = v * (double)P.interval;
-        v = v * (double)g_alpha;
-        const float g_d = (float)v;
+        const float g_d = ck.g_d(P.interval);
         const float dist = march_dist(P.stepdist, step);
         const float px = fmaf(dx, dist, sx), py = fmaf(dy, dist, sy), pz = fmaf(dz, dist, sz);
         const TriSetup t = dvgo_tri_setup(px, py, pz, P.mnx, P.mny, P.mnz, P.mxx, P.mxy, P.mxz, P.X, P.Y, P.Z);

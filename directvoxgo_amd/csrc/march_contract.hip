@@ -14,15 +14,18 @@
 //                               transmittance carry and the records (a wave-uniform branch), and nothing behind the stop is
 //                               visited: what the op-by-op path pays twice for all n_max steps of every ray, and then for every
 //                               occupied sample, this kernel pays only up to the surface.
-//   march_contract_density_bwd  one wavefront per ray over its records from the far end (march_records.h: the walk of
-//                               march_vm_density_bwd, the same g_d arithmetic); record i of ray r leaves its raw-density
+//   march_contract_density_bwd  one wavefront per ray over its records from the far end (march_records.h: march_records_bwd, the
+//                               walk of march_vm_density_bwd, on march_density_bwd's chunk); record i of ray r leaves its raw-density
 //                               gradient at g_raw[off2[r] + i] and its contracted position at q2[off2[r] + i].  No scatter, no
 //                               atomics, no LDS: bitwise repeatable.  The scatter into the grid is dvgo_grid_sample_bwd (C = 1).
 //   contract_positions          elementwise: q and t of kept (ray, step) pairs, the bits dvgo_contract_emit writes for them
 //                               (dvgo_march_gather rebuilds positions of uniform steps only; here it runs with no feature grid).
 //
-// The records, dvgo_march_gather, dvgo_march_composite and their backward are march.hip's, unchanged.  The transmittance
-// carry is march_density_kernel's plain ballot / readlane walk (its FAST == false body), restated.
+// The records, dvgo_march_gather, dvgo_march_composite and their backward are march.hip's, unchanged.  The activation
+// (the alpha filter is one compare behind it, here as there), the transmittance carry -- the plain ballot / readlane walk of
+// march_density_kernel's FAST == false body, not the hand-scheduled chain_walk -- and the commit of a chunk into the records
+// are the functions march.hip calls: march_records.h owns them, as common.h's dvgo_mask_index owns the occupancy lookup
+// behind contract_occupied.
 #include "contract_common.h"
 #include "march_records.h"
 
@@ -52,7 +55,7 @@ march_contract_density_kernel(const float* __restrict__ rays_o, const float* __r
   const int64_t YZ = (int64_t)P.Y * P.Z;
   const bool filt = P.thres > 0.0f;
   const bool pairs = P.Z >= 2;
-  const unsigned long long lt = mvm_lanemask_lt(lane);
+  const unsigned long long lt = lanemask_lt(lane);
 
   float lqx = 0.0f, lqy = 0.0f, lqz = 0.0f;      // q of the step before this chunk (q_k is a pure function of (ray, k): carried)
   float acc = 0.0f;                              // the thinning's accumulated distance: wave-uniform, carried
@@ -77,9 +80,13 @@ march_contract_density_kernel(const float* __restrict__ rays_o, const float* __r
     }
     const bool over = (over_m >> lane) & 1ull;
     bool keep = live && (inner || over);
-    if (keep && mask != nullptr)
+    if (keep && mask != nullptr) {
+      // dvgo_march_contract_density answers DVGO_EINVAL for a mask with mZ <= 0 before it launches (its `if (mask && ...)`
+      // check below): said here, the index product needs no sign word of mZ.  The assumption goes if that check ever does.
+      __builtin_assume(P.mZ > 0);
       keep = contract_occupied(qx, qy, qz, mask, P.mX, P.mY, P.mZ, P.scx, P.scy, P.scz, P.shx, P.shy, P.shz);
-    if (__ballot(keep) == 0ull) continue;          // nothing kept: no density read, nothing to carry or record
+    }
+    if (__ballot(keep) == 0ull) continue;         // nothing kept: no density read, nothing to carry or record
     float e = 0.f, a = 0.f;
     if (keep) {
       const TriSetup s = dvgo_tri_setup(qx, qy, qz, P.mnx, P.mny, P.mnz, P.mxx, P.mxy, P.mxz, P.X, P.Y, P.Z);
@@ -95,39 +102,17 @@ march_contract_density_kernel(const float* __restrict__ rays_o, const float* __r
           }
         }
       }
-      e = expf(dn + P.act_shift);
-      a = 1.0f - dvgo_pow_neg(1.0f + e, -P.interval);
+      march_alpha(dn, P.act_shift, P.interval, e, a);
       if (filt) keep = a > P.thres;
     }
-    // transmittance, in the reference's order and precision: T = (float)((double)T * (1. - alpha + 1e-10)), stop after the
-    // first sample with T < 1e-3; the float carry walks the kept lanes only (march.hip: march_density_kernel)
+    // transmittance: the float carry walks the kept lanes only; then the stop cut, the weight filter and the records
+    // (a ray writes at most n_max <= rec_stride of them)
     const double f = 1.0 - (double)a + 1e-10;
     float T_before = 1.0f;
-    int stop_lane = -1;
-    unsigned long long todo = __ballot(keep);
-    while (todo) {
-      const int j = __ffsll((long long)todo) - 1;
-      todo &= todo - 1;
-      float T_after = 1.0f;
-      if (lane == j) { T_before = Tc; T_after = (float)((double)Tc * f); }
-      Tc = dvgo_readlane_f(T_after, j);
-      // (double)T < 1e-3  <=>  T < 1e-3f for floats; T >= 0 (or NaN, which does not stop): unsigned compare of the bits
-      if (__float_as_uint(Tc) < 0x3A83126Fu) { stop_lane = j; break; }
-    }
-    const bool stop = stop_lane >= 0;
-    const bool valid2 = keep && (!stop || lane <= stop_lane);
-    const float w = T_before * a;
-    const bool keep3 = valid2 && (!filt || (w > P.thres));
-    const unsigned long long m2 = __ballot(valid2), m3 = __ballot(keep3);
-    if (valid2) {
-      dvgo_rec2_t r;
-      r.step = k | (keep3 ? (int32_t)0x80000000 : 0);
-      r.exp_d = e; r.alpha = a; r.T = T_before;
-      rec2[cs0 + c2 + __popcll(m2 & lt)] = r;      // c2 + rank < n_max <= rec_stride
-    }
-    c2 += __popcll(m2);
-    c3 += __popcll(m3);
-    if (stop) break;
+    const int stop_lane = plain_walk(__ballot(keep), f, lane, Tc, T_before);
+    const MarchCommit cm = march_commit(keep, stop_lane, k, e, a, T_before, filt, P.thres, lane, lt, rec2, cs0, c2, c3);
+    c2 = cm.c2; c3 = cm.c3;
+    if (stop_lane >= 0) break;
   }
   if (lane == 0) {
     n2[ray] = c2;

@@ -9,14 +9,17 @@
 //                         A chunk in which no lane survives box and mask skips the density loop (a wave-uniform branch), and
 //                         a ray never touches a chunk behind its stop: what the op-by-op path pays for every occupied sample
 //                         of every ray, this kernel pays only up to the surface.
-//   march_vm_density_bwd  one wavefront per ray over its records from the far end: march_density_bwd's walk, expression for
-//                         expression; record i of ray r leaves its raw-density gradient at g_raw[off2[r] + i] and its
-//                         position at xyz2[off2[r] + i].  No scatter, no atomics, no LDS: bitwise repeatable.  The scatter
-//                         into planes and lines is dvgo_vm_density_bwd on (g_raw, xyz2), which passes over exact zeros.
+//   march_vm_density_bwd  one wavefront per ray over its records from the far end: march_density_bwd's walk, chunk by
+//                         chunk the same function (march_records.h: march_bwd_chunk); record i of ray r leaves its
+//                         raw-density gradient at g_raw[off2[r] + i] and its position at xyz2[off2[r] + i].  No scatter, no
+//                         atomics, no LDS: bitwise repeatable.  The scatter into planes and lines is dvgo_vm_density_bwd on
+//                         (g_raw, xyz2), which passes over exact zeros.
 //
-// The records, dvgo_march_gather, dvgo_march_composite and their backward are march.hip's, unchanged.  The transmittance
-// carry is march_density_kernel's plain ballot / readlane walk (its FAST == false body), restated.
-#include "march_records.h"      // the lane mask, the suffix sum and the backward walk: shared with march_contract.hip
+// The records, dvgo_march_gather, dvgo_march_composite and their backward are march.hip's, unchanged.  The occupancy lookup
+// (common.h: dvgo_mask_index), the activation (the alpha filter is one compare behind it, here as there), the transmittance
+// carry -- the plain ballot / readlane walk of march_density_kernel's FAST == false body, not the hand-scheduled chain_walk --
+// and the commit of a chunk into the records are the functions march.hip calls: march_records.h owns them.
+#include "march_records.h"
 #include "vm_common.h"
 
 struct MarchVmParams {
@@ -54,7 +57,7 @@ march_vm_density_kernel(TpPlane PA, TpPlane PB, TpPlane PC, VmLine LA, VmLine LB
   const int ns = __builtin_amdgcn_readfirstlane((int)(S.n < rec_stride ? S.n : rec_stride));
   const int64_t cs0 = ray * rec_stride;
   const bool filt = P.thres > 0.0f;
-  const unsigned long long lt = mvm_lanemask_lt(lane);
+  const unsigned long long lt = lanemask_lt(lane);
 
   float Tc = 1.0f;
   int c2 = 0, c3 = 0;
@@ -64,11 +67,9 @@ march_vm_density_kernel(TpPlane PA, TpPlane PB, TpPlane PC, VmLine LA, VmLine LB
     const float px = fmaf(dx, dist, sx), py = fmaf(dy, dist, sy), pz = fmaf(dz, dist, sz);
     bool keep = (step < ns) && !((P.mnx > px) | (P.mny > py) | (P.mnz > pz) | (P.mxx < px) | (P.mxy < py) | (P.mxz < pz));
     if (mask != nullptr && keep) {
-      const int i = (int)roundf(fmaf(px, P.scx, P.shx));
-      const int j = (int)roundf(fmaf(py, P.scy, P.shy));
-      const int k = (int)roundf(fmaf(pz, P.scz, P.shz));
-      keep = (0 <= i) & (i < P.mX) & (0 <= j) & (j < P.mY) & (0 <= k) & (k < P.mZ);
-      if (keep) keep = mask[((int64_t)i * P.mY + j) * P.mZ + k] != 0;
+      int64_t idx;
+      keep = dvgo_mask_index(px, py, pz, P.scx, P.scy, P.scz, P.shx, P.shy, P.shz, P.mX, P.mY, P.mZ, idx);
+      if (keep) keep = mask[idx] != 0;
     }
     if (__ballot(keep) == 0ull) continue;          // empty or masked-out chunk: no density loop, nothing to carry or record
     float e = 0.f, a = 0.f;
@@ -93,39 +94,16 @@ march_vm_density_kernel(TpPlane PA, TpPlane PB, TpPlane PC, VmLine LA, VmLine LB
           for (int i = 0; i < VEC; ++i) acc = fmaf(p.v[i], l.v[i], acc);
         }
       }
-      e = expf(acc + P.act_shift);
-      a = 1.0f - dvgo_pow_neg(1.0f + e, -P.interval);
+      march_alpha(acc, P.act_shift, P.interval, e, a);
       if (filt) keep = a > P.thres;
     }
-    // transmittance, in the reference's order and precision: T = (float)((double)T * (1. - alpha + 1e-10)), stop after the
-    // first sample with T < 1e-3; the float carry walks the kept lanes only (march.hip: march_density_kernel)
+    // transmittance: the float carry walks the kept lanes only; then the stop cut, the weight filter and the records
     const double f = 1.0 - (double)a + 1e-10;
     float T_before = 1.0f;
-    int stop_lane = -1;
-    unsigned long long todo = __ballot(keep);
-    while (todo) {
-      const int j = __ffsll((long long)todo) - 1;
-      todo &= todo - 1;
-      float T_after = 1.0f;
-      if (lane == j) { T_before = Tc; T_after = (float)((double)Tc * f); }
-      Tc = dvgo_readlane_f(T_after, j);
-      // (double)T < 1e-3  <=>  T < 1e-3f for floats; T >= 0 (or NaN, which does not stop): unsigned compare of the bits
-      if (__float_as_uint(Tc) < 0x3A83126Fu) { stop_lane = j; break; }
-    }
-    const bool stop = stop_lane >= 0;
-    const bool valid2 = keep && (!stop || lane <= stop_lane);
-    const float w = T_before * a;
-    const bool keep3 = valid2 && (!filt || (w > P.thres));
-    const unsigned long long m2 = __ballot(valid2), m3 = __ballot(keep3);
-    if (valid2) {
-      dvgo_rec2_t r;
-      r.step = step | (keep3 ? (int32_t)0x80000000 : 0);
-      r.exp_d = e; r.alpha = a; r.T = T_before;
-      rec2[cs0 + c2 + __popcll(m2 & lt)] = r;
-    }
-    c2 += __popcll(m2);
-    c3 += __popcll(m3);
-    if (stop) break;
+    const int stop_lane = plain_walk(__ballot(keep), f, lane, Tc, T_before);
+    const MarchCommit cm = march_commit(keep, stop_lane, step, e, a, T_before, filt, P.thres, lane, lt, rec2, cs0, c2, c3);
+    c2 = cm.c2; c3 = cm.c3;
+    if (stop_lane >= 0) break;
   }
   if (lane == 0) {
     n2[ray] = c2;

@@ -34,27 +34,35 @@ from .ops import _grid_geom
 _MAX_STRIDE_SCRATCH_BYTES = 4 << 30
 
 
-class MarchConfig:
-    """Host-side constants of one model/render setting (model constants travel to the fused
-    kernels as kernel arguments, so they are kept as host arrays here)."""
+class _MarchConstants:
+    """What the config of every fused march holds: the bounds of the grids, the activation's constants and the occupancy mask
+    with its scale / shift.  Model constants travel to the fused kernels as kernel arguments, so they are kept as host arrays;
+    the device tensors serve the ops that take them from memory (the prepare kernel, dvgo_grid_sample_bwd)."""
 
-    def __init__(self, xyz_min, xyz_max, stepdist, act_shift, interval, fast_color_thres, near, far,
-                 mask=None, xyz2ijk_scale=None, xyz2ijk_shift=None, ndc_samples=0):
-        self.xyz_min_t, self.xyz_max_t = xyz_min, xyz_max          # device tensors (prepare kernel)
-        self.xyz_min_h, self.xyz_max_h = f3(xyz_min), f3(xyz_max)  # host copies (fused kernels)
-        self.stepdist = float(stepdist)
+    def __init__(self, xyz_min, xyz_max, act_shift, interval, fast_color_thres, mask, xyz2ijk_scale, xyz2ijk_shift):
+        self.xyz_min_t, self.xyz_max_t = xyz_min, xyz_max
+        self.xyz_min_h, self.xyz_max_h = f3(xyz_min), f3(xyz_max)
         self.act_shift = float(act_shift)
         self.interval = float(interval)
         self.thres = float(fast_color_thres)
+        self.mask = mask
+        self.scale_h = f3(xyz2ijk_scale) if mask is not None else f3([0, 0, 0])
+        self.shift_h = f3(xyz2ijk_shift) if mask is not None else f3([0, 0, 0])
+
+
+class MarchConfig(_MarchConstants):
+    """Host-side constants of one model/render setting."""
+
+    def __init__(self, xyz_min, xyz_max, stepdist, act_shift, interval, fast_color_thres, near, far,
+                 mask=None, xyz2ijk_scale=None, xyz2ijk_shift=None, ndc_samples=0):
+        super().__init__(xyz_min, xyz_max, act_shift, interval, fast_color_thres, mask, xyz2ijk_scale, xyz2ijk_shift)
+        self.stepdist = float(stepdist)
         self.near, self.far = float(near), float(far)
         # > 0: forward-facing / MPI sampling (lib/dmpigo.py:173-198): every ray has exactly ndc_samples
         # samples at o + d * s/(ndc_samples-1); encoded for the kernels as stepdist = -(ndc_samples-1)
         self.ndc_samples = int(ndc_samples)
         if self.ndc_samples > 0:
             self.stepdist = -float(self.ndc_samples - 1)
-        self.mask = mask
-        self.scale_h = f3(xyz2ijk_scale) if mask is not None else f3([0, 0, 0])
-        self.shift_h = f3(xyz2ijk_shift) if mask is not None else f3([0, 0, 0])
 
 
 def _rec_stride(cfg, n_rays):
@@ -487,6 +495,36 @@ def fused_march(density, k0, rays_o, rays_d, cfg, capacity=False, positions=Fals
     return _FusedMarch.apply(density, k0, rays_o.contiguous(), rays_d.contiguous(), cfg, capacity, positions)
 
 
+def _records_to_samples(rec2, n2, n3, off3, off2, N, stride, cfg, st, start, dirs, stepdist, n_steps=None):
+    """The forward tail of the record-per-gradient marches (_FusedMarchVM, _FusedMarchContract): the per-ray counts become
+    offsets (n3 -> off3, n2 -> off2), ONE host read brings both totals -- M3 (kept samples, sizes the outputs) and M2
+    (records, sizes the backward's per-record gradient) -- and dvgo_march_gather compacts the kept records into
+    ray_id / step_id / weights / alpha.  -> M3, M2, ray_id, step_id, weights, alpha.
+    The gather runs with no feature grid: zero channels of a 1 x 1 x 1 lattice.  In that mode it forms a uniform-step
+    position from `start`, `dirs` and `stepdist` and uses it for nothing, so a march whose steps are not uniform passes any
+    [N,3] floats for the first two (its rays_o / rays_d), and with a fixed stride it never reads `n_steps`: left out,
+    off3 stands in (any non-null int64 pointer)."""
+    dev = rec2.device
+    L.call('dvgo_exclusive_scan_i32', n3, N, off3, st)
+    torch.cumsum(n2, 0, dtype=torch.int64, out=off2[1:])
+    M3, M2 = torch.stack((off3[N], off2[N])).tolist()          # the one host read: both counts
+    ray_id = torch.empty(M3, dtype=torch.int64, device=dev)
+    step_id = torch.empty(M3, dtype=torch.int64, device=dev)
+    weights = torch.empty(M3, dtype=torch.float32, device=dev)
+    alpha = torch.empty(M3, dtype=torch.float32, device=dev)
+    L.call('dvgo_march_gather', rec2, n2, n_steps if n_steps is not None else off3, None, stride, off3, N, M3, start, dirs,
+           stepdist, cfg.xyz_min_h, cfg.xyz_max_h, None, 0, 1, 1, 1, 1, 1, 1, 1, ray_id, step_id, weights, alpha, None, st)
+    return M3, M2, ray_id, step_id, weights, alpha
+
+
+def _record_grads(g_w, g_last, M3, M2, dev):
+    """The backward preamble of the same marches -> gw [M3] (zeros when `weights` took no gradient), gl [N] or None, and
+    the two per-record outputs of the walk, uninitialised: g_raw [M2] and the positions [M2, 3]."""
+    gw = g_w.contiguous() if g_w is not None else torch.zeros(M3, dtype=torch.float32, device=dev)
+    gl = g_last.contiguous() if g_last is not None else None
+    return gw, gl, torch.empty(M2, dtype=torch.float32, device=dev), torch.empty((M2, 3), dtype=torch.float32, device=dev)
+
+
 class _FusedMarchVM(torch.autograd.Function):
     """csrc/march_vm.hip: the march over TensoRFVoxGO's decomposed density.  Two host-visible counts, read together: M3
     (kept samples, sizes the outputs) and M2 (records, sizes the backward's per-record gradient)."""
@@ -525,16 +563,8 @@ class _FusedMarchVM(torch.autograd.Function):
                    g[8], g[9], g[10], g[11], g[12], g[13], g[14], g[15], g[16], g[17], g[18], g[19], g[20], g[21], g[22], g[23],
                    g[24], g[25], g[26], g[27], g[28], g[29], R, cfg.act_shift, cfg.interval, cfg.thres, rec2, n2, n3, last,
                    rays_o, rays_d, cfg.near, cfg.far, st)
-            L.call('dvgo_exclusive_scan_i32', n3, N, off3, st)
-            torch.cumsum(n2, 0, dtype=torch.int64, out=off2[1:])
-            M3, M2 = torch.stack((off3[N], off2[N])).tolist()          # the one host read: both counts
-            ray_id = torch.empty(M3, dtype=torch.int64, device=dev)
-            step_id = torch.empty(M3, dtype=torch.int64, device=dev)
-            weights = torch.empty(M3, dtype=torch.float32, device=dev)
-            alpha = torch.empty(M3, dtype=torch.float32, device=dev)
-            # no feature grid: zero channels of a 1 x 1 x 1 lattice
-            L.call('dvgo_march_gather', rec2, n2, n_steps, None, stride, off3, N, M3, start, dirs, cfg.stepdist, cfg.xyz_min_h,
-                   cfg.xyz_max_h, None, 0, 1, 1, 1, 1, 1, 1, 1, ray_id, step_id, weights, alpha, None, st)
+            M3, M2, ray_id, step_id, weights, alpha = _records_to_samples(rec2, n2, n3, off3, off2, N, stride, cfg, st, start,
+                                                                          dirs, cfg.stepdist, n_steps=n_steps)
             pts = march_positions(start, dirs, ray_id, step_id, cfg.stepdist)
         ctx.cfg, ctx.counts = cfg, (stride, N, M2, M3)
         ctx.save_for_backward(rec2, n2, n_steps, off3, off2, start, dirs, last, *kt)
@@ -555,10 +585,7 @@ class _FusedMarchVM(torch.autograd.Function):
         dev = start.device
         grads = _vm_grad_buffers(kt)                  # one zero fill for the six
         if M2 > 0:
-            gw = g_w.contiguous() if g_w is not None else torch.zeros(M3, dtype=torch.float32, device=dev)
-            gl = g_last.contiguous() if g_last is not None else None
-            g_raw = torch.empty(M2, dtype=torch.float32, device=dev)
-            xyz2 = torch.empty((M2, 3), dtype=torch.float32, device=dev)
+            gw, gl, g_raw, xyz2 = _record_grads(g_w, g_last, M3, M2, dev)
             with L.device_of(start):
                 L.call('dvgo_march_vm_density_bwd', rec2, n2, n_steps, stride, off3, off2, N, start, dirs, cfg.stepdist, last,
                        cfg.interval, gw, gl, g_raw, xyz2, stream_of(start))
@@ -585,12 +612,11 @@ def fused_march_vm(density_planes, density_lines, rays_o, rays_d, cfg):
                                *_plane_list(density_planes), *_plane_list(density_lines))
 
 
-class ContractMarchConfig:
+class ContractMarchConfig(_MarchConstants):
     """Host-side constants of one DirectContractedVoxGO render setting, beside `MarchConfig`: the foreground box as centre and
     radius, the distance table `t_tab` [n_max] (device, float32) and the thinning distance `thin_thres` of
     dcvgo.contracted_t_table / thinning_threshold, `bg_len`, the norm ('inf' | 'l2'), the CONTRACTED bounds of the grids,
-    the activation's constants and the occupancy mask with its scale / shift.  Model constants travel to the kernels as
-    arguments, so they are kept as host arrays; the device tensors serve the existing ops of the backward."""
+    the activation's constants and the occupancy mask with its scale / shift."""
 
     def __init__(self, center, radius, t_tab, bg_len, contracted_norm, thin_thres, xyz_min, xyz_max, act_shift, interval,
                  fast_color_thres, mask=None, xyz2ijk_scale=None, xyz2ijk_shift=None):
@@ -598,18 +624,11 @@ class ContractMarchConfig:
             raise ValueError(f"contracted_norm must be 'inf' or 'l2', got {contracted_norm!r}")
         if t_tab.dim() != 1 or t_tab.dtype != torch.float32 or not t_tab.is_contiguous():
             raise RuntimeError('t_tab must be a contiguous float32 vector')
+        super().__init__(xyz_min, xyz_max, act_shift, interval, fast_color_thres, mask, xyz2ijk_scale, xyz2ijk_shift)
         self.center_h, self.radius_h = f3(center), f3(radius)
         self.t_tab, self.n_max = t_tab, int(t_tab.shape[0])
         self.bg_len, self.l2 = float(bg_len), 1 if contracted_norm == 'l2' else 0
         self.thin_thres = float(thin_thres)
-        self.xyz_min_t, self.xyz_max_t = xyz_min, xyz_max          # device tensors (dvgo_grid_sample_bwd)
-        self.xyz_min_h, self.xyz_max_h = f3(xyz_min), f3(xyz_max)
-        self.act_shift = float(act_shift)
-        self.interval = float(interval)
-        self.thres = float(fast_color_thres)
-        self.mask = mask
-        self.scale_h = f3(xyz2ijk_scale) if mask is not None else f3([0, 0, 0])
-        self.shift_h = f3(xyz2ijk_shift) if mask is not None else f3([0, 0, 0])
 
 
 class _FusedMarchContract(torch.autograd.Function):
@@ -638,20 +657,11 @@ class _FusedMarchContract(torch.autograd.Function):
             L.call('dvgo_march_contract_density', rays_o, rays_d, N, cfg.center_h, cfg.radius_h, cfg.t_tab, cfg.n_max, cfg.bg_len,
                    cfg.l2, cfg.thin_thres, mask, mshape[0], mshape[1], mshape[2], cfg.scale_h, cfg.shift_h, density, X, Y, Z,
                    cfg.xyz_min_h, cfg.xyz_max_h, cfg.act_shift, cfg.interval, cfg.thres, stride, rec2, n2, n3, last, st)
-            L.call('dvgo_exclusive_scan_i32', n3, N, off3, st)
-            torch.cumsum(n2, 0, dtype=torch.int64, out=off2[1:])
-            M3, M2 = torch.stack((off3[N], off2[N])).tolist()          # the one host read: both counts
-            ray_id = torch.empty(M3, dtype=torch.int64, device=dev)
-            step_id = torch.empty(M3, dtype=torch.int64, device=dev)
-            weights = torch.empty(M3, dtype=torch.float32, device=dev)
-            alpha = torch.empty(M3, dtype=torch.float32, device=dev)
+            # (the table's steps are not uniform: rays_o / rays_d stand in for the gather's start / direction)
+            M3, M2, ray_id, step_id, weights, alpha = _records_to_samples(rec2, n2, n3, off3, off2, N, stride, cfg, st, rays_o,
+                                                                          rays_d, 1.0)
             q = torch.empty((M3, 3), dtype=torch.float32, device=dev)
             t = torch.empty(M3, dtype=torch.float32, device=dev)
-            # no feature grid: zero channels of a 1 x 1 x 1 lattice.  In that mode the gather forms a uniform-step position from
-            # the start and direction it is given and uses it for nothing (rays_o / rays_d stand in: any [N,3] floats), and
-            # with a fixed stride it never reads n_steps (off3 stands in: any non-null int64 pointer).
-            L.call('dvgo_march_gather', rec2, n2, off3, None, stride, off3, N, M3, rays_o, rays_d, 1.0, cfg.xyz_min_h,
-                   cfg.xyz_max_h, None, 0, 1, 1, 1, 1, 1, 1, 1, ray_id, step_id, weights, alpha, None, st)
             L.call('dvgo_contract_positions', rays_o, rays_d, N, cfg.center_h, cfg.radius_h, cfg.t_tab, cfg.n_max, cfg.bg_len,
                    cfg.l2, ray_id, step_id, M3, q, t, st)
         ctx.cfg, ctx.counts, ctx.geom = cfg, (stride, N, M2, M3), (X, Y, Z)
@@ -676,10 +686,7 @@ class _FusedMarchContract(torch.autograd.Function):
         grad_density = torch.zeros_like(density, memory_format=torch.contiguous_format) if want_density else None
         grad_o = grad_d = None
         if M2 > 0 and (g_w is not None or g_last is not None):
-            gw = g_w.contiguous() if g_w is not None else torch.zeros(M3, dtype=torch.float32, device=dev)
-            gl = g_last.contiguous() if g_last is not None else None
-            g_raw = torch.empty(M2, dtype=torch.float32, device=dev)
-            q2 = torch.empty((M2, 3), dtype=torch.float32, device=dev)
+            gw, gl, g_raw, q2 = _record_grads(g_w, g_last, M3, M2, dev)
             with L.device_of(rays_o):
                 st = stream_of(rays_o)
                 L.call('dvgo_march_contract_density_bwd', rec2, n2, stride, off3, off2, N, rays_o, rays_d, cfg.center_h,

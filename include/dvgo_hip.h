@@ -915,14 +915,17 @@ int dvgo_vm_density_bwd(const float* grad_out,
  *       acc) -- the same bits as that entry gives for the same position, whatever the layout or alignment (16-byte loads
  *       under its rule, element loads otherwise);
  *     exp_d = expf(raw + act_shift), alpha = 1 - (1 + exp_d)^(-interval) (the power of dvgo_raw2alpha);
- *     T, the stop at T < 1e-3, the two filters and bit 31 of the record's step: as dvgo_march_density.
+ *     T, the stop at T < 1e-3, the two filters and bit 31 of the record's step: as dvgo_march_density -- the occupancy
+ *       index, the activation, the transmittance walk and the commit into the records are the functions that kernel calls
+ *       (csrc/common.h: dvgo_mask_index; csrc/march_records.h), not copies of them.
  *   A chunk of 64 steps none of which passes box and mask reads no plane or line, and no chunk behind the ray's stop is
  *   visited.  Bitwise repeatable.
  * dvgo_march_vm_density_bwd: rec2, n2, n_steps, rec_stride, off3, rays_start, rays_dir, stepdist, alphainv_last, interval,
  *   grad_weights, grad_last as dvgo_march_density_bwd, from the same forward (n_steps is not read: the records are at
- *   r * rec_stride); off2 [N + 1] the exclusive scan of n2, M2 = off2[N].  The walk is dvgo_march_density_bwd's, expression
- *   for expression: chunks of 64 records from the far end, rank of a flagged record from off3, the suffix sum of g_w * w over
- *   the lanes above by a shuffle tree, acc += the chunk's total, then
+ *   r * rec_stride); off2 [N + 1] the exclusive scan of n2, M2 = off2[N].  The walk is dvgo_march_density_bwd's, the same
+ *   function chunk by chunk (csrc/march_records.h owns it for every march): chunks of 64 records from the far end, rank of
+ *   a flagged record from off3, the suffix sum of g_w * w over the lanes above by a shuffle tree, acc += the chunk's total,
+ *   then
  *     g_alpha = (float)((double)(g_w * T) - (double)(acc + suffix) / ((double)(1 - alpha) + 1e-10))
  *     g_raw   = (float)(min((double)exp_d, 1e10) * (double)pow(1 + exp_d, -interval - 1) * interval * g_alpha)
  *   Record i of ray r writes g_raw[off2[r] + i] and its position xyz2[off2[r] + i] (the forward's expression: the same bits).
@@ -969,15 +972,16 @@ int dvgo_march_vm_density_bwd(const dvgo_rec2_t* rec2, const int32_t* n2, const 
  *     raw = the trilinear sample of density [X,Y,Z] (contiguous) at q_k over [xyz_min, xyz_max]: the bits dvgo_grid_sample_fwd
  *       gives at that position;  exp_d = expf(raw + act_shift), alpha = 1 - (1 + exp_d)^(-interval) (dvgo_raw2alpha's power,
  *       `interval` constant: stepsize * voxel_size_ratio);
- *     T, the stop at T < 1e-3, the two filters and bit 31 of the record's step (= k): as dvgo_march_density.
+ *     T, the stop at T < 1e-3, the two filters and bit 31 of the record's step (= k): as dvgo_march_density, through the
+ *       same functions (csrc/march_records.h; the occupancy index: csrc/common.h, dvgo_mask_index).
  *   Records of ray r at rec2[r * rec_stride ...], rec_stride >= n_max.  n2, n3 [N] int32, alphainv_last [N].
  *   A chunk in which no step is kept reads no density, and no chunk behind the ray's stop is visited (the thinning walk runs
  *   in every chunk that is visited).  Bitwise repeatable.
  * dvgo_march_contract_density_bwd: the walk of dvgo_march_vm_density_bwd over the same records, the same g_alpha and g_raw
- *   expressions (csrc/march_records.h is both kernels' one copy).  Record i of ray r writes g_raw[off2[r] + i] and its
- *   contracted position q2[off2[r] + i] = q_k of its step, the forward's bits.  off3 / off2 [N + 1]: exclusive scans of n3 /
- *   n2.  Nothing is scattered: no atomics, no LDS, bitwise repeatable, every one of the M2 rows written.  The gradient of the
- *   grid is dvgo_grid_sample_bwd(g_raw, C = 1, ..., q2, xyz_min, xyz_max, M2, ...).
+ *   expressions (csrc/march_records.h is their one copy, dvgo_march_density_bwd's too).  Record i of ray r writes
+ *   g_raw[off2[r] + i] and its contracted position q2[off2[r] + i] = q_k of its step, the forward's bits.  off3 / off2
+ *   [N + 1]: exclusive scans of n3 / n2.  Nothing is scattered: no atomics, no LDS, bitwise repeatable, every one of the M2
+ *   rows written.  The gradient of the grid is dvgo_grid_sample_bwd(g_raw, C = 1, ..., q2, xyz_min, xyz_max, M2, ...).
  * dvgo_contract_positions: elementwise over M pairs (ray_id, step_id): q [M,3] = q_k and t [M] = t_tab[k], the bits
  *   dvgo_contract_emit writes for that ray and step.  A pair outside [0, n_rays) x [0, n_max) reads nothing and gets NaN.
  * n_rays == 0 (M == 0): no-op.  DVGO_EINVAL: negative n_rays or M, n_max <= 0, rec_stride < n_max, X, Y or Z <= 0, null
