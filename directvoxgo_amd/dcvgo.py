@@ -30,7 +30,7 @@ Rays that require grad are refused, unless `raygrad=True`.  INTEGRATION.md secti
 
 `raygrad=True` (constructor option, default False; a plain attribute like `fused_march`, not a `get_kwargs` key and not in
 checkpoints: pass it to the constructor or to `load_model(..., raygrad=True)`): with grad mode on and `rays_o` or `rays_d`
-requiring grad, `forward` differentiates the render with respect to the rays, on either path (`_forward_raygrad` states the
+requiring grad, `forward` differentiates the render with respect to the rays, on either path (`_render` states the
 stop-gradients and the tie rule).  The sample positions are wrapped in ops.contract_points, whose backward is
 csrc/contract_raygrad.hip; on the fused march the density's share comes from the march's own backward
 (fused.fused_march_contract(..., raygrad=True)).  Every result key keeps the bits of the forward without the option, and
@@ -45,8 +45,8 @@ import torch.nn.functional as F
 from . import _lib as L
 from ._lib import _flt, _i64, _int, check_f32, check_input, ptr, stream_of
 from .fused import ContractMarchConfig, composite, fused_march_contract
-from .ops import contract_points
-from .voxel_model import VoxelModel, _as_f32, _result
+from .ops import contract_points, ray_offsets
+from .voxel_model import VoxelModel, _as_f32, _check_rays, _rays_want_grad
 
 
 def contracted_t_table(world, stepsize, bg_len):
@@ -217,75 +217,61 @@ class DirectContractedVoxGO(VoxelModel):
 
     def _march_contract_cfg(self, stepsize, device):
         """The fused march's constants for this step size, cached until the grids, the mask or the device change."""
-        key = (float(stepsize), str(device))
-        cfg = self._cfg_cache.get(key)
-        if cfg is None or cfg.mask is not self.mask_cache.mask:
+        def make():
             t_tab, _, thres = self._table(stepsize, device)
-            mc = self.mask_cache
-            cfg = self._cfg_cache[key] = ContractMarchConfig(
+            return ContractMarchConfig(
                 self.scene_center, self.scene_radius, t_tab, self.bg_len, self.contracted_norm, thres, self.xyz_min,
                 self.xyz_max, self.act_shift, float(stepsize * self.voxel_size_ratio), self.fast_color_thres,
-                mask=mc.mask, xyz2ijk_scale=mc.xyz2ijk_scale, xyz2ijk_shift=mc.xyz2ijk_shift)
-        return cfg
+                **self._mask_args())
+        return self._cached_cfg((float(stepsize), str(device)), make)
 
     def forward(self, rays_o, rays_d, viewdirs, global_step=None, **render_kwargs):
         """Volume rendering in contracted space; see the module docstring for the order and the extra keys.
-        `near` / `far` in render_kwargs are ignored; `ndc` rays are not supported."""
-        assert len(rays_o.shape) == 2 and rays_o.shape[-1] == 3, 'Only suuport point queries in [N, 3] format'
-        stepsize = render_kwargs['stepsize']
-        ray_grad = torch.is_grad_enabled() and (rays_o.requires_grad or rays_d.requires_grad)
-        if ray_grad and self.raygrad:
-            return self._forward_raygrad(rays_o, rays_d, viewdirs, stepsize, render_kwargs['bg'],
-                                         render_kwargs.get('render_depth', False))
-        if self.fused_march:
-            if ray_grad:
+        `near` / `far` in render_kwargs are ignored; `ndc` rays are not supported.  With grad mode on, rays that require
+        grad and `raygrad=True` the sample positions are wrapped in ops.contract_points (`_render` states what that means)."""
+        _check_rays(rays_o)
+        stepsize, wrap = render_kwargs['stepsize'], None
+        if _rays_want_grad(rays_o, rays_d):
+            if self.raygrad:
+                rays_o, rays_d, viewdirs = rays_o.contiguous(), rays_d.contiguous(), viewdirs.detach()
+                t_tab = self._table(stepsize, rays_o.device)[0]
+                wrap = lambda q, ray_id, step_id: contract_points(      # noqa: E731
+                    rays_o, rays_d, ray_id, step_id, q, self.scene_center_h, self.scene_radius_h, t_tab, self.bg_len,
+                    self.contracted_norm)
+            elif self.fused_march:
                 raise NotImplementedError('DirectContractedVoxGO(fused_march=True): rays that require grad are not '
                                           'differentiated through the contraction: construct it with raygrad=True')
-            cfg = self._march_contract_cfg(stepsize, self.density.device)
-            march = fused_march_contract(self.density, rays_o, rays_d, cfg)
-            if march is not None:
-                weights, alpha, alphainv_last, q, ray_id, step_id, t, _ = march
-                rgb = self._shade(self.grid_sampler(q, self.k0), viewdirs, ray_id)
-                ret = self._sum_rays(len(rays_o), weights, alpha, alphainv_last, rgb, ray_id, render_kwargs['bg'],
-                                     render_kwargs.get('render_depth', False), step_id, t)
-                ret['n_max'] = cfg.n_max
-                return ret
-        q, ray_id, step_id, t, n_max = self.sample_ray(rays_o, rays_d, stepsize)
-        ret = self._forward_unfused(len(rays_o), viewdirs, stepsize, render_kwargs['bg'],
-                                    render_kwargs.get('render_depth', False), q, ray_id, step_id, t)
-        ret['n_max'] = n_max
-        return ret
+        return self._render(rays_o, rays_d, viewdirs, stepsize, render_kwargs['bg'], render_kwargs.get('render_depth', False),
+                            wrap)
 
-    def _forward_raygrad(self, rays_o, rays_d, viewdirs, stepsize, bg, render_depth):
-        """`forward` for rays that require grad (raygrad=True): the same launches and the same bits in every result key as
-        the forward without, on sample positions that autograd knows as the contraction of their rays (ops.contract_points;
-        csrc/contract_raygrad.hip), sampled through the position-differentiable trilinear op (csrc/grid_sample_xyz.hip).
-        Stop-gradients, by contract:
+    def _render(self, rays_o, rays_d, viewdirs, stepsize, bg, render_depth, wrap=None):
+        """The fused march where the model has it and its records fit, else the sampler and the op-by-op sequence.
+
+        `wrap` (rays that require grad, raygrad=True; None for a plain render): the same launches and the same bits in
+        every result key as the forward without, on sample positions that autograd knows as the contraction of their rays
+        (ops.contract_points; csrc/contract_raygrad.hip), sampled through the position-differentiable trilinear op
+        (csrc/grid_sample_xyz.hip).  On the fused march the density's share of the ray gradient comes from the march's own
+        backward, k0's through the wrapped positions.  Stop-gradients, by contract:
           * the table of distances `t` is a constant (so the normalisation of rays_d IS differentiated, unlike
             DirectVoxGO._forward_raygrad's lam);
           * the set of kept samples is fixed: thinning, occupancy and both fast_color_thres filters select rows;
           * `s` and `depth` carry no gradient: the distortion loss reaches the rays through `weights` only;
           * viewdirs carries no gradient (the colour heads have no input gradient for the view embedding).
         At an inf-norm tie the lowest axis index attaining max|p_a| carries the norm's derivative; n == 1 is the identity."""
-        rays_o, rays_d, viewdirs = rays_o.contiguous(), rays_d.contiguous(), viewdirs.detach()
-        N, dev = len(rays_o), self.density.device
-        t_tab, n_max, _ = self._table(stepsize, rays_o.device)
-        wrap = lambda q, ray_id, step_id: contract_points(      # noqa: E731
-            rays_o, rays_d, ray_id, step_id, q, self.scene_center_h, self.scene_radius_h, t_tab, self.bg_len,
-            self.contracted_norm)
+        N = len(rays_o)
         if self.fused_march:
-            cfg = self._march_contract_cfg(stepsize, dev)
-            march = fused_march_contract(self.density, rays_o, rays_d, cfg, raygrad=True)
+            cfg = self._march_contract_cfg(stepsize, self.density.device)
+            march = fused_march_contract(self.density, rays_o, rays_d, cfg, raygrad=wrap is not None)
             if march is not None:
-                # the density's share of the ray gradient comes from the march's own backward; k0's through the wrapped q
                 weights, alpha, alphainv_last, q, ray_id, step_id, t, _ = march
-                rgb = self._shade(self.grid_sampler(wrap(q, ray_id, step_id), self.k0), viewdirs, ray_id)
+                rgb = self._colour(q if wrap is None else wrap(q, ray_id, step_id), None, viewdirs, ray_id)
                 ret = self._sum_rays(N, weights, alpha, alphainv_last, rgb, ray_id, bg, render_depth, step_id, t)
                 ret['n_max'] = cfg.n_max
                 return ret
-        with torch.no_grad():
+        with torch.no_grad():                                 # the sampler's outputs are constants either way
             q, ray_id, step_id, t, n_max = self.sample_ray(rays_o, rays_d, stepsize)
-        ret = self._forward_unfused(N, viewdirs, stepsize, bg, render_depth, wrap(q, ray_id, step_id), ray_id, step_id, t)
+        ret = self._forward_unfused(N, viewdirs, stepsize, bg, render_depth, q if wrap is None else wrap(q, ray_id, step_id),
+                                    ray_id, step_id, t)
         ret['n_max'] = n_max
         return ret
 
@@ -306,14 +292,13 @@ class DirectContractedVoxGO(VoxelModel):
         return self._tab_cache[key]
 
     def _sum_rays(self, N, weights, alpha, alphainv_last, rgb, ray_id, bg, render_depth, step_id, t):
-        """Per-ray sums in fixed order (the march's composite over the ray offsets): bitwise repeatable renders."""
-        dev = weights.device
-        off = torch.searchsorted(ray_id, torch.arange(N + 1, dtype=torch.int64, device=dev))
-        rgb_marched = composite(weights, rgb, alphainv_last, ray_id, off, bg)
-        ret = _result(alphainv_last, weights, rgb_marched, alpha, rgb, ray_id)
+        """Per-ray sums in fixed order (the march's composite over the ray offsets): bitwise repeatable renders.  The
+        depth is this model's own: it sums `t`, not `step_id`."""
+        off = ray_offsets(ray_id, N)
+        ret = self._finish_marched(N, weights, alpha, alphainv_last, rgb, ray_id, step_id, off, bg, False)
         ret.update(step_id=step_id, t=t, s=1 - 1 / (1 + t))
         if render_depth:
             with torch.no_grad():
                 t3 = t.unsqueeze(-1).expand(-1, 3).contiguous()
-                ret['depth'] = composite(weights.detach(), t3, torch.zeros(N, device=dev), ray_id, off, 0.0)[:, 0]
+                ret['depth'] = composite(weights.detach(), t3, torch.zeros(N, device=weights.device), ray_id, off, 0.0)[:, 0]
         return ret

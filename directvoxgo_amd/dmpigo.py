@@ -94,13 +94,7 @@ class DirectMPIGO(VoxelModel):
     def _march_cfg(self, near, far, stepsize):
         """The fused march with NDC spacing (include/dvgo_hip.h, `stepdist < 0`): a fixed number of samples per ray."""
         assert near == 0 and far == 1
-        key = float(stepsize)
-        cfg = self._cfg_cache.get(key)
-        if cfg is None or cfg.mask is not self.mask_cache.mask:
-            mc = self.mask_cache
-            cfg = MarchConfig(self.xyz_min, self.xyz_max, stepdist=1.0, act_shift=0.0,
-                              interval=float(stepsize * self.voxel_size_ratio), fast_color_thres=self.fast_color_thres,
-                              near=0.0, far=1.0, mask=mc.mask, xyz2ijk_scale=mc.xyz2ijk_scale,
-                              xyz2ijk_shift=mc.xyz2ijk_shift, ndc_samples=self.n_samples(stepsize))
-            self._cfg_cache[key] = cfg
-        return cfg
+        return self._cached_cfg(float(stepsize), lambda: MarchConfig(
+            self.xyz_min, self.xyz_max, stepdist=1.0, act_shift=0.0, interval=float(stepsize * self.voxel_size_ratio),
+            fast_color_thres=self.fast_color_thres, near=0.0, far=1.0, ndc_samples=self.n_samples(stepsize),
+            **self._mask_args()))

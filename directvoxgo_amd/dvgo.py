@@ -32,7 +32,8 @@ from ._lib import _flt, _i64, _int, f3, ptr, stream_of
 from .fused import MarchConfig, fused_hit
 from .ops import ray_points
 from .shade import head_layers
-from .voxel_model import VoxelModel, _freqs, make_rgbnet, mlp_forward  # noqa: F401 (tests and tools import the last two from here)
+from .voxel_model import (VoxelModel, _check_rays, _freqs, _rays_want_grad,  # noqa: F401 (tests and tools import the last two
+                          make_rgbnet, mlp_forward)                        # from here)
 
 
 class DirectVoxGO(VoxelModel):
@@ -197,8 +198,7 @@ class DirectVoxGO(VoxelModel):
         whatever `self.fused` says) the render is also differentiable with respect to the rays: see `_forward_raygrad`.
         With `fused_raygrad` set on a fused model such rays take the fused forward instead, rays attached and `viewdirs`
         detached: the same stop-gradients, the derivative from the march's own backward."""
-        if (torch.is_grad_enabled() and (rays_o.requires_grad or rays_d.requires_grad) and type(self) is DirectVoxGO
-                and self.posbase_pe == 0):
+        if _rays_want_grad(rays_o, rays_d) and type(self) is DirectVoxGO and self.posbase_pe == 0:
             if self.fused_raygrad and self.fused and not self.uses_posenc:
                 return super().forward(rays_o, rays_d, viewdirs.detach(), global_step=global_step, **render_kwargs)
             return self._forward_raygrad(rays_o, rays_d, viewdirs, **render_kwargs)
@@ -213,7 +213,7 @@ class DirectVoxGO(VoxelModel):
           * the set of kept samples is fixed: the in-box test, the occupancy mask and both fast_color_thres filters select
             rows and are not differentiated;
           * viewdirs carries no gradient (the colour heads have no input gradient for the view embedding)."""
-        assert len(rays_o.shape) == 2 and rays_o.shape[-1] == 3, 'Only suuport point queries in [N, 3] format'
+        _check_rays(rays_o)
         rays_o, rays_d = rays_o.contiguous(), rays_d.contiguous()
         stepdist = stepsize * self.voxel_size
         with torch.no_grad():
@@ -236,18 +236,13 @@ class DirectVoxGO(VoxelModel):
         return self.rgbnet is not None and self.posbase_pe > 0
 
     def _march_cfg(self, near, far, stepsize):
-        key = (float(near), float(far), float(stepsize))
-        cfg = self._cfg_cache.get(key)
-        if cfg is None or cfg.mask is not (self.mask_cache.mask if self.mask_cache is not None else None):
-            mc = self.mask_cache
-            cfg = MarchConfig(self.xyz_min, self.xyz_max, stepdist=float(stepsize * self.voxel_size),
-                              act_shift=self.act_shift, interval=float(stepsize * self.voxel_size_ratio),
-                              fast_color_thres=self.fast_color_thres, near=near, far=far,
-                              mask=None if mc is None else mc.mask,
-                              xyz2ijk_scale=None if mc is None else mc.xyz2ijk_scale,
-                              xyz2ijk_shift=None if mc is None else mc.xyz2ijk_shift)
-            self._cfg_cache[key] = cfg
-        return cfg
+        return self._cached_cfg((float(near), float(far), float(stepsize)),
+                                lambda: self._new_march_cfg(near, far, stepsize, self.act_shift))
+
+    def _new_march_cfg(self, near, far, stepsize, act_shift):
+        return MarchConfig(self.xyz_min, self.xyz_max, stepdist=float(stepsize * self.voxel_size), act_shift=act_shift,
+                           interval=float(stepsize * self.voxel_size_ratio), fast_color_thres=self.fast_color_thres,
+                           near=near, far=far, **self._mask_args())
 
     def can_keep_count_on_device(self):
         """True when `forward(..., _capacity=True)` is available: the fused march with the fused colour head."""

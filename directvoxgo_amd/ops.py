@@ -301,6 +301,29 @@ def _vm_args(planes, lines, xyz):
     return planes, lines, geom, R, xyz.shape[0]
 
 
+def _vm_tensors(planes, lines):
+    """The checks of `vm_sample` and `vm_density` ahead of their autograd functions -> the three planes, then the three lines."""
+    tensors = _plane_list(planes) + _plane_list(lines)
+    for ln, k in zip(tensors[3:], PLANE_KEYS):             # shapes before devices
+        if ln.dim() != 4 or ln.shape[0] != 1 or ln.shape[3] != 1:
+            raise RuntimeError(f'{k}_line must be [1,R,N,1]')
+    for p, k in zip(tensors[:3], PLANE_KEYS):
+        _plane_geom(p, k)
+    for ln, k in zip(tensors[3:], PLANE_KEYS):
+        _line_geom(ln, k + '_line')
+    return tensors
+
+
+def _vm_grad_args(tensors, grad_planes, grad_lines):
+    """The six gradient buffers of `vm_bwd` and `vm_density_bwd`, checked against the planes and lines they belong to."""
+    grad_planes, grad_lines = _plane_list(grad_planes), _plane_list(grad_lines)
+    for t, g in zip(tensors, grad_planes + grad_lines):
+        if g.shape != t.shape or g.dtype != torch.float32 or g.device != t.device or \
+                any(a != b for a, b, n in zip(g.stride(), t.stride(), t.shape) if n > 1):
+            raise RuntimeError('a gradient buffer must have the shape, strides, dtype and device of the tensor it belongs to')
+    return grad_planes, grad_lines
+
+
 def vm_fwd(planes, lines, xyz, xyz_min, xyz_max):
     """dvgo_vm_fwd on the strides as they are: planes [1,R,H,W], lines [1,R,N,1], xyz [M,3] -> [M,3R], plane value times
     line value per component (xy, yz, zx; include/dvgo_hip.h has the arithmetic).  No autograd."""
@@ -316,11 +339,7 @@ def vm_bwd(grad_out, planes, lines, grad_planes, grad_lines, xyz, xyz_min, xyz_m
     lines they belong to) in place.  `run`: samples a lane merges before its atomics; `mode`: 1 all sums to global memory,
     2 the line sums through a table in LDS (0: the library's choice, for both)."""
     planes, lines, geom, R, M = _vm_args(planes, lines, xyz)
-    grad_planes, grad_lines = _plane_list(grad_planes), _plane_list(grad_lines)
-    for t, g in zip(planes + lines, grad_planes + grad_lines):
-        if g.shape != t.shape or g.dtype != torch.float32 or g.device != t.device or \
-                any(a != b for a, b, n in zip(g.stride(), t.stride(), t.shape) if n > 1):
-            raise RuntimeError('a gradient buffer must have the shape, strides, dtype and device of the tensor it belongs to')
+    grad_planes, grad_lines = _vm_grad_args(planes + lines, grad_planes, grad_lines)
     check_input(grad_out, 'grad_out'); check_f32(grad_out, 'grad_out')
     if tuple(grad_out.shape) != (M, 3 * R):
         raise RuntimeError('grad_out has the wrong shape')
@@ -352,14 +371,7 @@ def vm_sample(planes, lines, xyz, xyz_min, xyz_max):
     dict with the keys 'xy', 'yz', 'zx' (or the three in that order), each [1,R,N,1], line s running along the world axis
     plane s does not see (xy: x, yz: z, zx: y); xyz [...,3] world coordinates -> [...,3R]: per component the plane's
     bilinear value times the line's linear value, in the order xy, yz, zx.  Differentiable w.r.t. planes and lines only."""
-    tensors = _plane_list(planes) + _plane_list(lines)
-    for ln, k in zip(tensors[3:], PLANE_KEYS):             # shapes before devices
-        if ln.dim() != 4 or ln.shape[0] != 1 or ln.shape[3] != 1:
-            raise RuntimeError(f'{k}_line must be [1,R,N,1]')
-    for p, k in zip(tensors[:3], PLANE_KEYS):
-        _plane_geom(p, k)
-    for ln, k in zip(tensors[3:], PLANE_KEYS):
-        _line_geom(ln, k + '_line')
+    tensors = _vm_tensors(planes, lines)
     shape = xyz.shape[:-1]
     flat = xyz.reshape(-1, 3).contiguous()
     out = _VMSample.apply(flat, xyz_min.contiguous(), xyz_max.contiguous(), *tensors)
@@ -372,9 +384,7 @@ def vm_density_fwd(planes, lines, xyz, xyz_min, xyz_max):
     planes, lines, g, R, M = _vm_args(planes, lines, xyz)
     out = torch.empty((M,), dtype=torch.float32, device=xyz.device)
     with L.device_of(xyz):
-        L.call('dvgo_vm_density_fwd', g[0], g[1], g[2], g[3], g[4], g[5], g[6], g[7], g[8], g[9], g[10], g[11], g[12], g[13],
-               g[14], g[15], g[16], g[17], g[18], g[19], g[20], g[21], g[22], g[23], g[24], g[25], g[26], g[27], g[28], g[29],
-               R, xyz, xyz_min, xyz_max, M, out, stream_of(xyz))
+        L.call('dvgo_vm_density_fwd', *g, R, xyz, xyz_min, xyz_max, M, out, stream_of(xyz))
     return out
 
 
@@ -382,19 +392,12 @@ def vm_density_bwd(grad_out, planes, lines, grad_planes, grad_lines, xyz, xyz_mi
     """dvgo_vm_density_bwd: `vm_bwd` with one float of incoming gradient per sample, grad_out [M]; samples whose gradient
     is exactly 0 are passed over.  Accumulates into the six buffers in place; `run` and `mode` as in `vm_bwd`."""
     planes, lines, g, R, M = _vm_args(planes, lines, xyz)
-    gp, gl = _plane_list(grad_planes), _plane_list(grad_lines)
-    for t, b in zip(planes + lines, gp + gl):
-        if b.shape != t.shape or b.dtype != torch.float32 or b.device != t.device or \
-                any(x != y for x, y, n in zip(b.stride(), t.stride(), t.shape) if n > 1):
-            raise RuntimeError('a gradient buffer must have the shape, strides, dtype and device of the tensor it belongs to')
+    gp, gl = _vm_grad_args(planes + lines, grad_planes, grad_lines)
     check_input(grad_out, 'grad_out'); check_f32(grad_out, 'grad_out')
     if tuple(grad_out.shape) != (M,):
         raise RuntimeError('grad_out has the wrong shape')
     with L.device_of(xyz):
-        L.call('dvgo_vm_density_bwd', grad_out, g[0], g[1], g[2], g[3], g[4], g[5], g[6], g[7], g[8], g[9], g[10], g[11],
-               g[12], g[13], g[14], g[15], g[16], g[17], g[18], g[19], g[20], g[21], g[22], g[23], g[24], g[25], g[26], g[27],
-               g[28], g[29], gp[0], gp[1], gp[2], gl[0], gl[1], gl[2], R, xyz, xyz_min, xyz_max, M, int(run), int(mode),
-               stream_of(xyz))
+        L.call('dvgo_vm_density_bwd', grad_out, *g, *gp, *gl, R, xyz, xyz_min, xyz_max, M, int(run), int(mode), stream_of(xyz))
     return gp, gl
 
 
@@ -436,14 +439,7 @@ def vm_density(planes, lines, xyz, xyz_min, xyz_max):
     """TensoRF's vector-matrix density as one HIP op: `planes` and `lines` as in `vm_sample`; xyz [...,3] world coordinates
     -> [...]: the sum over the three planes and their R components of plane value times line value, summed on chip (no
     [M, 3R] intermediate, forward or backward).  Differentiable w.r.t. planes and lines only."""
-    tensors = _plane_list(planes) + _plane_list(lines)
-    for ln, k in zip(tensors[3:], PLANE_KEYS):             # shapes before devices
-        if ln.dim() != 4 or ln.shape[0] != 1 or ln.shape[3] != 1:
-            raise RuntimeError(f'{k}_line must be [1,R,N,1]')
-    for p, k in zip(tensors[:3], PLANE_KEYS):
-        _plane_geom(p, k)
-    for ln, k in zip(tensors[3:], PLANE_KEYS):
-        _line_geom(ln, k + '_line')
+    tensors = _vm_tensors(planes, lines)
     shape = xyz.shape[:-1]
     flat = xyz.reshape(-1, 3).contiguous()
     return _VMDensity.apply(flat, xyz_min.contiguous(), xyz_max.contiguous(), *tensors).reshape(shape)
@@ -830,6 +826,11 @@ def segment_coo(src, index, out, reduce='sum'):
     return _SegmentSum.apply(src.contiguous(), index, out)
 
 
+def ray_offsets(ray_id, N):
+    """[N + 1] int64: where each ray's samples start in the sorted `ray_id` (what a fused march returns as off3)."""
+    return torch.searchsorted(ray_id, torch.arange(N + 1, device=ray_id.device))
+
+
 def _segment_sum3(src, ray_id, n):
     out = torch.zeros((n, 3), dtype=torch.float32, device=src.device)
     with L.device_of(src):
@@ -898,7 +899,7 @@ class _ContractPoints(torch.autograd.Function):
         center, radius, bg_len, l2 = ctx.consts
         N, dev = rays_o.shape[0], rays_o.device
         g = g.contiguous()
-        off = torch.searchsorted(ray_id, torch.arange(N + 1, dtype=torch.int64, device=dev))
+        off = ray_offsets(ray_id, N)
         grad_o = torch.empty((N, 3), dtype=torch.float32, device=dev)       # every row is written by the kernel
         grad_d = torch.empty((N, 3), dtype=torch.float32, device=dev)
         with L.device_of(rays_o):

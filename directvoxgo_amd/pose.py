@@ -145,7 +145,7 @@ def refine_poses(model, refiner, images, cfg_train, render_kwargs, n_iters, n_ra
 
     A `DirectContractedVoxGO(raygrad=True)` (unbounded scenes) renders by its own path, fused march or op by op as it was
     constructed, with the rays differentiated through the contraction (csrc/contract_raygrad.hip;
-    DirectContractedVoxGO._forward_raygrad states the stop-gradients).  `fused=True` then requires `model.fused_march`
+    DirectContractedVoxGO._render states the stop-gradients).  `fused=True` then requires `model.fused_march`
     (ValueError otherwise) and, with `train_model`, steps the model by a `train.TrainStep`, whose plan for this model is dense
     gradients and the optimizer's own step; `cfg_train['weight_distortion']` adds the distortion loss as in training.
 

@@ -38,10 +38,10 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from .fused import MarchConfig, composite, composite_depth, fused_march_vm
-from .ops import PLANE_KEYS, MaskCache, Raw2Alpha, vm_density
+from .fused import fused_march_vm
+from .ops import PLANE_KEYS, Raw2Alpha, vm_density
 from .triplane import PLANE_AXES
-from .voxel_model import _result
+from .voxel_model import _check_rays, _rays_want_grad
 from .vm import LINE_AXIS, VM_FINE_TRAIN, VMTriPlaneVoxGO
 
 # VM_FINE_TRAIN with TensoRF's published rate for its grids, 2e-2, on the density planes and lines as well.  The paper's
@@ -120,8 +120,7 @@ class TensoRFVoxGO(VMTriPlaneVoxGO):
         planes, lines = self._density_tensors(feats)
         return vm_density(planes, lines, pts, self.xyz_min, self.xyz_max)
 
-    def _raw_density(self, pts, feats):
-        return self.raw_density(pts, feats)
+    _raw_density = raw_density
 
     def activate_density(self, density, interval=None):
         """The base's Raw2Alpha with the shift act_shift + density_offset."""
@@ -146,11 +145,6 @@ class TensoRFVoxGO(VMTriPlaneVoxGO):
 
     def _pooled_alpha(self):
         return F.max_pool3d(self.activate_density(self.dense_density()), kernel_size=3, padding=1, stride=1)
-
-    def _set_mask_cache(self, mask):
-        self.mask_cache = MaskCache(path=None, mask=mask.cpu(), xyz_min=self._xyz_min_cpu,
-                                    xyz_max=self._xyz_max_cpu).to(self.xyz_min.device)
-        self._cfg_cache = {}
 
     # ------------------------------------------------------------------ grid maintenance
     def _resize_density(self, ws):
@@ -212,32 +206,21 @@ class TensoRFVoxGO(VMTriPlaneVoxGO):
         """The base's MarchConfig (`_march_cfg`, which `hit_coarse_geo` keeps using) with the shift of `activate_density`,
         act_shift + density_offset, formed as it forms it (one float64 sum, narrowed once at the library boundary: the
         same float32).  Cached per (near, far, stepsize, density_offset); `_set_mask_cache` empties the cache."""
-        key = ('vm', float(near), float(far), float(stepsize), self.density_offset)
-        cfg = self._cfg_cache.get(key)
-        if cfg is None or cfg.mask is not self.mask_cache.mask:
-            mc = self.mask_cache
-            cfg = MarchConfig(self.xyz_min, self.xyz_max, stepdist=float(stepsize * self.voxel_size),
-                              act_shift=self.act_shift + self.density_offset, interval=float(stepsize * self.voxel_size_ratio),
-                              fast_color_thres=self.fast_color_thres, near=near, far=far, mask=mc.mask,
-                              xyz2ijk_scale=mc.xyz2ijk_scale, xyz2ijk_shift=mc.xyz2ijk_shift)
-            self._cfg_cache[key] = cfg
-        return cfg
+        return self._cached_cfg(('vm', float(near), float(far), float(stepsize), self.density_offset),
+                                lambda: self._new_march_cfg(near, far, stepsize, self.act_shift + self.density_offset))
 
     def render(self, feats, rays_o, rays_d, viewdirs, global_step=None, **render_kwargs):
         """The base's result dict from either path of this model (module docstring).  `feats`: the colour planes and
         lines as in the base and, beside them, density tensors under the keys of `raw_density`."""
-        assert len(rays_o.shape) == 2 and rays_o.shape[-1] == 3, 'Only suuport point queries in [N, 3] format'
+        _check_rays(rays_o)
         if self.fused_march:
-            if torch.is_grad_enabled() and (rays_o.requires_grad or rays_d.requires_grad):
+            if _rays_want_grad(rays_o, rays_d):
                 self._refuse('rays that require grad', 'has no derivative of its density with respect to the sample positions')
             cfg = self._march_vm_cfg(render_kwargs['near'], render_kwargs['far'], render_kwargs['stepsize'])
             march = fused_march_vm(*self._density_tensors(feats), rays_o, rays_d, cfg)
             if march is not None:                   # None: no fixed record stride for these render_kwargs -> op by op
                 weights, alpha, alphainv_last, pts, ray_id, step_id, off3 = march
-                rgb = self._shade(self._head_features(pts, feats), viewdirs, ray_id)
-                ret = _result(alphainv_last, weights, composite(weights, rgb, alphainv_last, ray_id, off3, render_kwargs['bg']),
-                              alpha, rgb, ray_id)
-                if render_kwargs.get('render_depth', False):
-                    ret['depth'] = composite_depth(weights.detach(), step_id, off3, len(rays_o))
-                return ret
+                rgb = self._colour(pts, feats, viewdirs, ray_id)
+                return self._finish_marched(len(rays_o), weights, alpha, alphainv_last, rgb, ray_id, step_id, off3,
+                                            render_kwargs['bg'], render_kwargs.get('render_depth', False))
         return self._render_unfused(feats, rays_o, rays_d, viewdirs, global_step, **render_kwargs)

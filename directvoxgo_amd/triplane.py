@@ -27,10 +27,10 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from .dvgo import DirectVoxGO
-from .fused import composite, composite_depth, fused_march
-from .ops import PLANE_KEYS, Alphas2Weights, plane_reg_add_grad, triplane_sample
+from .fused import fused_march
+from .ops import PLANE_KEYS, plane_reg_add_grad, triplane_sample
 from .train import FINE_TRAIN
-from .voxel_model import VoxelModel, _freqs, _result, make_rgbnet
+from .voxel_model import VoxelModel, _check_rays, _freqs, make_rgbnet
 
 # which world axis the rows (H) and the columns (W) of each plane follow
 PLANE_AXES = {'xy': (1, 2), 'yz': (0, 1), 'zx': (2, 0)}
@@ -223,53 +223,22 @@ class TriPlaneVoxGO(DirectVoxGO):
         """lib/tri_dvgo.py:688-809.  `feats`: the three planes {'xy', 'yz', 'zx'}, each [1, rgbnet_dim, H, W] (any sizes;
         gradients flow into them).  Returns the reference's dict: alphainv_last [N], weights [M], rgb_marched [N,3],
         raw_alpha [M], raw_rgb [M,3], ray_id [M] (+ depth [N] when render_kwargs['render_depth'])."""
-        assert len(rays_o.shape) == 2 and rays_o.shape[-1] == 3, 'Only suuport point queries in [N, 3] format'
-        N = len(rays_o)
-        bg, render_depth = render_kwargs['bg'], render_kwargs.get('render_depth', False)
+        _check_rays(rays_o)
         if self.fused:
             cfg = self._march_cfg(render_kwargs['near'], render_kwargs['far'], render_kwargs['stepsize'])
             # the march writes the kept samples' positions where it would write k0 features; the stand-in has no channel
             no_k0 = self.density.detach()[:, :0]
             weights, alpha, alphainv_last, pts, ray_id, step_id, off3 = fused_march(
                 self.density, no_k0, rays_o, rays_d, cfg, positions=True)
-            rgb = self._shade(self._head_features(pts, feats), viewdirs, ray_id)
-            ret = _result(alphainv_last, weights, composite(weights, rgb, alphainv_last, ray_id, off3, bg), alpha, rgb, ray_id)
-            if render_depth:
-                ret['depth'] = composite_depth(weights.detach(), step_id, off3, N)
-            return ret
+            rgb = self._colour(pts, feats, viewdirs, ray_id)
+            return self._finish_marched(len(rays_o), weights, alpha, alphainv_last, rgb, ray_id, step_id, off3,
+                                        render_kwargs['bg'], render_kwargs.get('render_depth', False))
         return self._render_unfused(feats, rays_o, rays_d, viewdirs, global_step, **render_kwargs)
 
-    def _raw_density(self, pts, feats):
-        """The raw density at `pts` on the op-by-op path (a subclass whose density is not a grid says its own)."""
-        return self.grid_sampler(pts, self.density)
+    _sum_rays = VoxelModel._sum_rays_in_order      # both paths then agree bit for bit in rgb_marched
 
-    def _render_unfused(self, feats, rays_o, rays_d, viewdirs, global_step=None, **render_kwargs):
-        """The reference's op sequence on the drop-in ops (`fused=False`)."""
-        N = len(rays_o)
-        bg, render_depth = render_kwargs['bg'], render_kwargs.get('render_depth', False)
-        pts, ray_id, step_id = self.sample_ray(rays_o=rays_o, rays_d=rays_d, is_train=global_step is not None, **render_kwargs)
-        if self.mask_cache is not None:                      # skip known free space
-            mask = self.mask_cache(pts)
-            pts, ray_id, step_id = pts[mask], ray_id[mask], step_id[mask]
-        alpha = self.activate_density(self._raw_density(pts, feats), render_kwargs['stepsize'] * self.voxel_size_ratio)
-        if self.fast_color_thres > 0:
-            mask = alpha > self.fast_color_thres
-            pts, ray_id, step_id, alpha = pts[mask], ray_id[mask], step_id[mask], alpha[mask]
-        weights, alphainv_last = Alphas2Weights.apply(alpha, ray_id, N)
-        if self.fast_color_thres > 0:
-            mask = weights > self.fast_color_thres
-            pts, ray_id, step_id, alpha, weights = pts[mask], ray_id[mask], step_id[mask], alpha[mask], weights[mask]
-        rgb = self._shade(self._head_features(pts, feats), viewdirs, ray_id)
-        return self._sum_rays(N, weights, alpha, alphainv_last, rgb, ray_id, bg, render_depth, step_id)
-
-    def _sum_rays(self, N, weights, alpha, alphainv_last, rgb, ray_id, bg, render_depth, step_id):
-        """lib/tri_dvgo.py:786-808 with the fused path's own per-ray sum (fused.composite: one ray's samples in order) in
-        place of segment_coo, whose atomics sum in another order: the two paths then agree bit for bit in rgb_marched."""
-        off3 = torch.searchsorted(ray_id, torch.arange(N + 1, device=ray_id.device))       # ray_id is sorted
-        ret = _result(alphainv_last, weights, composite(weights, rgb, alphainv_last, ray_id, off3, bg), alpha, rgb, ray_id)
-        if render_depth:
-            ret['depth'] = composite_depth(weights.detach(), step_id, off3, N)
-        return ret
+    def _colour(self, pts, feats, viewdirs, ray_id):
+        return self._shade(self._head_features(pts, feats), viewdirs, ray_id)
 
     def _head_features(self, pts, feats):
         """What the colour head reads of a sample before the view embedding: the plane features (a subclass may append)."""

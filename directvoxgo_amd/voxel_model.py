@@ -1,16 +1,24 @@
-"""VoxelModel: what the three scene models share, once.
+"""VoxelModel: what the scene models share, once.
 
-A scene model here is a density grid, a colour (or feature) grid `k0` with an optional shallow MLP behind it, and an
-occupancy `mask_cache`, all over one axis-aligned box, volume-rendered along rays.  `VoxelModel` owns the box buffers and
-their host copies, grid allocation / resizing / the occupancy mask rebuilt from the grids, the colour head and its
-construction, the op wrappers, and the two ways a forward ends:
+A scene model here is a density, colour features (a grid `k0`, planes, a hash table) with an optional shallow MLP behind
+them, and an occupancy `mask_cache`, all over one axis-aligned box, volume-rendered along rays.  `VoxelModel` owns the box
+buffers and their host copies, grid allocation / resizing / the occupancy mask rebuilt from the grids, the colour head and
+its construction, the op wrappers, and the render skeleton:
 
-  `_forward_fused`    fused_march -> colour -> composite -> result dict (-> composite_depth);
-  `_forward_unfused`  after the sampler and the occupancy lookup: density -> alpha -> alpha filter -> Alphas2Weights ->
-                      weight filter -> k0 -> colour, then `_sum_rays` (the per-ray sum, the dict and the depth).
+  `_forward_fused`     fused_march -> colour -> `_finish_marched`;
+  `_finish_marched`    how every march ends: composite -> result dict (-> n_samples) (-> composite_depth);
+  `_render_unfused`    sample_ray -> occupancy lookup -> `_forward_unfused`;
+  `_forward_unfused`   `_raw_density` -> alpha -> alpha filter -> Alphas2Weights -> weight filter -> `_colour` -> `_sum_rays`;
+  `_sum_rays`          the per-ray sum, the dict and the depth on segment_coo (DirectVoxGO, DirectMPIGO);
+  `_sum_rays_in_order` the same in the marches' fixed order: offsets from the sorted ray_id, then `_finish_marched`;
+  `_cached_cfg`        the march-config cache behind every config builder; `_set_mask_cache` empties it;
+  `_check_rays`, `_rays_want_grad`   the two predicates of every forward and render.
 
-A subclass keeps its constructor, `_set_grid_resolution`, `get_kwargs`, `sample_ray`, its MarchConfig (`_march_cfg`) and its
-maintenance kernels; see dvgo.py (bounded scenes), dmpigo.py (NDC / multi-plane) and dcvgo.py (contracted space).
+Hooks, with this class's grids as the default: `_raw_density(pts, feats)` (the density grid) and `_colour(pts, feats,
+viewdirs, ray_id)` (k0, or the positions' encoding under `uses_posenc`).  A subclass still owns its constructor,
+`_set_grid_resolution`, `get_kwargs`, `sample_ray`, its config builder (`_march_cfg` and its kin), its maintenance kernels,
+which march its `forward` / `render` calls and which `_sum_rays` it ends in; see dvgo.py (bounded scenes), dmpigo.py (NDC /
+multi-plane), dcvgo.py (contracted space) and triplane.py with its subclasses (features from planes, lines or a hash table).
 """
 import numpy as np
 import torch
@@ -18,7 +26,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from .fused import composite, composite_depth, fused_march
-from .ops import Alphas2Weights, MaskCache, Raw2Alpha, grid_sample, segment_coo, total_variation_add_grad
+from .ops import Alphas2Weights, MaskCache, Raw2Alpha, grid_sample, ray_offsets, segment_coo, total_variation_add_grad
 from .shade import shade, shade_posenc, viewdir_embed
 
 
@@ -97,6 +105,15 @@ def _result(alphainv_last, weights, rgb_marched, alpha, rgb, ray_id):
             'raw_alpha': alpha, 'raw_rgb': rgb, 'ray_id': ray_id}
 
 
+def _check_rays(rays_o):
+    assert len(rays_o.shape) == 2 and rays_o.shape[-1] == 3, 'Only suuport point queries in [N, 3] format'
+
+
+def _rays_want_grad(rays_o, rays_d):
+    """True when a render has to be differentiable with respect to its rays."""
+    return torch.is_grad_enabled() and (rays_o.requires_grad or rays_d.requires_grad)
+
+
 class VoxelModel(nn.Module):
     """Base of DirectVoxGO, DirectMPIGO and DirectContractedVoxGO (see the module docstring).
 
@@ -157,8 +174,9 @@ class VoxelModel(nn.Module):
         return coarse(self._grid_xyz(ws, device))
 
     def _set_mask_cache(self, mask):
+        """The occupancy grid over the box, on the device of the box buffers (not every subclass has a `density`)."""
         self.mask_cache = MaskCache(path=None, mask=mask.cpu(), xyz_min=self._xyz_min_cpu,
-                                    xyz_max=self._xyz_max_cpu).to(self.density.device)
+                                    xyz_max=self._xyz_max_cpu).to(self.xyz_min.device)
         self._cfg_cache = {}
 
     def _init_mask_cache(self, ws, mask_cache_path, mask_cache_thres):
@@ -240,22 +258,43 @@ class VoxelModel(nn.Module):
         ret = [grid_sample(g, xyz, self.xyz_min, self.xyz_max) for g in grids]
         return ret[0] if len(ret) == 1 else ret
 
+    # ------------------------------------------------------------------ march configs
+    def _cached_cfg(self, key, make):
+        """The config `make()` built for `key`, rebuilt when its `mask` is no longer the mask cache's tensor (None when
+        there is no mask cache).  `_set_mask_cache` empties the cache."""
+        cfg = self._cfg_cache.get(key)
+        if cfg is None or cfg.mask is not (self.mask_cache.mask if self.mask_cache is not None else None):
+            cfg = self._cfg_cache[key] = make()
+        return cfg
+
+    def _mask_args(self):
+        """The occupancy mask with its scale and shift, as every march config takes them (none without a mask cache)."""
+        mc = self.mask_cache
+        return {} if mc is None else dict(mask=mc.mask, xyz2ijk_scale=mc.xyz2ijk_scale, xyz2ijk_shift=mc.xyz2ijk_shift)
+
+    # ------------------------------------------------------------------ hooks
+    def _raw_density(self, pts, feats=None):
+        """The raw density at `pts` on the op-by-op path: the density grid (a subclass whose density is not a grid says
+        its own; `feats` is whatever the caller handed to `render`)."""
+        return self.grid_sampler(pts, self.density)
+
+    def _colour(self, pts, feats, viewdirs, ray_id):
+        """rgb of the samples at `pts`: from their positions' encoding (uses_posenc), else from k0 there (a subclass whose
+        colour features are not k0 says its own).  (The reference also interpolates k0 under posenc and never uses it.)"""
+        if self.uses_posenc:
+            return self._shade_posenc(pts, viewdirs, ray_id)
+        return self._shade(self.grid_sampler(pts, self.k0), viewdirs, ray_id)
+
     # ------------------------------------------------------------------ forward (H2)
     def forward(self, rays_o, rays_d, viewdirs, global_step=None, **render_kwargs):
         """Volume rendering (lib/dvgo.py:450-577, lib/dmpigo.py:200-283).  Returns the reference's dict:
         alphainv_last [N], weights [M], rgb_marched [N,3], raw_alpha [M], raw_rgb [M,3], ray_id [M]
         (+ depth [N] when render_kwargs['render_depth'])."""
-        assert len(rays_o.shape) == 2 and rays_o.shape[-1] == 3, 'Only suuport point queries in [N, 3] format'
+        _check_rays(rays_o)
         if self.fused:
             cfg = self._march_cfg(render_kwargs['near'], render_kwargs['far'], render_kwargs['stepsize'])
             return self._forward_fused(rays_o, rays_d, viewdirs, cfg, **render_kwargs)
-        ray_pts, ray_id, step_id = self.sample_ray(rays_o=rays_o, rays_d=rays_d, is_train=global_step is not None,
-                                                   **render_kwargs)
-        if self.mask_cache is not None:                      # skip known free space
-            mask = self.mask_cache(ray_pts)
-            ray_pts, ray_id, step_id = ray_pts[mask], ray_id[mask], step_id[mask]
-        return self._forward_unfused(len(rays_o), viewdirs, render_kwargs['stepsize'], render_kwargs['bg'],
-                                     render_kwargs.get('render_depth', False), ray_pts, ray_id, step_id)
+        return self._render_unfused(None, rays_o, rays_d, viewdirs, global_step, **render_kwargs)
 
     def _forward_fused(self, rays_o, rays_d, viewdirs, cfg, bg, render_depth=False, _capacity=False, **_unused):
         """csrc/march.hip: 4 kernels and 1 host sync, then the colour head and the composite.
@@ -275,19 +314,33 @@ class VoxelModel(nn.Module):
                 self.density, self.k0, rays_o, rays_d, cfg, capacity=_capacity)
             m_dev = off3[N:] if _capacity else None
             rgb = self._shade(k0, viewdirs, ray_id, m_dev)
-        rgb_marched = composite(weights, rgb, alphainv_last, ray_id, off3, bg, m_dev)
-        ret = _result(alphainv_last, weights, rgb_marched, alpha, rgb, ray_id)
-        if _capacity:
+        return self._finish_marched(N, weights, alpha, alphainv_last, rgb, ray_id, step_id, off3, bg, render_depth, m_dev)
+
+    def _finish_marched(self, N, weights, alpha, alphainv_last, rgb, ray_id, step_id, off3, bg, render_depth, m_dev=None):
+        """How every render with per-ray offsets `off3` ends: fused.composite (one ray's samples in order) -> the result
+        dict (-> `n_samples`, capacity mode) (-> composite_depth)."""
+        ret = _result(alphainv_last, weights, composite(weights, rgb, alphainv_last, ray_id, off3, bg, m_dev), alpha, rgb, ray_id)
+        if m_dev is not None:
             ret['n_samples'] = m_dev
         if render_depth:
             ret['depth'] = composite_depth(weights.detach(), step_id, off3, N)
         return ret
 
-    def _forward_unfused(self, N, viewdirs, stepsize, bg, render_depth, pts, ray_id, *carried):
+    def _render_unfused(self, feats, rays_o, rays_d, viewdirs, global_step=None, **render_kwargs):
+        """The reference's op sequence on the drop-in ops (`fused=False`): the sampler, the occupancy lookup, then
+        `_forward_unfused`.  `feats`: what the caller handed to a subclass's `render` (None: the model's own tensors)."""
+        pts, ray_id, step_id = self.sample_ray(rays_o=rays_o, rays_d=rays_d, is_train=global_step is not None, **render_kwargs)
+        if self.mask_cache is not None:                      # skip known free space
+            mask = self.mask_cache(pts)
+            pts, ray_id, step_id = pts[mask], ray_id[mask], step_id[mask]
+        return self._forward_unfused(len(rays_o), viewdirs, render_kwargs['stepsize'], render_kwargs['bg'],
+                                     render_kwargs.get('render_depth', False), pts, ray_id, step_id, feats=feats)
+
+    def _forward_unfused(self, N, viewdirs, stepsize, bg, render_depth, pts, ray_id, *carried, feats=None):
         """The reference's op sequence (lib/dvgo.py:470-577) on the drop-in ops, from samples that passed the occupancy
         lookup: `pts`, `ray_id` and whatever other per-sample arrays (`carried`) the subclass's `_sum_rays` wants, all
         taken through the alpha and the weight filter together."""
-        alpha = self.activate_density(self.grid_sampler(pts, self.density), stepsize * self.voxel_size_ratio)
+        alpha = self.activate_density(self._raw_density(pts, feats), stepsize * self.voxel_size_ratio)
         if self.fast_color_thres > 0:
             mask = alpha > self.fast_color_thres
             pts, ray_id, *carried = [x[mask] for x in (pts, ray_id, *carried)]
@@ -297,10 +350,7 @@ class VoxelModel(nn.Module):
             mask = weights > self.fast_color_thres
             weights, alpha = weights[mask], alpha[mask]
             pts, ray_id, *carried = [x[mask] for x in (pts, ray_id, *carried)]
-        if self.uses_posenc:       # (the reference also interpolates k0 here and never uses the result: skipped)
-            rgb = self._shade_posenc(pts, viewdirs, ray_id)
-        else:
-            rgb = self._shade(self.grid_sampler(pts, self.k0), viewdirs, ray_id)
+        rgb = self._colour(pts, feats, viewdirs, ray_id)
         return self._sum_rays(N, weights, alpha, alphainv_last, rgb, ray_id, bg, render_depth, *carried)
 
     def _sum_rays(self, N, weights, alpha, alphainv_last, rgb, ray_id, bg, render_depth, step_id):
@@ -315,3 +365,9 @@ class VoxelModel(nn.Module):
                 ret['depth'] = segment_coo(src=(weights * step_id), index=ray_id,
                                            out=torch.zeros([N], device=weights.device), reduce='sum')
         return ret
+
+    def _sum_rays_in_order(self, N, weights, alpha, alphainv_last, rgb, ray_id, bg, render_depth, step_id):
+        """`_sum_rays` for the subclasses whose two paths agree bit for bit in rgb_marched (lib/tri_dvgo.py:786-808): the
+        fused path's own per-ray sum over offsets found in the sorted `ray_id`, in place of segment_coo's atomics."""
+        return self._finish_marched(N, weights, alpha, alphainv_last, rgb, ray_id, step_id, ray_offsets(ray_id, N), bg,
+                                    render_depth)

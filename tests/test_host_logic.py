@@ -332,3 +332,33 @@ def test_scene_models_share_a_base_and_keep_their_checkpoint_layout(name, with_h
         assert k == k2 and torch.equal(a, b), k
     # DirectMPIGO and DirectContractedVoxGO by VoxelModel's defaults; this DirectVoxGO: no posbase_pe, and a 16-wide head
     assert m.uses_posenc is False and m.can_keep_count_on_device() is False
+
+
+@pytest.mark.parametrize('name', ['DirectVoxGO', 'DirectMPIGO'])
+def test_march_config_cache_follows_the_mask_cache(name):
+    """VoxelModel._cached_cfg behind `_march_cfg`: one config per key, served from the cache until `_set_mask_cache` installs
+    another mask tensor; DirectVoxGO without a mask cache builds (and caches) a config whose mask is None."""
+    from directvoxgo_amd.dmpigo import DirectMPIGO
+    from directvoxgo_amd.dvgo import DirectVoxGO
+    if name == 'DirectMPIGO':
+        m = DirectMPIGO([-1, -1, -1], [1, 1, 1], num_voxels=5 * 5 * 4, mpi_depth=4, fast_color_thres=1e-4)
+        one, other = (0, 1, 1.0), (0, 1, 0.5)
+    else:
+        m = DirectVoxGO([-1, -1, -1], [1, 1, 1], num_voxels=5 ** 3, num_voxels_base=5 ** 3, alpha_init=1e-2, fast_color_thres=1e-4)
+        one, other = (0.5, 4.0, 0.5), (0.5, 4.0, 1.0)
+    cfg = m._march_cfg(*one)
+    assert cfg.mask is m.mask_cache.mask and list(cfg.scale_h) == m.mask_cache.xyz2ijk_scale.tolist()
+    assert m._march_cfg(*one) is cfg                                           # a repeated call: the same object
+    assert m._march_cfg(*other) is not cfg and m._march_cfg(*one) is cfg       # another key: another object, beside the first
+    new_mask = torch.zeros(tuple(m.mask_cache.mask.shape), dtype=torch.bool)
+    m._set_mask_cache(new_mask)
+    cfg2 = m._march_cfg(*one)
+    assert cfg2 is not cfg and cfg2.mask is m.mask_cache.mask and not bool(cfg2.mask.any())
+    assert m._march_cfg(*one) is cfg2
+    m.mask_cache.mask = torch.ones_like(new_mask)                              # the tensor replaced behind the cache's back
+    cfg3 = m._march_cfg(*one)
+    assert cfg3 is not cfg2 and cfg3.mask is m.mask_cache.mask and bool(cfg3.mask.all())
+    if name == 'DirectVoxGO':
+        m.mask_cache = None
+        bare = m._march_cfg(*one)
+        assert bare is not cfg3 and bare.mask is None and m._march_cfg(*one) is bare
