@@ -15,8 +15,19 @@ read by the usual colour head.  Density stays the dense 3-D grid on the fused ma
 this class reuses.  No equality with any other implementation is claimed: the contract is INTEGRATION.md section 6f, held
 by tests/hash_oracle.py.
 
+`raygrad=True` (constructor option, default False; a plain attribute like DirectContractedVoxGO.raygrad, not a `get_kwargs`
+key and not in checkpoints: pass it to the constructor or to `load_model(HashVoxGO, path, raygrad=True)`): with grad mode on
+and `rays_o` or `rays_d` requiring grad, `forward` takes DirectVoxGO._forward_raygrad whatever `self.fused` says -- the
+sampler's own positions known to autograd as o + d * lam (ops.ray_points), the density through the position-differentiable
+trilinear op, the features through `hash_sample(..., position_grad=True)` (csrc/hash_xyz.hip), the per-ray sum the model's
+in-order one -- so that pose.refine_poses can move the cameras.  The stop-gradients are `_forward_raygrad`'s (lam constant,
+the kept set fixed, no gradient for viewdirs), and every key of the result has the bits of the `fused=False` forward on the
+same detached rays (where the fused colour-head kernel takes a `fused=True` model's head, raw_rgb and rgb_marched are that
+head's, as in DirectVoxGO._forward_raygrad).  Rays that do not require grad, and every path of a model without the option,
+are untouched by it: a default model keeps refusing such rays (fused.fused_march(positions=True) has no ray gradient).
+
 Left out, each a NotImplementedError naming this class: k0_total_variation_add_grad (no k0), extract_mesh, data-parallel
-training, pose refinement, posbase_pe.
+training, pose refinement without `raygrad=True`, posbase_pe.
 """
 import numpy as np
 import torch
@@ -26,7 +37,7 @@ import torch.nn.functional as F
 from .ops import HASH_MAX_LEVELS, HashLevels, hash_sample
 from .train import FINE_TRAIN
 from .triplane import TriPlaneVoxGO
-from .voxel_model import VoxelModel
+from .voxel_model import VoxelModel, _rays_want_grad
 
 # FINE_TRAIN with Instant-NGP's published rate for the table, 1e-2.  It is the paper's number and has not been tuned on
 # this model.  The table is updated where its gradient is non-zero only, like the density: a row no sample touched in a
@@ -74,7 +85,7 @@ class HashVoxGO(TriPlaneVoxGO):
                  mask_cache_path=None, mask_cache_thres=1e-3, fast_color_thres=0,
                  rgbnet_direct=False, rgbnet_depth=3, rgbnet_width=128, viewbase_pe=4,
                  n_levels=16, n_feat=2, log2_hashmap_size=19, base_res=16, max_res=512,
-                 fused=True, verbose=False, **kwargs):
+                 fused=True, verbose=False, raygrad=False, **kwargs):
         VoxelModel.__init__(self)
         if kwargs.pop('posbase_pe', 0):
             raise NotImplementedError('posbase_pe: a positional embedding beside the hash features is not built for HashVoxGO')
@@ -88,6 +99,7 @@ class HashVoxGO(TriPlaneVoxGO):
             raise ValueError(f'max_res must not be below base_res, got max_res={max_res}, base_res={base_res}')
         self.verbose = verbose
         self.fused = bool(fused)
+        self.raygrad = bool(raygrad)              # rays that require grad are differentiated; not in get_kwargs (module docstring)
         self.fused_shade = True
         self.channels_last = True
         self._set_box(xyz_min, xyz_max)
@@ -146,15 +158,20 @@ class HashVoxGO(TriPlaneVoxGO):
 
     # ------------------------------------------------------------------ forward
     def forward(self, rays_o, rays_d, viewdirs, global_step=None, **render_kwargs):
-        """The base's `render` (both paths) on the model's own table."""
+        """The base's `render` (both paths) on the model's own table; with `raygrad=True`, rays that require grad take
+        DirectVoxGO._forward_raygrad (the module docstring says what that means)."""
+        if self.raygrad and _rays_want_grad(rays_o, rays_d):
+            return self._forward_raygrad(rays_o, rays_d, viewdirs, **render_kwargs)
         return self.render(None, rays_o, rays_d, viewdirs, global_step, **render_kwargs)
 
     def _head_features(self, pts, feats):
         return self.sample_hash(pts, feats)
 
     def sample_hash(self, pts, table=None):
-        """[M, n_levels * n_feat]; `table`: another table of the model's level layout (gradients flow into it), None: its own."""
-        return hash_sample(self.hash_table if table is None else table, pts, self.xyz_min, self.xyz_max, self.levels)
+        """[M, n_levels * n_feat]; `table`: another table of the model's level layout (gradients flow into it), None: its own.
+        With `raygrad=True`, positions that require grad receive theirs."""
+        return hash_sample(self.hash_table if table is None else table, pts, self.xyz_min, self.xyz_max, self.levels,
+                           position_grad=self.raygrad)
 
     def sample_planes(self, pts, feats=None):
         raise NotImplementedError('sample_planes: HashVoxGO has no planes; see sample_hash')

@@ -18,7 +18,8 @@ saved-tensor conventions) on top of the HIP kernels:
   vm_density                  TensoRF's vector-matrix density (no counterpart in the reference): the same 3R products summed
                               on chip into one float per sample, + backward from one float of gradient per sample
   hash_sample                 Instant-NGP's multiresolution hash-grid features (no counterpart in the reference): L trilinear
-                              levels, dense or hashed, in one table, + backward into the table
+                              levels, dense or hashed, in one table, + backward into the table and, with
+                              position_grad=True, into the positions (csrc/hash_xyz.hip)
   segment_coo                 torch_scatter.segment_coo(src, index, out, reduce='sum')
   total_variation_add_grad    lib/cuda/total_variation.cpp:16-24
   plane_reg_add_grad          total variation and L1 of the tri-plane models' planes and lines added to their gradients, one
@@ -513,35 +514,59 @@ def hash_bwd(grad_out, grad_table, xyz, xyz_min, xyz_max, levels, run=0, mode=0)
     return grad_table
 
 
+def hash_bwd_xyz(table, grad_out, xyz, xyz_min, xyz_max, levels):
+    """dvgo_hash_bwd_xyz: the gradient of the features with respect to the positions, table [T,F], grad_out [M, L F],
+    xyz [M,3] -> [M,3], every row written (include/dvgo_hip.h has the arithmetic).  No autograd."""
+    Fc, M = _hash_args(table, levels, xyz)
+    check_input(grad_out, 'grad_out'); check_f32(grad_out, 'grad_out')
+    if tuple(grad_out.shape) != (M, levels.L * Fc):
+        raise RuntimeError('grad_out has the wrong shape')
+    grad_xyz = torch.empty_like(xyz)
+    with L.device_of(xyz):
+        L.call('dvgo_hash_bwd_xyz', table, Fc, levels.L, levels.c_res, levels.c_offsets, grad_out, xyz, xyz_min, xyz_max, M,
+               grad_xyz, stream_of(xyz))
+    return grad_xyz
+
+
 class _HashSample(torch.autograd.Function):
     @staticmethod
     def forward(ctx, table, xyz, xyz_min, xyz_max, levels):
         out = hash_fwd(table, xyz, xyz_min, xyz_max, levels)
-        ctx.save_for_backward(xyz, xyz_min, xyz_max)          # linear in the table: its values are not needed again
+        if ctx.needs_input_grad[1]:       # the position gradient reads the table's values
+            ctx.save_for_backward(xyz, xyz_min, xyz_max, table)
+        else:                             # linear in the table: its values are not needed again
+            ctx.save_for_backward(xyz, xyz_min, xyz_max)
         ctx.levels, ctx.shape = levels, table.shape
         return out
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, grad_out):
-        xyz, xyz_min, xyz_max = ctx.saved_tensors
-        grad = None
+        xyz, xyz_min, xyz_max = ctx.saved_tensors[:3]
+        grad = grad_xyz = None
+        grad_out = grad_out.contiguous()
+        # the position kernel first: it reads the table's values, which an in-place optimizer step may change
+        # (_FusedMarch.backward states the rule); the scatter after it, on the same stream, reads none
+        if ctx.needs_input_grad[1]:
+            grad_xyz = hash_bwd_xyz(ctx.saved_tensors[3], grad_out, xyz, xyz_min, xyz_max, ctx.levels)
         if ctx.needs_input_grad[0]:
             grad = torch.zeros(ctx.shape, dtype=torch.float32, device=xyz.device)
-            hash_bwd(grad_out.contiguous(), grad, xyz, xyz_min, xyz_max, ctx.levels)
-        return grad, None, None, None, None
+            hash_bwd(grad_out, grad, xyz, xyz_min, xyz_max, ctx.levels)
+        return grad, grad_xyz, None, None, None
 
 
-def hash_sample(table, xyz, xyz_min, xyz_max, res, offsets=None):
+def hash_sample(table, xyz, xyz_min, xyz_max, res, offsets=None, position_grad=False):
     """Multiresolution hash-grid features (Instant-NGP) as one HIP op: `table` [T_total, F] float32 contiguous, F in
     (1, 2, 4, 8); `res` [L,3] the node counts of every level along x, y, z and `offsets` [L+1] the levels' first rows (host
     values: tensors, arrays or lists), or `res` a HashLevels made from them once; xyz [...,3] world coordinates ->
     [..., L F], level by level.  A level with one row per node is dense, any other is hashed into its power-of-two row
     count; a table that fits neither is a ValueError.  Positions outside the box read its faces.  Differentiable w.r.t.
-    `table` only."""
+    `table` and, with `position_grad=True` and an `xyz` that requires grad, w.r.t. `xyz` (csrc/hash_xyz.hip: the derivative
+    of the cell the forward chose, zero along an axis on which the position lies outside the box; once differentiable; the
+    table is then saved for the backward).  The forward is the same launch either way; by default `xyz` is detached."""
     levels = res if isinstance(res, HashLevels) else HashLevels(res, offsets)
     shape = xyz.shape[:-1]
-    flat = xyz.detach().reshape(-1, 3).contiguous()
+    flat = (xyz if position_grad else xyz.detach()).reshape(-1, 3).contiguous()
     _hash_args(table, levels, flat)
     out = _HashSample.apply(table, flat, xyz_min.contiguous(), xyz_max.contiguous(), levels)
     return out.reshape(*shape, out.shape[-1])

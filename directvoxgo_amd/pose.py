@@ -1,5 +1,5 @@
-"""Camera-pose refinement against a DirectVoxGO or, for unbounded scenes, a DirectContractedVoxGO(raygrad=True) model (no
-counterpart in the reference, whose poses are constants).
+"""Camera-pose refinement against a DirectVoxGO, a HashVoxGO(raygrad=True) or, for unbounded scenes, a
+DirectContractedVoxGO(raygrad=True) model (no counterpart in the reference, whose poses are constants).
 
 Poses from structure-from-motion are off by fractions of a degree, which on a 160^3 - 256^3 grid blurs what the grids could
 hold.  This module makes the poses learnable: `CameraRefiner` holds one se(3) correction per view and turns pixels into
@@ -10,7 +10,8 @@ together.  `refine_poses(..., fused=True)` keeps the render on the fused march (
 ray gradients from the march's own backward) and, with `train_model`, steps the model by a train.TrainStep: the brick
 scatter with the Adam update inside it, as in any other training step.  For the contracted model the positions are the
 contraction of their rays (ops.contract_points; csrc/contract_raygrad.hip applies the contraction's Jacobian and sums per
-ray), on either of its render paths.
+ray), on either of its render paths.  For the hash-grid model the colour features' share of the gradient comes from the
+hashed gather's own position derivative (ops.hash_sample(position_grad=True); csrc/hash_xyz.hip), on the op-by-op path.
 
 Pure torch: everything but `refine_poses`' model call runs on CPU tensors too.
 """
@@ -119,9 +120,14 @@ def _contracted(model):
     return type(model) is DirectContractedVoxGO
 
 
+def _hashed(model):
+    from .hashgrid import HashVoxGO
+    return type(model) is HashVoxGO
+
+
 def _supported(model):
     from .dvgo import DirectVoxGO
-    if _contracted(model):
+    if _contracted(model) or _hashed(model):
         return model.raygrad
     return type(model) is DirectVoxGO and model.posbase_pe == 0
 
@@ -149,16 +155,24 @@ def refine_poses(model, refiner, images, cfg_train, render_kwargs, n_iters, n_ra
     (ValueError otherwise) and, with `train_model`, steps the model by a `train.TrainStep`, whose plan for this model is dense
     gradients and the optimizer's own step; `cfg_train['weight_distortion']` adds the distortion loss as in training.
 
+    A `HashVoxGO(raygrad=True)` renders such rays op by op (DirectVoxGO._forward_raygrad; the features' position derivative
+    is csrc/hash_xyz.hip) whatever `model.fused` says: `fused=True` is a ValueError for it, and `train_model` steps density,
+    table and head by the eager optimiser.
+
     The gradient reaches `delta` through the sample positions only (DirectVoxGO._forward_raygrad states the stop-gradients).
-    Supported: a plain DirectVoxGO with posbase_pe == 0 and a DirectContractedVoxGO constructed with raygrad=True.
-    DirectMPIGO (NDC warp), TriPlaneVoxGO (plane sampler) and positional-encoding heads (position input of the head) lack
-    their derivative and raise NotImplementedError, as does a DirectContractedVoxGO without raygrad."""
+    Supported: a plain DirectVoxGO with posbase_pe == 0, a HashVoxGO constructed with raygrad=True (with fused=False only)
+    and a DirectContractedVoxGO constructed with raygrad=True.  DirectMPIGO (NDC warp), the tri-plane, VM, TensoRF, LIIF and
+    bilinear-decoder models (plane samplers) and positional-encoding heads (position input of the head) lack their
+    derivative and raise NotImplementedError, as do a DirectContractedVoxGO and a HashVoxGO without raygrad."""
     if not _supported(model):
         kind = type(model).__name__ + (' with posbase_pe > 0' if getattr(model, 'posbase_pe', 0) > 0 else '')
-        hint = ': construct it with raygrad=True' if _contracted(model) else ''
+        hint = ': construct it with raygrad=True' if (_contracted(model) or _hashed(model)) else ''
         raise NotImplementedError(f'refine_poses: {kind} is not supported: only a plain DirectVoxGO with posbase_pe == 0 has '
                                   f'the position derivative of its sampler{hint}')
     contracted = _contracted(model)
+    if fused and _hashed(model):
+        raise ValueError('refine_poses(fused=True): HashVoxGO differentiates its rays on the op-by-op path only '
+                         '(fused_march(positions=True) has no ray gradient): call it with fused=False')
     if fused and contracted and not model.fused_march:
         raise ValueError('refine_poses(fused=True) needs a DirectContractedVoxGO on the fused march (fused_march=True)')
     if fused and not getattr(model, 'fused', False):

@@ -41,7 +41,7 @@ extern "C" {
 /* version of this ABI; bumped on any signature change (6: the positional-encoding colour head; 7: the contracted
  * sampler and the distortion loss of unbounded scenes; 8: the tri-plane sampler; 9: the trilinear sample's gradient
  * with respect to the position; 10: the LIIF plane decoder; 11: the fused march's gradient with respect to its rays).
- * The two dvgo_plane_rows_*, the two dvgo_vm_*, the two dvgo_hash_*, the two dvgo_vm_density_*, the two dvgo_march_vm_density*, the two dvgo_march_contract_density*, the dvgo_contract_positions and the two dvgo_contract_ray_bwd* entries were added without a bump, unlike the additions before them: an
+ * The two dvgo_plane_rows_*, the two dvgo_vm_*, the two dvgo_hash_*, the two dvgo_vm_density_*, the two dvgo_march_vm_density*, the two dvgo_march_contract_density*, the dvgo_contract_positions, the two dvgo_contract_ray_bwd* and the dvgo_hash_bwd_xyz entries were added without a bump, unlike the additions before them: an
  * existing test pins the value 11, and a library built before them is still caught at load, by the check that every declared entry is exported. */
 #define DVGO_ABI_VERSION 11
 int dvgo_abi_version(void);
@@ -1109,12 +1109,43 @@ int dvgo_plane_reg_add_grad(const float* const* params, float* const* grads, con
  * 1..DVGO_HASH_MAX_LEVELS, a node count below 2, offsets[0] < 0, a size_l that is neither the node count nor a power of two
  * below it, negative M or run, a mode outside 0..3, null or misaligned pointers.  DVGO_ERANGE: M L F >= 2^31 (mode 2:
  * 8 M L >= 2^31), Rx Ry >= 2^31, a hashed level of more than 2^31 rows.  All of it is answered before any launch.
+ *
+ * dvgo_hash_bwd_xyz (csrc/hash_xyz.hip): the gradient of the features with respect to the sample POSITION, which
+ * dvgo_hash_bwd does not give.  table [T_total, F] (its values are read), grad_out [M, L F], xyz [M,3] -> grad_xyz [M,3].
+ * Every row of grad_xyz is written with plain stores: no atomics, no workspace, nothing to zero beforehand.  F, L, res,
+ * offsets and the alignment of table and grad_out are dvgo_hash_fwd's (grad_xyz: a float's).  Added without a bump of
+ * DVGO_ABI_VERSION, as the two entries above were.
+ * The cell (fx, fy, fz) and the weights w0, w1 of every axis are the forward's own, bit for bit, so the derivative is that of
+ * the cell the forward chose: floorf picks the upper cell on an interior lattice plane, f = min(floor, R - 2) the last cell
+ * at g == R - 1.  The forward clamps the coordinate, so outside the box the features are constant along the clamped axis:
+ * with inside_a = (g_a >= 0) & (g_a <= R_a - 1) on the UNCLAMPED float32 g_a (a NaN is not inside), level l contributes
+ * exactly 0.0f along axis a when !inside_a; the other axes keep theirs.
+ * Per sample m, in float32, one lane, everything in this order whatever the launch shape (bitwise repeatable):
+ *   ox = oy = oz = 0.0f
+ *   for l = 0 .. L - 1 ascending:
+ *     the two-weight product of corner n = 0..7 (bx = n >> 2 & 1, by = n >> 1 & 1, bz = n & 1), first factor * second:
+ *       for d/dx  wy[by] * wz[bz]      for d/dy  wx[bx] * wz[bz]      for d/dz  wx[bx] * wy[by]
+ *     negated on the lower corner of the derivative's axis (b = 0) and as it is on the upper (b = 1): sx_n, sy_n, sz_n (exact)
+ *     ax = ay = az = 0.0f
+ *     for c = 0 .. F - 1 ascending:
+ *       dx = dy = dz = 0.0f;  for n = 0 .. 7 ascending, v = table[offsets[l] + row_n, c]:
+ *         dx = fmaf(v, sx_n, dx);  dy = fmaf(v, sy_n, dy);  dz = fmaf(v, sz_n, dz)
+ *       ax = fmaf(grad_out[m, l F + c], dx, ax);  ay, az likewise
+ *     the level's scale is applied once, after the last channel:  tx = ax * ((float)(Rx_l - 1) / (max_x - min_x)), ty, tz likewise
+ *     ox = ox + (inside_x ? tx : 0.0f);  oy, oz likewise
+ *   grad_xyz[m] = (ox, oy, oz)
+ * Two corners of one cell that share a row of a hashed level are two terms, as in the forward.
+ * M == 0: no-op, no device pointer is looked at (the level table is still checked).  DVGO_EINVAL and DVGO_ERANGE as for
+ * dvgo_hash_fwd, for the same conditions in the same order; all of it is answered before any launch.
  * --------------------------------------------------------------------------------- */
 #define DVGO_HASH_MAX_LEVELS 32
 int dvgo_hash_fwd(const float* table, int F, int L, const int32_t* res, const int64_t* offsets, const float* xyz,
                   const float* xyz_min, const float* xyz_max, int64_t M, float* out, void* stream);
 int dvgo_hash_bwd(const float* grad_out, float* grad_table, int F, int L, const int32_t* res, const int64_t* offsets,
                   const float* xyz, const float* xyz_min, const float* xyz_max, int64_t M, int run, int mode, void* stream);
+int dvgo_hash_bwd_xyz(const float* table, int F, int L, const int32_t* res, const int64_t* offsets,
+                      const float* grad_out, const float* xyz, const float* xyz_min, const float* xyz_max,
+                      int64_t M, float* grad_xyz, void* stream);
 
 #ifdef __cplusplus
 }
