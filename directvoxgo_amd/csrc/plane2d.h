@@ -96,6 +96,42 @@ __device__ __forceinline__ void tp_store(float* __restrict__ p, const TpVal<VEC>
   }
 }
 
+// tp_sample in two steps, for a caller that needs the corner values as well as the plane value (vm_xyz.hip): the same
+// loads, in-range tests and fma chain as tp_sample below, hence the same bits.  (tp_sample is not written in terms of these:
+// DESIGN.md section 6o.)
+// VEC channels from c on of the four corners of cell (b.h0, b.w0) of plane q, and which corners are in range: the loads
+// come from clamped, always valid addresses, and a corner out of range is dropped by whoever blends (zero padding)
+template <int VEC>
+struct TpCorners {
+  bool okh0, okh1, okw0, okw1;
+  TpVal<VEC> v00, v01, v10, v11;
+};
+
+template <int VEC>
+__device__ __forceinline__ TpCorners<VEC> tp_gather(const TpPlane& q, const BiSetup& b, int c) {
+  TpCorners<VEC> k;
+  const int h1 = b.h0 + 1, w1 = b.w0 + 1;
+  k.okh0 = (b.h0 >= 0) & (b.h0 < q.H); k.okh1 = (h1 >= 0) & (h1 < q.H);
+  k.okw0 = (b.w0 >= 0) & (b.w0 < q.W); k.okw1 = (w1 >= 0) & (w1 < q.W);
+  const int64_t oh0 = (int64_t)min(max(b.h0, 0), q.H - 1) * q.sH, oh1 = (int64_t)min(max(h1, 0), q.H - 1) * q.sH;
+  const int64_t ow0 = (int64_t)min(max(b.w0, 0), q.W - 1) * q.sW, ow1 = (int64_t)min(max(w1, 0), q.W - 1) * q.sW;
+  const float* base = q.p + (int64_t)c * q.sC;
+  k.v00 = tp_load<VEC>(base + oh0 + ow0, q.sC); k.v01 = tp_load<VEC>(base + oh0 + ow1, q.sC);
+  k.v10 = tp_load<VEC>(base + oh1 + ow0, q.sC); k.v11 = tp_load<VEC>(base + oh1 + ow1, q.sC);
+  return k;
+}
+
+// the plane value of channel i of the gathered corners: the fma chain over 00, 01, 10, 11 from 0, corners out of range skipped
+template <int VEC>
+__device__ __forceinline__ float tp_blend(const TpCorners<VEC>& k, int i, float k00, float k01, float k10, float k11) {
+  float acc = 0.f;
+  acc = (k.okh0 & k.okw0) ? fmaf(k.v00.v[i], k00, acc) : acc;
+  acc = (k.okh0 & k.okw1) ? fmaf(k.v01.v[i], k01, acc) : acc;
+  acc = (k.okh1 & k.okw0) ? fmaf(k.v10.v[i], k10, acc) : acc;
+  acc = (k.okh1 & k.okw1) ? fmaf(k.v11.v[i], k11, acc) : acc;
+  return acc;
+}
+
 // VEC channels from c on of plane q at sample m
 template <int VEC>
 __device__ __forceinline__ TpVal<VEC> tp_sample(const TpPlane& q, int ah, int aw, int c, const float* __restrict__ xyz,

@@ -38,6 +38,36 @@ __device__ __forceinline__ VmLine vm_pick(const VmLine A, const VmLine B, const 
 
 __device__ __forceinline__ float* vm_pick(const VmGrads G, int s) { return (s == 0) ? G.a : (s == 1) ? G.b : G.c; }
 
+// vm_line in two steps, for a caller that needs the node values as well as the line value (vm_xyz.hip): the same loads,
+// in-range tests and fma chain as vm_line below, hence the same bits (vm_line itself stays as it is: DESIGN.md section 6o).
+// VEC components from c on of the two nodes of the interval (n0, n0 + 1) of line q, and which nodes are in range: the
+// loads come from clamped, always valid addresses, and a node out of range is dropped by whoever blends (zero padding)
+template <int VEC>
+struct VmNodes {
+  bool ok0, ok1;
+  TpVal<VEC> v0, v1;
+};
+
+template <int VEC>
+__device__ __forceinline__ VmNodes<VEC> vm_gather(const VmLine& q, int c, int n0) {
+  VmNodes<VEC> k;
+  const int n1 = n0 + 1;
+  k.ok0 = (n0 >= 0) & (n0 < q.N); k.ok1 = (n1 >= 0) & (n1 < q.N);
+  const float* base = q.p + (int64_t)c * q.sC;
+  k.v0 = tp_load<VEC>(base + (int64_t)min(max(n0, 0), q.N - 1) * q.sN, q.sC);
+  k.v1 = tp_load<VEC>(base + (int64_t)min(max(n1, 0), q.N - 1) * q.sN, q.sC);
+  return k;
+}
+
+// the line value of component i of the gathered nodes: the fma chain over the nodes from 0, nodes out of range skipped
+template <int VEC>
+__device__ __forceinline__ float vm_blend(const VmNodes<VEC>& k, int i, float w0, float w1) {
+  float l = 0.f;
+  l = k.ok0 ? fmaf(k.v0.v[i], w0, l) : l;
+  l = k.ok1 ? fmaf(k.v1.v[i], w1, l) : l;
+  return l;
+}
+
 // VEC components from c on of line q in the interval (n0, n0 + 1) with the weights (w0, w1)
 template <int VEC>
 __device__ __forceinline__ TpVal<VEC> vm_line(const VmLine& q, int c, int n0, float w0, float w1) {
@@ -193,6 +223,12 @@ struct VmLines { VmLine a, b, c; };
 static int vm_check(const TpPlanes& P, const VmLines& L, int R, int64_t M, const void* xyz, const void* mn, const void* mx,
                     const void* io) {
   return tp_check(P, R, M, L.a.N >= 1 && L.b.N >= 1 && L.c.N >= 1, xyz, mn, mx, {L.a.p, L.b.p, L.c.p, io}, 3, R);
+}
+
+// the same for an entry with an incoming gradient `in` and an output `out` (vm_xyz.hip)
+static int vm_check(const TpPlanes& P, const VmLines& L, int R, int64_t M, const void* xyz, const void* mn, const void* mx,
+                    const void* in, const void* out) {
+  return tp_check(P, R, M, L.a.N >= 1 && L.b.N >= 1 && L.c.N >= 1, xyz, mn, mx, {L.a.p, L.b.p, L.c.p, in, out}, 3, R);
 }
 
 // The argument check and the launch shape of a scatter entry, after `vm_check` semantics: < 0 the error, 1 nothing to do,

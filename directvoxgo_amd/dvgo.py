@@ -204,7 +204,7 @@ class DirectVoxGO(VoxelModel):
             return self._forward_raygrad(rays_o, rays_d, viewdirs, **render_kwargs)
         return super().forward(rays_o, rays_d, viewdirs, global_step=global_step, **render_kwargs)
 
-    def _forward_raygrad(self, rays_o, rays_d, viewdirs, near, far, stepsize, bg, render_depth=False, **_unused):
+    def _forward_raygrad(self, rays_o, rays_d, viewdirs, near, far, stepsize, bg, render_depth=False, feats=None, **_unused):
         """The op-by-op forward on positions that autograd knows as o + d * lam (ops.ray_points), sampled through the
         position-differentiable trilinear op (csrc/grid_sample_xyz.hip).  Forward values are those of the `fused=False`
         path: the positions are the sampling kernel's own, bit for bit.  Stop-gradients, by contract:
@@ -212,7 +212,9 @@ class DirectVoxGO(VoxelModel):
             norm passes a gradient back to the ray;
           * the set of kept samples is fixed: the in-box test, the occupancy mask and both fast_color_thres filters select
             rows and are not differentiated;
-          * viewdirs carries no gradient (the colour heads have no input gradient for the view embedding)."""
+          * viewdirs carries no gradient (the colour heads have no input gradient for the view embedding).
+        `feats`: what the caller handed to a subclass's `render`, passed on to `_forward_unfused` (None: the model's own
+        tensors)."""
         _check_rays(rays_o)
         rays_o, rays_d = rays_o.contiguous(), rays_d.contiguous()
         stepdist = stepsize * self.voxel_size
@@ -226,7 +228,7 @@ class DirectVoxGO(VoxelModel):
                 ray_pts, ray_id, step_id = ray_pts[keep], ray_id[keep], step_id[keep]
             lam = t_min[ray_id] + (float(stepdist) * step_id) / rays_d.norm(dim=-1)[ray_id]
         pts = ray_points(rays_o, rays_d, lam.contiguous(), ray_id, ray_pts.contiguous())
-        return self._forward_unfused(len(rays_o), viewdirs.detach(), stepsize, bg, render_depth, pts, ray_id, step_id)
+        return self._forward_unfused(len(rays_o), viewdirs.detach(), stepsize, bg, render_depth, pts, ray_id, step_id, feats=feats)
 
     # ------------------------------------------------------------------ colour head and forward (H2)
     @property

@@ -14,9 +14,11 @@ saved-tensor conventions) on top of the HIP kernels:
   plane_rows, interp_decode   lib/tri_dvgo.py:568-607 (interpolate, liif=False: bilinear features, sampled coordinates and their
                               encoding as one MLP input row per plane, + backward; the Interp_MLPs stay torch modules)
   vm_sample                   TensoRF's vector-matrix features (no counterpart in the reference): per component a plane's
-                              bilinear value times a line's linear value, + backward into planes and lines
+                              bilinear value times a line's linear value, + backward into planes and lines and, with
+                              position_grad=True, into the positions (csrc/vm_xyz.hip)
   vm_density                  TensoRF's vector-matrix density (no counterpart in the reference): the same 3R products summed
                               on chip into one float per sample, + backward from one float of gradient per sample
+                              (position_grad=True: into the positions as well, csrc/vm_xyz.hip)
   hash_sample                 Instant-NGP's multiresolution hash-grid features (no counterpart in the reference): L trilinear
                               levels, dense or hashed, in one table, + backward into the table and, with
                               position_grad=True, into the positions (csrc/hash_xyz.hip)
@@ -350,6 +352,29 @@ def vm_bwd(grad_out, planes, lines, grad_planes, grad_lines, xyz, xyz_min, xyz_m
     return grad_planes, grad_lines
 
 
+def _vm_bwd_xyz(entry, per_comp, grad_out, planes, lines, xyz, xyz_min, xyz_max):
+    planes, lines, geom, R, M = _vm_args(planes, lines, xyz)
+    check_input(grad_out, 'grad_out'); check_f32(grad_out, 'grad_out')
+    if tuple(grad_out.shape) != ((M, 3 * R) if per_comp else (M,)):
+        raise RuntimeError('grad_out has the wrong shape')
+    grad_xyz = torch.empty_like(xyz)
+    with L.device_of(xyz):
+        L.call(entry, *geom, R, grad_out, xyz, xyz_min, xyz_max, M, grad_xyz, stream_of(xyz))
+    return grad_xyz
+
+
+def vm_bwd_xyz(grad_out, planes, lines, xyz, xyz_min, xyz_max):
+    """dvgo_vm_bwd_xyz: the gradient of `vm_fwd`'s features with respect to the positions, grad_out [M, 3R], xyz [M,3] ->
+    [M,3], every row written (csrc/vm_xyz.hip; include/dvgo_hip.h has the arithmetic).  No autograd."""
+    return _vm_bwd_xyz('dvgo_vm_bwd_xyz', True, grad_out, planes, lines, xyz, xyz_min, xyz_max)
+
+
+def vm_density_bwd_xyz(grad_out, planes, lines, xyz, xyz_min, xyz_max):
+    """dvgo_vm_density_bwd_xyz: `vm_bwd_xyz` for `vm_density_fwd`, one float of incoming gradient per sample, grad_out [M];
+    a sample whose gradient is exactly 0 gets an exactly zero row.  No autograd."""
+    return _vm_bwd_xyz('dvgo_vm_density_bwd_xyz', False, grad_out, planes, lines, xyz, xyz_min, xyz_max)
+
+
 class _VMSample(torch.autograd.Function):
     @staticmethod
     def forward(ctx, xyz, xyz_min, xyz_max, *tensors):
@@ -362,19 +387,28 @@ class _VMSample(torch.autograd.Function):
     @torch.autograd.function.once_differentiable
     def backward(ctx, grad_out):
         xyz, xyz_min, xyz_max, *kt = ctx.saved_tensors
+        grad_xyz = None
+        grad_out = grad_out.contiguous()
+        # the position kernel first, the scatter after it (_HashSample.backward states the rule); it reads the saved `kt`
+        # the forward read
+        if ctx.needs_input_grad[0]:
+            grad_xyz = vm_bwd_xyz(grad_out, kt[:3], kt[3:], xyz, xyz_min, xyz_max)
         grads = _scatter_grads(ctx, ctx.needs_input_grad[3:],
-                               lambda g: vm_bwd(grad_out.contiguous(), kt[:3], kt[3:], g[:3], g[3:], xyz, xyz_min, xyz_max))
-        return (None, None, None, *grads)
+                               lambda g: vm_bwd(grad_out, kt[:3], kt[3:], g[:3], g[3:], xyz, xyz_min, xyz_max))
+        return (grad_xyz, None, None, *grads)
 
 
-def vm_sample(planes, lines, xyz, xyz_min, xyz_max):
+def vm_sample(planes, lines, xyz, xyz_min, xyz_max, position_grad=False):
     """TensoRF's vector-matrix features as one HIP op: `planes` as in `triplane_sample`, each [1,R,H,W]; `lines` likewise a
     dict with the keys 'xy', 'yz', 'zx' (or the three in that order), each [1,R,N,1], line s running along the world axis
     plane s does not see (xy: x, yz: z, zx: y); xyz [...,3] world coordinates -> [...,3R]: per component the plane's
-    bilinear value times the line's linear value, in the order xy, yz, zx.  Differentiable w.r.t. planes and lines only."""
+    bilinear value times the line's linear value, in the order xy, yz, zx.  Differentiable w.r.t. planes and lines and, with
+    `position_grad=True` and an `xyz` that requires grad, w.r.t. `xyz` (csrc/vm_xyz.hip: the derivative of the cell the
+    forward chose, with the forward's zero padding; once differentiable).  The forward is the same launch either way; by
+    default `xyz` is detached."""
     tensors = _vm_tensors(planes, lines)
     shape = xyz.shape[:-1]
-    flat = xyz.reshape(-1, 3).contiguous()
+    flat = (xyz if position_grad else xyz.detach()).reshape(-1, 3).contiguous()
     out = _VMSample.apply(flat, xyz_min.contiguous(), xyz_max.contiguous(), *tensors)
     return out.reshape(*shape, out.shape[-1])
 
@@ -429,20 +463,28 @@ class _VMDensity(torch.autograd.Function):
     def backward(ctx, grad_out):
         xyz, xyz_min, xyz_max, *kt = ctx.saved_tensors
         needs = ctx.needs_input_grad[3:]
+        grad_xyz = None
+        grad_out = grad_out.contiguous()
+        # the position kernel first, the scatter after it (_HashSample.backward states the rule); it reads the saved `kt`
+        # the forward read
+        if ctx.needs_input_grad[0]:
+            grad_xyz = vm_density_bwd_xyz(grad_out, kt[:3], kt[3:], xyz, xyz_min, xyz_max)
         if not any(needs):
-            return (None,) * 9
+            return (grad_xyz,) + (None,) * 8
         grads = _vm_grad_buffers(kt)
-        vm_density_bwd(grad_out.contiguous(), kt[:3], kt[3:], grads[:3], grads[3:], xyz, xyz_min, xyz_max)
-        return (None, None, None, *[g if need else None for g, need in zip(grads, needs)])
+        vm_density_bwd(grad_out, kt[:3], kt[3:], grads[:3], grads[3:], xyz, xyz_min, xyz_max)
+        return (grad_xyz, None, None, *[g if need else None for g, need in zip(grads, needs)])
 
 
-def vm_density(planes, lines, xyz, xyz_min, xyz_max):
+def vm_density(planes, lines, xyz, xyz_min, xyz_max, position_grad=False):
     """TensoRF's vector-matrix density as one HIP op: `planes` and `lines` as in `vm_sample`; xyz [...,3] world coordinates
     -> [...]: the sum over the three planes and their R components of plane value times line value, summed on chip (no
-    [M, 3R] intermediate, forward or backward).  Differentiable w.r.t. planes and lines only."""
+    [M, 3R] intermediate, forward or backward).  Differentiable w.r.t. planes and lines and, with `position_grad=True` and
+    an `xyz` that requires grad, w.r.t. `xyz` (csrc/vm_xyz.hip, as in `vm_sample`).  The forward is the same launch either
+    way; by default `xyz` is detached."""
     tensors = _vm_tensors(planes, lines)
     shape = xyz.shape[:-1]
-    flat = xyz.reshape(-1, 3).contiguous()
+    flat = (xyz if position_grad else xyz.detach()).reshape(-1, 3).contiguous()
     return _VMDensity.apply(flat, xyz_min.contiguous(), xyz_max.contiguous(), *tensors).reshape(shape)
 
 

@@ -1,5 +1,6 @@
-"""Camera-pose refinement against a DirectVoxGO, a HashVoxGO(raygrad=True) or, for unbounded scenes, a
-DirectContractedVoxGO(raygrad=True) model (no counterpart in the reference, whose poses are constants).
+"""Camera-pose refinement against a DirectVoxGO, a HashVoxGO(raygrad=True), a VMTriPlaneVoxGO(raygrad=True), a
+TensoRFVoxGO(raygrad=True) or, for unbounded scenes, a DirectContractedVoxGO(raygrad=True) model (no counterpart in the
+reference, whose poses are constants).
 
 Poses from structure-from-motion are off by fractions of a degree, which on a 160^3 - 256^3 grid blurs what the grids could
 hold.  This module makes the poses learnable: `CameraRefiner` holds one se(3) correction per view and turns pixels into
@@ -12,6 +13,8 @@ scatter with the Adam update inside it, as in any other training step.  For the 
 contraction of their rays (ops.contract_points; csrc/contract_raygrad.hip applies the contraction's Jacobian and sums per
 ray), on either of its render paths.  For the hash-grid model the colour features' share of the gradient comes from the
 hashed gather's own position derivative (ops.hash_sample(position_grad=True); csrc/hash_xyz.hip), on the op-by-op path.
+For the two vector-matrix models it comes from the position derivative of planes times lines (ops.vm_sample and, for
+TensoRFVoxGO's density, ops.vm_density with position_grad=True; csrc/vm_xyz.hip), on the op-by-op path as well.
 
 Pure torch: everything but `refine_poses`' model call runs on CPU tensors too.
 """
@@ -125,9 +128,20 @@ def _hashed(model):
     return type(model) is HashVoxGO
 
 
+def _vm(model):
+    from .tensorf import TensoRFVoxGO
+    from .vm import VMTriPlaneVoxGO
+    return type(model) in (VMTriPlaneVoxGO, TensoRFVoxGO)
+
+
+def _takes_raygrad(model):
+    """The classes that differentiate their rays only when constructed with raygrad=True."""
+    return _contracted(model) or _hashed(model) or _vm(model)
+
+
 def _supported(model):
     from .dvgo import DirectVoxGO
-    if _contracted(model) or _hashed(model):
+    if _takes_raygrad(model):
         return model.raygrad
     return type(model) is DirectVoxGO and model.posbase_pe == 0
 
@@ -159,20 +173,31 @@ def refine_poses(model, refiner, images, cfg_train, render_kwargs, n_iters, n_ra
     is csrc/hash_xyz.hip) whatever `model.fused` says: `fused=True` is a ValueError for it, and `train_model` steps density,
     table and head by the eager optimiser.
 
+    A `VMTriPlaneVoxGO(raygrad=True)` and a `TensoRFVoxGO(raygrad=True)` render such rays op by op as well
+    (DirectVoxGO._forward_raygrad; the position derivative of planes times lines is csrc/vm_xyz.hip, for the features and,
+    in TensoRFVoxGO, for the density) whatever `model.fused` and `model.fused_march` say: `fused=True` is a ValueError for
+    them (the VM march has no ray backward), and `train_model` steps planes, lines, basis, the density tensors and the head
+    by the eager optimiser.
+
     The gradient reaches `delta` through the sample positions only (DirectVoxGO._forward_raygrad states the stop-gradients).
-    Supported: a plain DirectVoxGO with posbase_pe == 0, a HashVoxGO constructed with raygrad=True (with fused=False only)
-    and a DirectContractedVoxGO constructed with raygrad=True.  DirectMPIGO (NDC warp), the tri-plane, VM, TensoRF, LIIF and
-    bilinear-decoder models (plane samplers) and positional-encoding heads (position input of the head) lack their
-    derivative and raise NotImplementedError, as do a DirectContractedVoxGO and a HashVoxGO without raygrad."""
+    Supported: a plain DirectVoxGO with posbase_pe == 0, a HashVoxGO, a VMTriPlaneVoxGO or a TensoRFVoxGO constructed with
+    raygrad=True (with fused=False only) and a DirectContractedVoxGO constructed with raygrad=True.  DirectMPIGO (NDC warp),
+    the tri-plane, LIIF and bilinear-decoder models (plane samplers) and positional-encoding heads (position input of the
+    head) lack their derivative and raise NotImplementedError, as do a DirectContractedVoxGO, a HashVoxGO, a VMTriPlaneVoxGO
+    and a TensoRFVoxGO without raygrad."""
     if not _supported(model):
         kind = type(model).__name__ + (' with posbase_pe > 0' if getattr(model, 'posbase_pe', 0) > 0 else '')
-        hint = ': construct it with raygrad=True' if (_contracted(model) or _hashed(model)) else ''
+        hint = ': construct it with raygrad=True' if _takes_raygrad(model) else ''
         raise NotImplementedError(f'refine_poses: {kind} is not supported: only a plain DirectVoxGO with posbase_pe == 0 has '
                                   f'the position derivative of its sampler{hint}')
     contracted = _contracted(model)
     if fused and _hashed(model):
         raise ValueError('refine_poses(fused=True): HashVoxGO differentiates its rays on the op-by-op path only '
                          '(fused_march(positions=True) has no ray gradient): call it with fused=False')
+    if fused and _vm(model):
+        raise ValueError(f'refine_poses(fused=True): {type(model).__name__} differentiates its rays on the op-by-op path only '
+                         '(the fused marches over positions and over the decomposed density have no ray gradient): call it '
+                         'with fused=False')
     if fused and contracted and not model.fused_march:
         raise ValueError('refine_poses(fused=True) needs a DirectContractedVoxGO on the fused march (fused_march=True)')
     if fused and not getattr(model, 'fused', False):

@@ -28,11 +28,19 @@ Occupancy goes through `dense_density()`, the op evaluated at the world_size lat
 `_alpha_mask`, `scale_volume_grid` and fit.compute_bbox_by_coarse_geo read it; it is a temporary, never a parameter.
 `maskout_near_cam_vox` cannot write -100 into a grid and clears the occupancy mask at the same voxels instead.
 
+`raygrad=True` (constructor option of the base, default False; not a `get_kwargs` key and not in checkpoints: pass it to the
+constructor or to `load_model(TensoRFVoxGO, path, raygrad=True)`): with grad mode on and `rays_o` or `rays_d` requiring grad,
+`forward` and `render` take DirectVoxGO._forward_raygrad whatever `fused` and `fused_march` say (the VM march has no ray
+backward): the density through `vm_density(..., position_grad=True)`, the features through `vm_sample(...,
+position_grad=True) @ basis`, both derivatives one kernel body (csrc/vm_xyz.hip).  Every key of the result has the bits of
+the op-by-op forward on the same detached rays; the stop-gradients are `_forward_raygrad`'s.  pose.refine_poses accepts the
+model only with this option.
+
 Refused, each naming this class: voxel_count_views / pervoxel_lr, density_total_variation_add_grad (the regularisers of the
-density are the config keys train.DENSITY_REG_KEYS), export_volume, extract_mesh, refine_poses, data-parallel training,
-rays that require grad, and everything the bases refuse.  Not built: a coarse stage (per-voxel learning rates), PSNR
-against a dense density (no quality claim is made), a device-side sample count for the fused march (its forward reads two
-counts).  INTEGRATION.md section 6g is the contract.
+density are the config keys train.DENSITY_REG_KEYS), export_volume, extract_mesh, refine_poses and rays that require grad
+without `raygrad=True`, data-parallel training, and everything the bases refuse.  Not built: a coarse stage (per-voxel
+learning rates), PSNR against a dense density (no quality claim is made), a device-side sample count for the fused march
+(its forward reads two counts).  INTEGRATION.md section 6g is the contract.
 """
 import torch
 import torch.nn as nn
@@ -116,9 +124,10 @@ class TensoRFVoxGO(VMTriPlaneVoxGO):
     def raw_density(self, pts, feats=None):
         """[...]: the decomposed density at `pts` [..., 3], before the activation.  `feats`: optionally the caller's density
         tensors under 'xy_density', 'yz_density', 'zx_density' and 'xy_density_line', ...; a missing key means the
-        model's own tensor.  Gradients flow into whichever is used."""
+        model's own tensor.  Gradients flow into whichever is used and, with `raygrad=True`, into positions that require
+        grad."""
         planes, lines = self._density_tensors(feats)
-        return vm_density(planes, lines, pts, self.xyz_min, self.xyz_max)
+        return vm_density(planes, lines, pts, self.xyz_min, self.xyz_max, position_grad=self.raygrad)
 
     _raw_density = raw_density
 
@@ -211,11 +220,15 @@ class TensoRFVoxGO(VMTriPlaneVoxGO):
 
     def render(self, feats, rays_o, rays_d, viewdirs, global_step=None, **render_kwargs):
         """The base's result dict from either path of this model (module docstring).  `feats`: the colour planes and
-        lines as in the base and, beside them, density tensors under the keys of `raw_density`."""
+        lines as in the base and, beside them, density tensors under the keys of `raw_density`.  With `raygrad=True`, rays
+        that require grad take DirectVoxGO._forward_raygrad on the same `feats`."""
         _check_rays(rays_o)
+        if self.raygrad and _rays_want_grad(rays_o, rays_d):
+            return self._forward_raygrad(rays_o, rays_d, viewdirs, feats=feats, **render_kwargs)
         if self.fused_march:
             if _rays_want_grad(rays_o, rays_d):
-                self._refuse('rays that require grad', 'has no derivative of its density with respect to the sample positions')
+                self._refuse('rays that require grad', 'has no derivative of its density with respect to the sample positions: '
+                                                       'construct it with raygrad=True')
             cfg = self._march_vm_cfg(render_kwargs['near'], render_kwargs['far'], render_kwargs['stepsize'])
             march = fused_march_vm(*self._density_tensors(feats), rays_o, rays_d, cfg)
             if march is not None:                   # None: no fixed record stride for these render_kwargs -> op by op

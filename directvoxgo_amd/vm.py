@@ -11,8 +11,18 @@ The sampler and its gradient are one HIP op (ops.vm_sample, csrc/vm.hip; include
 matmul is torch's.  Density stays the dense 3-D grid on the fused march, as in the base.  No equality with any other
 implementation is claimed: the contract is INTEGRATION.md section 6d, held by tests/vm_oracle.py.
 
-Everything the base leaves out stays out: extract_mesh, data-parallel training, pose refinement, the plane decoders'
-options and the encoder's keys.  Not built either: the basis matmul fused into the sampler.  (The VM-decomposed density is
+`raygrad=True` (constructor option, default False; a plain attribute like HashVoxGO.raygrad, not a `get_kwargs` key and not
+in checkpoints: pass it to the constructor or to `load_model(VMTriPlaneVoxGO, path, raygrad=True)`): with grad mode on and
+`rays_o` or `rays_d` requiring grad, `forward` and `render` take DirectVoxGO._forward_raygrad whatever `self.fused` says --
+the sampler's own positions known to autograd as o + d * lam (ops.ray_points), the density through the
+position-differentiable trilinear op, the features through `vm_sample(..., position_grad=True) @ basis` (csrc/vm_xyz.hip),
+the per-ray sum the model's in-order one -- so that pose.refine_poses can move the cameras.  The stop-gradients are
+`_forward_raygrad`'s (lam constant, the kept set fixed, no gradient for viewdirs), and every key of the result has the bits
+of the `fused=False` forward on the same detached rays.  Rays that do not require grad, and every path of a model without
+the option, are untouched by it.
+
+Everything the base leaves out stays out: extract_mesh, data-parallel training, pose refinement without `raygrad=True`, the
+plane decoders' options and the encoder's keys.  Not built either: the basis matmul fused into the sampler.  (The VM-decomposed density is
 tensorf.TensoRFVoxGO.)
 
 Regularisers (TensoRF trains its VM model with them): `plane_regularizers_add_grad` adds total variation on the planes,
@@ -27,6 +37,7 @@ import torch.nn.functional as F
 
 from .ops import PLANE_KEYS, vm_sample
 from .triplane import TRI_FINE_TRAIN, TriPlaneVoxGO
+from .voxel_model import _rays_want_grad
 
 # which world axis the line of each plane follows: the one the plane's rows and columns do not
 LINE_AXIS = {'xy': 0, 'yz': 2, 'zx': 1}
@@ -40,9 +51,10 @@ class VMTriPlaneVoxGO(TriPlaneVoxGO):
     """TriPlaneVoxGO whose colour features are `vm_sample(planes, lines, pts) @ basis`.  Takes the base's arguments plus
     `n_comp` (components per plane, R) and `line_size` (an int: the length of all three lines; None: each line takes the
     `world_size` extent of its axis and is resized with the grid).  `rgbnet_dim` is the feature width the head sees.
-    `tri_aggregation` is not an option: the products are concatenated in front of the basis."""
+    `tri_aggregation` is not an option: the products are concatenated in front of the basis.  `raygrad`: rays that require
+    grad are differentiated (module docstring)."""
 
-    def __init__(self, xyz_min, xyz_max, n_comp=16, line_size=None, **kwargs):
+    def __init__(self, xyz_min, xyz_max, n_comp=16, line_size=None, raygrad=False, **kwargs):
         if kwargs.pop('tri_aggregation', 'concat') != 'concat':
             raise ValueError("tri_aggregation is not an option of VMTriPlaneVoxGO: the 3 * n_comp products are concatenated "
                              "and mixed by `basis`")
@@ -51,6 +63,9 @@ class VMTriPlaneVoxGO(TriPlaneVoxGO):
         if line_size is not None and int(line_size) < 1:
             raise ValueError(f'line_size must be at least 1, got {line_size}')
         object.__setattr__(self, 'n_comp', int(n_comp))          # read by _alloc_plane, which the base constructor calls
+        # rays that require grad are differentiated; not in get_kwargs (module docstring).  Set ahead of the base constructor,
+        # whose occupancy mask may already sample the model
+        object.__setattr__(self, 'raygrad', bool(raygrad))
         super().__init__(xyz_min, xyz_max, **kwargs)
         self.line_size = None if line_size is None else int(line_size)
         self.lines = nn.ParameterDict({k: nn.Parameter(self._alloc_line(self._line_n(k))) for k in PLANE_KEYS})
@@ -104,10 +119,19 @@ class VMTriPlaneVoxGO(TriPlaneVoxGO):
                 items.append((ln, (w, 0.0, weight_l1_lines)))
         return items
 
+    # ------------------------------------------------------------------ forward
+    def render(self, feats, rays_o, rays_d, viewdirs, global_step=None, **render_kwargs):
+        """The base's `render`; with `raygrad=True`, rays that require grad take DirectVoxGO._forward_raygrad on the same
+        `feats` (the module docstring says what that means)."""
+        if self.raygrad and _rays_want_grad(rays_o, rays_d):
+            return self._forward_raygrad(rays_o, rays_d, viewdirs, feats=feats, **render_kwargs)
+        return super().render(feats, rays_o, rays_d, viewdirs, global_step, **render_kwargs)
+
     # ------------------------------------------------------------------ features
     def sample_planes(self, pts, feats=None):
         """[M, rgbnet_dim].  `feats`: the planes under 'xy', 'yz', 'zx' and, optionally, lines under 'xy_line', 'yz_line',
-        'zx_line'; a missing line key means the model's own line.  The basis is always the model's."""
+        'zx_line'; a missing line key means the model's own line.  The basis is always the model's.  With `raygrad=True`,
+        positions that require grad receive theirs."""
         planes = self.planes if feats is None else feats
         lines = {k: planes[k + '_line'] if k + '_line' in planes else self.lines[k] for k in PLANE_KEYS}
-        return vm_sample(planes, lines, pts, self.xyz_min, self.xyz_max) @ self.basis
+        return vm_sample(planes, lines, pts, self.xyz_min, self.xyz_max, position_grad=self.raygrad) @ self.basis

@@ -41,7 +41,7 @@ extern "C" {
 /* version of this ABI; bumped on any signature change (6: the positional-encoding colour head; 7: the contracted
  * sampler and the distortion loss of unbounded scenes; 8: the tri-plane sampler; 9: the trilinear sample's gradient
  * with respect to the position; 10: the LIIF plane decoder; 11: the fused march's gradient with respect to its rays).
- * The two dvgo_plane_rows_*, the two dvgo_vm_*, the two dvgo_hash_*, the two dvgo_vm_density_*, the two dvgo_march_vm_density*, the two dvgo_march_contract_density*, the dvgo_contract_positions, the two dvgo_contract_ray_bwd* and the dvgo_hash_bwd_xyz entries were added without a bump, unlike the additions before them: an
+ * The two dvgo_plane_rows_*, the two dvgo_vm_*, the two dvgo_hash_*, the two dvgo_vm_density_*, the two dvgo_march_vm_density*, the two dvgo_march_contract_density*, the dvgo_contract_positions, the two dvgo_contract_ray_bwd* and the dvgo_hash_bwd_xyz entries were added without a bump, unlike the additions before them (the two dvgo_vm_*bwd_xyz entries were added the same way): an
  * existing test pins the value 11, and a library built before them is still caught at load, by the check that every declared entry is exported. */
 #define DVGO_ABI_VERSION 11
 int dvgo_abi_version(void);
@@ -858,6 +858,62 @@ int dvgo_vm_bwd(const float* grad_out,
                 float* g_xy, float* g_yz, float* g_zx, float* gl_xy, float* gl_yz, float* gl_zx,
                 int R, const float* xyz, const float* xyz_min, const float* xyz_max, int64_t M, int run, int mode,
                 void* stream);
+
+/* ---------------------------------------------------------------------------------
+ * The VM samplers' gradient with respect to the sample POSITION (csrc/vm_xyz.hip; INTEGRATION.md
+ * section 7), which dvgo_vm_bwd and dvgo_vm_density_bwd do not give.  Added without a bump of DVGO_ABI_VERSION, as the
+ * entries above were.  Planes, lines and the axis table are those of the VM block above.
+ * dvgo_vm_bwd_xyz:          grad_out [M, 3R], g_{s,r} = grad_out[m, s * R + r]  (dvgo_vm_fwd's output)
+ * dvgo_vm_density_bwd_xyz:  grad_out [M],     g_{s,r} = grad_out[m]             (dvgo_vm_density_fwd's output)
+ * Both: the values of planes and lines, xyz [M,3] -> grad_xyz [M,3].  Every row of grad_xyz is written with plain stores:
+ * no atomics, no workspace, nothing to zero beforehand.  One lane per sample, everything in the order below whatever the
+ * launch shape, the layout and the alignment (bitwise repeatable, the same bits for every layout of the same values).
+ * The cell (h0, w0) of plane s, the node n0 of line s and the float32 weights wh0, wh1, ww0, ww1, w0, w1 are the forward's
+ * own, bit for bit, so the derivative is that of the cell the forward chose (floor picks the upper cell on a lattice line).
+ * The forward zero-pads: a corner or node out of range is dropped and the weights are not clamped; the derivative drops the
+ * same corners and nodes, and there is no `inside` predicate.  A position less than one cell outside the box therefore has
+ * a non-zero derivative; more than one cell outside on any axis, or with a NaN coordinate, every term is dropped and the
+ * row is exactly 0.0 (for finite grad_out).
+ * Per sample m, in float32, no contraction but where fmaf is written:
+ *   out[0] = out[1] = out[2] = 0.0f
+ *   for s = xy, yz, zx, with (ah, aw, al) = (1, 2, 0), (0, 1, 2), (2, 0, 1) the world axes of rows, columns and line:
+ *     Ah = Aw = An = 0.0f
+ *     for r = 0 .. R - 1 ascending, v_ij the corner (h0 + i, w0 + j) and v0, v1 the nodes n0, n0 + 1 of component r:
+ *       p  = the forward's plane value: 0, then fmaf(v_ij, wh_i * ww_j, p) over the corners 00, 01, 10, 11 in range
+ *       l  = the forward's line value:  0, then fmaf(v0, w0, l), fmaf(v1, w1, l) over the nodes in range
+ *       dh = 0, then fmaf(v_ij, c_ij, dh) over the corners 00, 01, 10, 11 in range, c = (-ww0, -ww1, +ww0, +ww1)
+ *       dw = the same with c = (-wh0, +wh0, -wh1, +wh1)
+ *       dn = (v1 if n0 + 1 in range else 0.0f) - (v0 if n0 in range else 0.0f)
+ *       t = g_{s,r} * l;  Ah = fmaf(t, dh, Ah);  Aw = fmaf(t, dw, Aw)
+ *       u = g_{s,r} * p;  An = fmaf(u, dn, An)
+ *     the scales once, after the last component (an axis of size 1 has scale 0 and adds exactly 0):
+ *       out[ah] = out[ah] + Ah * ((float)(H_s - 1) / (max[ah] - min[ah]))
+ *       out[aw] = out[aw] + Aw * ((float)(W_s - 1) / (max[aw] - min[aw]))
+ *       out[al] = out[al] + An * ((float)(N_s - 1) / (max[al] - min[al]))
+ *   grad_xyz[m] = out: each world axis has received exactly three contributions, in the order s = xy, yz, zx.
+ * dvgo_vm_density_bwd_xyz passes over a sample whose grad_out[m] is exactly 0 (either sign): its row is exactly 0.0.
+ * R % 4 == 0 with channels-last, 16-byte aligned planes and lines (dvgo_vm_bwd_xyz: grad_out as well): 16-byte loads;
+ * everything else element by element through the strides.  The result is the same.
+ * M == 0 or R == 0: no-op, no pointer is looked at.  DVGO_EINVAL: negative M or R, a plane axis or line length < 1, null
+ * pointers (grad_out and grad_xyz among them).  DVGO_ERANGE: M * 3R >= 2^31.  The conditions and their order are
+ * dvgo_vm_fwd's; all of it is answered before any launch.
+ * --------------------------------------------------------------------------------- */
+int dvgo_vm_bwd_xyz(const float* xy, int H_xy, int W_xy, int64_t sC_xy, int64_t sH_xy, int64_t sW_xy,
+                    const float* yz, int H_yz, int W_yz, int64_t sC_yz, int64_t sH_yz, int64_t sW_yz,
+                    const float* zx, int H_zx, int W_zx, int64_t sC_zx, int64_t sH_zx, int64_t sW_zx,
+                    const float* l_xy, int N_xy, int64_t lC_xy, int64_t lN_xy,
+                    const float* l_yz, int N_yz, int64_t lC_yz, int64_t lN_yz,
+                    const float* l_zx, int N_zx, int64_t lC_zx, int64_t lN_zx,
+                    int R, const float* grad_out, const float* xyz, const float* xyz_min, const float* xyz_max, int64_t M,
+                    float* grad_xyz, void* stream);
+int dvgo_vm_density_bwd_xyz(const float* xy, int H_xy, int W_xy, int64_t sC_xy, int64_t sH_xy, int64_t sW_xy,
+                            const float* yz, int H_yz, int W_yz, int64_t sC_yz, int64_t sH_yz, int64_t sW_yz,
+                            const float* zx, int H_zx, int W_zx, int64_t sC_zx, int64_t sH_zx, int64_t sW_zx,
+                            const float* l_xy, int N_xy, int64_t lC_xy, int64_t lN_xy,
+                            const float* l_yz, int N_yz, int64_t lC_yz, int64_t lN_yz,
+                            const float* l_zx, int N_zx, int64_t lC_zx, int64_t lN_zx,
+                            int R, const float* grad_out, const float* xyz, const float* xyz_min, const float* xyz_max,
+                            int64_t M, float* grad_xyz, void* stream);
 
 /* ---------------------------------------------------------------------------------
  * Vector-matrix (VM) decomposed density (csrc/vm_density.hip): the 3R
