@@ -21,6 +21,11 @@ needs five.
                      the backward leaves one gradient per record and hands the scatter to dvgo_grid_sample_bwd.  With
                      `raygrad=True` it also returns the rays' gradient: the per-record gradients through the trilinear
                      position gradient and csrc/contract_raygrad.hip (camera-pose refinement of unbounded scenes).
+
+`fused_march(..., positions=True, raygrad=True)` and `fused_march_vm(..., raygrad=True)` differentiate their rays as well
+(csrc/march_pts_raygrad.hip: dvgo_march_ray_bwd_pts, dvgo_march_vm_ray_bwd, one wavefront per ray over the march's own
+records): the returned positions are differentiable, and the backward's first launch sums, per ray, the density's share
+of every record and the gradient that arrived for the positions.  The defaults refuse such rays, as before.
 """
 import math
 
@@ -234,7 +239,7 @@ _NO_ADAM = (None, None, None, 0.0, 0, None, None, None, 0.0, 0, 0.0, 0.0, 0.0, N
 
 class _FusedMarch(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, density, k0, rays_o, rays_d, cfg, capacity=False, positions=False):
+    def forward(ctx, density, k0, rays_o, rays_d, cfg, capacity=False, positions=False, raygrad=False):
         for x, n in ((rays_o, 'rays_o'), (rays_d, 'rays_d')):
             check_input(x, n); check_f32(x, n)
         if not (density.is_cuda and k0.is_cuda):
@@ -252,6 +257,9 @@ class _FusedMarch(torch.autograd.Function):
         # rays that require grad (camera-pose refinement): the backward also launches dvgo_march_ray_bwd (fused_march has
         # refused what that kernel does not differentiate)
         ray_grad = bool(ctx.needs_input_grad[2] or ctx.needs_input_grad[3]) and not (positions or ndc)
+        # ... and with positions (raygrad=True): dvgo_march_ray_bwd_pts, which takes the gradient that arrives for the
+        # returned positions in place of the k0 term
+        pts_grad = bool(ctx.needs_input_grad[2] or ctx.needs_input_grad[3]) and bool(positions and raygrad) and not ndc
         stride = cfg.ndc_samples if ndc else _rec_stride(cfg, N)
 
         setup_in_march = (not ndc) and stride > 0        # K1-K3 inside march_density: one launch less
@@ -325,11 +333,11 @@ class _FusedMarch(torch.autograd.Function):
         ctx.union = (bu, union_active, bu.n_union) if (bu is not None and bu.sparse) else None
         ctx.padded = padded
         ctx.density_meta, ctx.k0_meta = density, k0
-        ctx.ray_grad = ray_grad
+        ctx.ray_grad, ctx.pts_grad = ray_grad, pts_grad
         ctx.save_for_backward(rec2, n2, n_steps, cum if cum is not None else n_steps, off3, start, dirs, last,
-                              ray_id, step_id, *((rays_o, rays_d) if ray_grad else ()))
+                              ray_id, step_id, *((rays_o, rays_d) if (ray_grad or pts_grad) else ()))
         off3 = off3[:N + 1]
-        ctx.mark_non_differentiable(alpha, ray_id, step_id, off3, *((feat,) if positions else ()))
+        ctx.mark_non_differentiable(alpha, ray_id, step_id, off3, *((feat,) if (positions and not pts_grad) else ()))
         ctx.set_materialize_grads(False)     # no zero-filled [M3] int64 'gradients' for the id outputs (33 MB per step)
         return weights, alpha, last, feat, ray_id, step_id, off3
 
@@ -347,7 +355,7 @@ class _FusedMarch(torch.autograd.Function):
             want_k0 = ctx.needs_input_grad[1] and g_feat is not None and C > 0
             want_d = ctx.needs_input_grad[0]
             gw = gl = None
-            if want_d or ctx.ray_grad:
+            if want_d or ctx.ray_grad or ctx.pts_grad:
                 gw = g_w.contiguous() if g_w is not None else torch.zeros(M3, dtype=torch.float32, device=dev)
                 gl = g_last.contiguous() if g_last is not None else None
             rays = (None, None)
@@ -363,6 +371,15 @@ class _FusedMarch(torch.autograd.Function):
                        ctx.density_meta, X, Y, Z, ctx.k0_meta, C, sC, sX, sY, sZ, gw, gl,
                        g_feat.contiguous() if (g_feat is not None and C > 0) else None, go, gd, st)
                 rays = (go if ctx.needs_input_grad[2] else None, gd if ctx.needs_input_grad[3] else None)
+            elif ctx.pts_grad:
+                # the same rule: first.  `g_feat` is the gradient that arrived for the positions (None: none did)
+                rays_o, rays_d = ctx.saved_tensors[10:]
+                go = torch.empty((N, 3), dtype=torch.float32, device=dev)
+                gd = torch.empty((N, 3), dtype=torch.float32, device=dev)
+                L.call('dvgo_march_ray_bwd_pts', rec2, n2, n_steps, cum if stride == 0 else None, stride, off3, N, start, dirs,
+                       cfg.stepdist, cfg.xyz_min_h, cfg.xyz_max_h, last, cfg.interval, rays_o, rays_d, cfg.near, cfg.far,
+                       ctx.density_meta, X, Y, Z, gw, gl, g_feat.contiguous() if g_feat is not None else None, go, gd, st)
+                rays = (go if ctx.needs_input_grad[2] else None, gd if ctx.needs_input_grad[3] else None)
 
             def density_bwd(dst, dst_stride, kept, cursor=None, recs=None):
                 L.call('dvgo_march_density_bwd', rec2, n2, n_steps, cum if stride == 0 else None, stride, off3, N, start, dirs,
@@ -374,7 +391,7 @@ class _FusedMarch(torch.autograd.Function):
                 raise RuntimeError('capacity-mode forward (device-side sample count) needs the brick scatter backward for both grids')
             if plan is not None:
                 ctx.plan = None                                 # the fill cursors are consumed: one backward per forward
-                return _brick_backward(ctx, plan, density_bwd, g_feat, start, dirs, st) + rays + (None,) * 3
+                return _brick_backward(ctx, plan, density_bwd, g_feat, start, dirs, st) + rays + (None,) * 4
 
             # worth its two extra full-grid passes (zero 64 B, split 116 B per voxel) from ~1 kept sample per 6 voxels
             combined = (COMBINED_GRID_GRAD and want_k0 and want_d and C == 12 and M3 * COMBINED_MIN_RATIO >= X * Y * Z and tuple(ctx.density_meta.shape[2:]) == (X, Y, Z)
@@ -390,7 +407,7 @@ class _FusedMarch(torch.autograd.Function):
                 cap = grid_rows_capture._active
                 if cap is not None and cap.G is None and cap.density is ctx.density_meta and cap.k0 is ctx.k0_meta:
                     cap.G = G                  # the optimizer consumes the rows; no dense gradients are produced
-                    return (None, None) + rays + (None,) * 3
+                    return (None, None) + rays + (None,) * 4
                 grad_k0 = torch.empty_like(ctx.k0_meta, memory_format=torch.preserve_format)
                 grad_density = torch.empty_like(ctx.density_meta)
                 assert grad_k0.stride() == ctx.k0_meta.stride() and grad_density.is_contiguous()
@@ -404,7 +421,7 @@ class _FusedMarch(torch.autograd.Function):
                 if want_d:
                     grad_density = torch.zeros_like(ctx.density_meta)
                     density_bwd(grad_density, 1, None)
-        return (grad_density, grad_k0) + rays + (None,) * 3
+        return (grad_density, grad_k0) + rays + (None,) * 4
 
 
 def _brick_backward(ctx, plan, density_bwd, g_feat, start, dirs, st):
@@ -480,7 +497,7 @@ def fused_hit(rays_o, rays_d, cfg):
     return hit
 
 
-def fused_march(density, k0, rays_o, rays_d, cfg, capacity=False, positions=False):
+def fused_march(density, k0, rays_o, rays_d, cfg, capacity=False, positions=False, raygrad=False):
     """-> weights [M3], raw_alpha [M3], alphainv_last [N], k0 features [M3,C], ray_id, step_id [M3],
     off3 [N+1] (exclusive offsets of each ray's samples in the M3 arrays).
     `capacity=True`: no host synchronisation; the M3-sized outputs are allocated at their upper bound and only their
@@ -488,11 +505,17 @@ def fused_march(density, k0, rays_o, rays_d, cfg, capacity=False, positions=Fals
     `positions=True` (positional-encoding colour head): k0 must have zero channels (nothing is read from it) and the
     fourth output is the kept samples' positions [M3,3] instead of the features, with no gradient.
     `rays_o` / `rays_d` that require grad get one (csrc/march.hip: march_ray_bwd, launched first in the backward; the
-    stop-gradients are DirectVoxGO._forward_raygrad's); with `positions=True` or NDC sampling that is a NotImplementedError."""
-    if torch.is_grad_enabled() and (rays_o.requires_grad or rays_d.requires_grad) and (positions or cfg.ndc_samples > 0):
+    stop-gradients are DirectVoxGO._forward_raygrad's); with `positions=True` or NDC sampling that is a NotImplementedError.
+    `positions=True, raygrad=True` (HashVoxGO, VMTriPlaneVoxGO with raygrad='fused'): the same launches and the same bits, the
+    returned positions are differentiable, and the backward launches dvgo_march_ray_bwd_pts first (csrc/march_pts_raygrad.hip:
+    the density's share per record plus the gradient that arrived for the positions, summed per ray with the same
+    stop-gradients).  NDC sampling stays refused."""
+    if torch.is_grad_enabled() and (rays_o.requires_grad or rays_d.requires_grad) and (
+            (positions and not raygrad) or cfg.ndc_samples > 0):
         raise NotImplementedError('fused_march: rays that require grad are not differentiated through '
-                                  + ('the positional-encoding head\'s position input' if positions else 'NDC sampling'))
-    return _FusedMarch.apply(density, k0, rays_o.contiguous(), rays_d.contiguous(), cfg, capacity, positions)
+                                  + ('the positional-encoding head\'s position input' if (positions and not raygrad)
+                                     else 'NDC sampling'))
+    return _FusedMarch.apply(density, k0, rays_o.contiguous(), rays_d.contiguous(), cfg, capacity, positions, bool(raygrad))
 
 
 def _records_to_samples(rec2, n2, n3, off3, off2, N, stride, cfg, st, start, dirs, stepdist, n_steps=None):
@@ -530,7 +553,7 @@ class _FusedMarchVM(torch.autograd.Function):
     (kept samples, sizes the outputs) and M2 (records, sizes the backward's per-record gradient)."""
 
     @staticmethod
-    def forward(ctx, rays_o, rays_d, cfg, stride, *tensors):
+    def forward(ctx, rays_o, rays_d, cfg, stride, raygrad, *tensors):
         from .ops import PLANE_KEYS, _kernel_tensors, _line_geom, _plane_pack
         from .shade import march_positions
         for x, n in ((rays_o, 'rays_o'), (rays_d, 'rays_d')):
@@ -567,22 +590,47 @@ class _FusedMarchVM(torch.autograd.Function):
                                                                           dirs, cfg.stepdist, n_steps=n_steps)
             pts = march_positions(start, dirs, ray_id, step_id, cfg.stepdist)
         ctx.cfg, ctx.counts = cfg, (stride, N, M2, M3)
-        ctx.save_for_backward(rec2, n2, n_steps, off3, off2, start, dirs, last, *kt)
-        ctx.mark_non_differentiable(alpha, pts, ray_id, step_id, off3)
+        # rays that require grad (raygrad=True): the backward launches dvgo_march_vm_ray_bwd first, and the positions
+        # carry a gradient back to it
+        ctx.ray_grad = bool(raygrad) and bool(ctx.needs_input_grad[0] or ctx.needs_input_grad[1])
+        ctx.save_for_backward(rec2, n2, n_steps, off3, off2, start, dirs, last, *kt, *((rays_o, rays_d) if ctx.ray_grad else ()))
+        ctx.mark_non_differentiable(alpha, ray_id, step_id, off3, *(() if ctx.ray_grad else (pts,)))
         ctx.set_materialize_grads(False)
         return weights, alpha, last, pts, ray_id, step_id, off3
 
     @staticmethod
     @torch.autograd.function.once_differentiable
-    def backward(ctx, g_w, _g_alpha, g_last, _g_pts, _g_rid, _g_sid, _g_off):
+    def backward(ctx, g_w, _g_alpha, g_last, g_pts, _g_rid, _g_sid, _g_off):
         from .ops import _vm_grad_buffers, vm_density_bwd
-        rec2, n2, n_steps, off3, off2, start, dirs, last, *kt = ctx.saved_tensors
+        rec2, n2, n_steps, off3, off2, start, dirs, last, *kt = ctx.saved_tensors[:14]
         stride, N, M2, M3 = ctx.counts
         cfg = ctx.cfg
-        needs = ctx.needs_input_grad[4:]
-        if not any(needs):
-            return (None,) * 10
+        needs = ctx.needs_input_grad[5:]
+        if not any(needs) and not ctx.ray_grad:
+            return (None,) * 11
         dev = start.device
+        go = gd = None
+        if ctx.ray_grad:
+            # FIRST (the rule of _FusedMarch.backward), and also when the model is frozen: the kernel does its own walk over
+            # the records and reads the planes and lines the forward read
+            from .ops import PLANE_KEYS, _line_geom, _plane_pack
+            rays_o, rays_d = ctx.saved_tensors[14:]
+            g = _plane_pack(kt[:3])
+            for ln, k in zip(kt[3:], PLANE_KEYS):
+                g += [ln, *_line_geom(ln, k + '_line')]
+            go = torch.empty((N, 3), dtype=torch.float32, device=dev)
+            gd = torch.empty((N, 3), dtype=torch.float32, device=dev)
+            gw = g_w.contiguous() if g_w is not None else torch.zeros(M3, dtype=torch.float32, device=dev)
+            with L.device_of(start):
+                L.call('dvgo_march_vm_ray_bwd', rec2, n2, stride, off3, N, start, dirs, cfg.stepdist, cfg.xyz_min_h, cfg.xyz_max_h,
+                       last, cfg.interval, rays_o, rays_d, cfg.near, cfg.far, g[0], g[1], g[2], g[3], g[4], g[5], g[6], g[7], g[8],
+                       g[9], g[10], g[11], g[12], g[13], g[14], g[15], g[16], g[17], g[18], g[19], g[20], g[21], g[22], g[23], g[24],
+                       g[25], g[26], g[27], g[28], g[29], kt[0].shape[1], gw,
+                       g_last.contiguous() if g_last is not None else None,
+                       g_pts.contiguous() if g_pts is not None else None, go, gd, stream_of(start))
+            go, gd = (go if ctx.needs_input_grad[0] else None), (gd if ctx.needs_input_grad[1] else None)
+        if not any(needs):
+            return (go, gd) + (None,) * 9
         grads = _vm_grad_buffers(kt)                  # one zero fill for the six
         if M2 > 0:
             gw, gl, g_raw, xyz2 = _record_grads(g_w, g_last, M3, M2, dev)
@@ -590,25 +638,29 @@ class _FusedMarchVM(torch.autograd.Function):
                 L.call('dvgo_march_vm_density_bwd', rec2, n2, n_steps, stride, off3, off2, N, start, dirs, cfg.stepdist, last,
                        cfg.interval, gw, gl, g_raw, xyz2, stream_of(start))
             vm_density_bwd(g_raw, kt[:3], kt[3:], grads[:3], grads[3:], xyz2, cfg.xyz_min_t, cfg.xyz_max_t)
-        return (None, None, None, None, *[b if need else None for b, need in zip(grads, needs)])
+        return (go, gd, None, None, None, *[b if need else None for b, need in zip(grads, needs)])
 
 
-def fused_march_vm(density_planes, density_lines, rays_o, rays_d, cfg):
+def fused_march_vm(density_planes, density_lines, rays_o, rays_d, cfg, raygrad=False):
     """`fused_march(..., positions=True)` over a vector-matrix decomposed density (csrc/march_vm.hip) -> weights [M3],
     raw_alpha [M3], alphainv_last [N], pts [M3,3], ray_id, step_id [M3], off3 [N+1].  `density_planes` / `density_lines`: as
     `ops.vm_density` takes them; gradients flow into the six tensors (the per-record gradient of the raw density, then
     ops.vm_density_bwd).  The result does not depend on their layout.
     Returns None when no fixed record stride exists for `cfg` (`_rec_stride`: an infinite `far`, or scratch over the
-    budget): the caller then takes its op-by-op path.  NDC sampling and rays that require grad are refused."""
+    budget): the caller then takes its op-by-op path.  NDC sampling and rays that require grad are refused, the latter unless
+    `raygrad=True`: then the forward is the same launches and the same bits, the returned positions are differentiable, and
+    the backward launches dvgo_march_vm_ray_bwd first (csrc/march_pts_raygrad.hip: per record the raw-density gradient through
+    the position derivative of planes times lines, plus the gradient that arrived for the positions, summed per ray; it
+    runs also when none of the six tensors takes a gradient).  The stop-gradients are DirectVoxGO._forward_raygrad's."""
     from .ops import _plane_list
     if cfg.ndc_samples > 0:
         raise NotImplementedError('fused_march_vm: NDC sampling is not built for the decomposed density')
-    if torch.is_grad_enabled() and (rays_o.requires_grad or rays_d.requires_grad):
+    if not raygrad and torch.is_grad_enabled() and (rays_o.requires_grad or rays_d.requires_grad):
         raise NotImplementedError('fused_march_vm: rays that require grad are not differentiated through the decomposed density')
     stride = _rec_stride(cfg, rays_o.shape[0])
     if stride == 0:
         return None
-    return _FusedMarchVM.apply(rays_o.contiguous(), rays_d.contiguous(), cfg, stride,
+    return _FusedMarchVM.apply(rays_o.contiguous(), rays_d.contiguous(), cfg, stride, bool(raygrad),
                                *_plane_list(density_planes), *_plane_list(density_lines))
 
 

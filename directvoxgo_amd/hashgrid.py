@@ -24,7 +24,14 @@ in-order one -- so that pose.refine_poses can move the cameras.  The stop-gradie
 the kept set fixed, no gradient for viewdirs), and every key of the result has the bits of the `fused=False` forward on the
 same detached rays (where the fused colour-head kernel takes a `fused=True` model's head, raw_rgb and rgb_marched are that
 head's, as in DirectVoxGO._forward_raygrad).  Rays that do not require grad, and every path of a model without the option,
-are untouched by it: a default model keeps refusing such rays (fused.fused_march(positions=True) has no ray gradient).
+are untouched by it: a default model keeps refusing such rays (fused.fused_march(positions=True) has no ray gradient by default).
+
+`raygrad='fused'` sets `raygrad` and, on the instance, `fused_raygrad` (like `raygrad` no `get_kwargs` key and not in
+checkpoints: `load_model(HashVoxGO, path, raygrad='fused')`): with `self.fused`, rays that require grad stay on the fused march
+-- `fused_march(positions=True, raygrad=True)`, whose backward launches dvgo_march_ray_bwd_pts (csrc/march_pts_raygrad.hip)
+first: the density's share of every record plus what `hash_sample(..., position_grad=True)` returned for the positions,
+summed per ray -- with the fused forward's bits in every key and the same stop-gradients; `viewdirs` is detached.  With
+`fused=False` such rays take `_forward_raygrad` as before.  `pose.refine_poses(fused=True)` accepts the model only with it.
 
 Left out, each a NotImplementedError naming this class: k0_total_variation_add_grad (no k0), extract_mesh, data-parallel
 training, pose refinement without `raygrad=True`, posbase_pe.
@@ -100,6 +107,8 @@ class HashVoxGO(TriPlaneVoxGO):
         self.verbose = verbose
         self.fused = bool(fused)
         self.raygrad = bool(raygrad)              # rays that require grad are differentiated; not in get_kwargs (module docstring)
+        if raygrad == 'fused':                    # ... on the fused march where there is one (DirectVoxGO.fused_raygrad, per instance)
+            self.fused_raygrad = True
         self.fused_shade = True
         self.channels_last = True
         self._set_box(xyz_min, xyz_max)
@@ -159,8 +168,9 @@ class HashVoxGO(TriPlaneVoxGO):
     # ------------------------------------------------------------------ forward
     def forward(self, rays_o, rays_d, viewdirs, global_step=None, **render_kwargs):
         """The base's `render` (both paths) on the model's own table; with `raygrad=True`, rays that require grad take
-        DirectVoxGO._forward_raygrad (the module docstring says what that means)."""
-        if self.raygrad and _rays_want_grad(rays_o, rays_d):
+        DirectVoxGO._forward_raygrad (the module docstring says what that means), or, with `raygrad='fused'` on a fused
+        model, the base's fused render with the march's own ray backward."""
+        if self.raygrad and _rays_want_grad(rays_o, rays_d) and not (self.fused_raygrad and self.fused):
             return self._forward_raygrad(rays_o, rays_d, viewdirs, **render_kwargs)
         return self.render(None, rays_o, rays_d, viewdirs, global_step, **render_kwargs)
 

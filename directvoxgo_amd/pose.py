@@ -14,7 +14,10 @@ contraction of their rays (ops.contract_points; csrc/contract_raygrad.hip applie
 ray), on either of its render paths.  For the hash-grid model the colour features' share of the gradient comes from the
 hashed gather's own position derivative (ops.hash_sample(position_grad=True); csrc/hash_xyz.hip), on the op-by-op path.
 For the two vector-matrix models it comes from the position derivative of planes times lines (ops.vm_sample and, for
-TensoRFVoxGO's density, ops.vm_density with position_grad=True; csrc/vm_xyz.hip), on the op-by-op path as well.
+TensoRFVoxGO's density, ops.vm_density with position_grad=True; csrc/vm_xyz.hip), on the op-by-op path as well.  Constructed
+with raygrad='fused', those three models keep such rays on their fused march: the march's own ray backward
+(csrc/march_pts_raygrad.hip) sums, per ray, the density's share of every record and the gradient the samplers returned for the
+kept samples' positions.
 
 Pure torch: everything but `refine_poses`' model call runs on CPU tensors too.
 """
@@ -171,17 +174,23 @@ def refine_poses(model, refiner, images, cfg_train, render_kwargs, n_iters, n_ra
 
     A `HashVoxGO(raygrad=True)` renders such rays op by op (DirectVoxGO._forward_raygrad; the features' position derivative
     is csrc/hash_xyz.hip) whatever `model.fused` says: `fused=True` is a ValueError for it, and `train_model` steps density,
-    table and head by the eager optimiser.
+    table and head by the eager optimiser.  A `HashVoxGO(raygrad='fused')` (the instance carries `fused_raygrad`) is accepted
+    with `fused=True`: the render is `fused_march(positions=True, raygrad=True)`, `delta`'s gradient comes from
+    dvgo_march_ray_bwd_pts (csrc/march_pts_raygrad.hip), and with `train_model` the model is stepped by a `train.TrainStep`.
 
     A `VMTriPlaneVoxGO(raygrad=True)` and a `TensoRFVoxGO(raygrad=True)` render such rays op by op as well
     (DirectVoxGO._forward_raygrad; the position derivative of planes times lines is csrc/vm_xyz.hip, for the features and,
     in TensoRFVoxGO, for the density) whatever `model.fused` and `model.fused_march` say: `fused=True` is a ValueError for
-    them (the VM march has no ray backward), and `train_model` steps planes, lines, basis, the density tensors and the head
-    by the eager optimiser.
+    them, and `train_model` steps planes, lines, basis, the density tensors and the head by the eager optimiser.
+    Constructed with `raygrad='fused'` they are accepted with `fused=True` as the hash-grid model is: the VMTriPlaneVoxGO on
+    `fused_march(positions=True, raygrad=True)`, the TensoRFVoxGO on `fused_march_vm(raygrad=True)` (dvgo_march_vm_ray_bwd),
+    which requires `model.fused_march` (ValueError naming `fused_march` otherwise); with `train_model` a `train.TrainStep`
+    steps the model.  The instance's `fused_raygrad` is left as it was found.
 
     The gradient reaches `delta` through the sample positions only (DirectVoxGO._forward_raygrad states the stop-gradients).
     Supported: a plain DirectVoxGO with posbase_pe == 0, a HashVoxGO, a VMTriPlaneVoxGO or a TensoRFVoxGO constructed with
-    raygrad=True (with fused=False only) and a DirectContractedVoxGO constructed with raygrad=True.  DirectMPIGO (NDC warp),
+    raygrad=True (with fused=False only) or raygrad='fused' (either) and a DirectContractedVoxGO constructed with raygrad=True.
+    NDC rays, posbase_pe heads, data-parallel steps and the plain tri-plane / LIIF / bilinear-decoder models stay refused.  DirectMPIGO (NDC warp),
     the tri-plane, LIIF and bilinear-decoder models (plane samplers) and positional-encoding heads (position input of the
     head) lack their derivative and raise NotImplementedError, as do a DirectContractedVoxGO, a HashVoxGO, a VMTriPlaneVoxGO
     and a TensoRFVoxGO without raygrad."""
@@ -191,13 +200,17 @@ def refine_poses(model, refiner, images, cfg_train, render_kwargs, n_iters, n_ra
         raise NotImplementedError(f'refine_poses: {kind} is not supported: only a plain DirectVoxGO with posbase_pe == 0 has '
                                   f'the position derivative of its sampler{hint}')
     contracted = _contracted(model)
-    if fused and _hashed(model):
+    on_march = bool(model.__dict__.get('fused_raygrad'))           # raygrad='fused': the instance's own attribute
+    if fused and _hashed(model) and not on_march:
         raise ValueError('refine_poses(fused=True): HashVoxGO differentiates its rays on the op-by-op path only '
-                         '(fused_march(positions=True) has no ray gradient): call it with fused=False')
-    if fused and _vm(model):
+                         '(fused_march(positions=True) has no ray gradient by default): call it with fused=False, or construct it with '
+                         "raygrad='fused'")
+    if fused and _vm(model) and not on_march:
         raise ValueError(f'refine_poses(fused=True): {type(model).__name__} differentiates its rays on the op-by-op path only '
-                         '(the fused marches over positions and over the decomposed density have no ray gradient): call it '
-                         'with fused=False')
+                         '(the fused marches over positions and over the decomposed density have no ray gradient by default): call it '
+                         "with fused=False, or construct it with raygrad='fused'")
+    if fused and _vm(model) and hasattr(model, 'fused_march') and not model.fused_march:
+        raise ValueError(f'refine_poses(fused=True) needs a {type(model).__name__} on the fused march (fused_march=True)')
     if fused and contracted and not model.fused_march:
         raise ValueError('refine_poses(fused=True) needs a DirectContractedVoxGO on the fused march (fused_march=True)')
     if fused and not getattr(model, 'fused', False):

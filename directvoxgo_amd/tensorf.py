@@ -30,11 +30,19 @@ Occupancy goes through `dense_density()`, the op evaluated at the world_size lat
 
 `raygrad=True` (constructor option of the base, default False; not a `get_kwargs` key and not in checkpoints: pass it to the
 constructor or to `load_model(TensoRFVoxGO, path, raygrad=True)`): with grad mode on and `rays_o` or `rays_d` requiring grad,
-`forward` and `render` take DirectVoxGO._forward_raygrad whatever `fused` and `fused_march` say (the VM march has no ray
-backward): the density through `vm_density(..., position_grad=True)`, the features through `vm_sample(...,
+`forward` and `render` take DirectVoxGO._forward_raygrad whatever `fused` and `fused_march` say (the VM march's ray backward
+is `raygrad='fused'`, below): the density through `vm_density(..., position_grad=True)`, the features through `vm_sample(...,
 position_grad=True) @ basis`, both derivatives one kernel body (csrc/vm_xyz.hip).  Every key of the result has the bits of
 the op-by-op forward on the same detached rays; the stop-gradients are `_forward_raygrad`'s.  pose.refine_poses accepts the
 model only with this option.
+
+`raygrad='fused'` (the base's: `raygrad` plus the instance attribute `fused_raygrad`; `load_model(TensoRFVoxGO, path,
+raygrad='fused')`): with `fused` and `fused_march=True`, rays that require grad stay on the VM march --
+`fused_march_vm(..., raygrad=True)`, whose backward launches dvgo_march_vm_ray_bwd (csrc/march_pts_raygrad.hip) first: per
+record the raw-density gradient through the position derivative of planes times lines, plus what `vm_sample(...,
+position_grad=True) @ basis` returned for the positions, summed per ray; it runs with the model frozen too -- with the
+fused march's bits in every key and the same stop-gradients; `viewdirs` is detached.  Without `fused_march`, or where the
+march has no fixed record stride, such rays take `_forward_raygrad` as before.  `pose.refine_poses(fused=True)` needs both.
 
 Refused, each naming this class: voxel_count_views / pervoxel_lr, density_total_variation_add_grad (the regularisers of the
 density are the config keys train.DENSITY_REG_KEYS), export_volume, extract_mesh, refine_poses and rays that require grad
@@ -223,16 +231,23 @@ class TensoRFVoxGO(VMTriPlaneVoxGO):
         lines as in the base and, beside them, density tensors under the keys of `raw_density`.  With `raygrad=True`, rays
         that require grad take DirectVoxGO._forward_raygrad on the same `feats`."""
         _check_rays(rays_o)
-        if self.raygrad and _rays_want_grad(rays_o, rays_d):
+        want = _rays_want_grad(rays_o, rays_d)
+        # raygrad='fused': such rays stay on the VM march (its own ray backward) where this model is on it
+        on_march = bool(want and self.raygrad and self.fused_raygrad and self.fused and self.fused_march)
+        if self.raygrad and want and not on_march:
             return self._forward_raygrad(rays_o, rays_d, viewdirs, feats=feats, **render_kwargs)
         if self.fused_march:
-            if _rays_want_grad(rays_o, rays_d):
+            if want and not on_march:
                 self._refuse('rays that require grad', 'has no derivative of its density with respect to the sample positions: '
                                                        'construct it with raygrad=True')
             cfg = self._march_vm_cfg(render_kwargs['near'], render_kwargs['far'], render_kwargs['stepsize'])
-            march = fused_march_vm(*self._density_tensors(feats), rays_o, rays_d, cfg)
+            march = fused_march_vm(*self._density_tensors(feats), rays_o, rays_d, cfg, raygrad=on_march)
+            if march is None and on_march:          # no fixed record stride: op by op, as a plain render
+                return self._forward_raygrad(rays_o, rays_d, viewdirs, feats=feats, **render_kwargs)
             if march is not None:                   # None: no fixed record stride for these render_kwargs -> op by op
                 weights, alpha, alphainv_last, pts, ray_id, step_id, off3 = march
+                if on_march:
+                    viewdirs = viewdirs.detach()
                 rgb = self._colour(pts, feats, viewdirs, ray_id)
                 return self._finish_marched(len(rays_o), weights, alpha, alphainv_last, rgb, ray_id, step_id, off3,
                                             render_kwargs['bg'], render_kwargs.get('render_depth', False))

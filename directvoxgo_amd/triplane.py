@@ -228,8 +228,13 @@ class TriPlaneVoxGO(DirectVoxGO):
             cfg = self._march_cfg(render_kwargs['near'], render_kwargs['far'], render_kwargs['stepsize'])
             # the march writes the kept samples' positions where it would write k0 features; the stand-in has no channel
             no_k0 = self.density.detach()[:, :0]
+            # raygrad='fused' (HashVoxGO, VMTriPlaneVoxGO): rays that require grad stay on this path, the positions carry
+            # their gradient back to the march's own ray backward and `viewdirs` carries none
+            raygrad = bool(getattr(self, 'raygrad', False) and self.fused_raygrad)
+            if raygrad:
+                viewdirs = viewdirs.detach()
             weights, alpha, alphainv_last, pts, ray_id, step_id, off3 = fused_march(
-                self.density, no_k0, rays_o, rays_d, cfg, positions=True)
+                self.density, no_k0, rays_o, rays_d, cfg, positions=True, raygrad=raygrad)
             rgb = self._colour(pts, feats, viewdirs, ray_id)
             return self._finish_marched(len(rays_o), weights, alpha, alphainv_last, rgb, ray_id, step_id, off3,
                                         render_kwargs['bg'], render_kwargs.get('render_depth', False))

@@ -21,6 +21,13 @@ the per-ray sum the model's in-order one -- so that pose.refine_poses can move t
 of the `fused=False` forward on the same detached rays.  Rays that do not require grad, and every path of a model without
 the option, are untouched by it.
 
+`raygrad='fused'` sets `raygrad` and, on the instance, `fused_raygrad` (no `get_kwargs` key either, not in checkpoints:
+`load_model(VMTriPlaneVoxGO, path, raygrad='fused')`): with `self.fused`, rays that require grad stay on the fused march --
+`fused_march(positions=True, raygrad=True)`, whose backward launches dvgo_march_ray_bwd_pts (csrc/march_pts_raygrad.hip)
+first: the density's share of every record plus what `vm_sample(..., position_grad=True)` returned for the positions, summed
+per ray -- with the fused forward's bits in every key and the same stop-gradients; `viewdirs` is detached.  With
+`fused=False` such rays take `_forward_raygrad` as before.  `pose.refine_poses(fused=True)` accepts the model only with it.
+
 Everything the base leaves out stays out: extract_mesh, data-parallel training, pose refinement without `raygrad=True`, the
 plane decoders' options and the encoder's keys.  Not built either: the basis matmul fused into the sampler.  (The VM-decomposed density is
 tensorf.TensoRFVoxGO.)
@@ -66,6 +73,8 @@ class VMTriPlaneVoxGO(TriPlaneVoxGO):
         # rays that require grad are differentiated; not in get_kwargs (module docstring).  Set ahead of the base constructor,
         # whose occupancy mask may already sample the model
         object.__setattr__(self, 'raygrad', bool(raygrad))
+        if raygrad == 'fused':               # ... on the fused march where there is one (DirectVoxGO.fused_raygrad, per instance)
+            object.__setattr__(self, 'fused_raygrad', True)
         super().__init__(xyz_min, xyz_max, **kwargs)
         self.line_size = None if line_size is None else int(line_size)
         self.lines = nn.ParameterDict({k: nn.Parameter(self._alloc_line(self._line_n(k))) for k in PLANE_KEYS})
@@ -122,8 +131,9 @@ class VMTriPlaneVoxGO(TriPlaneVoxGO):
     # ------------------------------------------------------------------ forward
     def render(self, feats, rays_o, rays_d, viewdirs, global_step=None, **render_kwargs):
         """The base's `render`; with `raygrad=True`, rays that require grad take DirectVoxGO._forward_raygrad on the same
-        `feats` (the module docstring says what that means)."""
-        if self.raygrad and _rays_want_grad(rays_o, rays_d):
+        `feats` (the module docstring says what that means) or, with `raygrad='fused'` on a fused model, the base's fused
+        render with the march's own ray backward."""
+        if self.raygrad and _rays_want_grad(rays_o, rays_d) and not (self.fused_raygrad and self.fused):
             return self._forward_raygrad(rays_o, rays_d, viewdirs, feats=feats, **render_kwargs)
         return super().render(feats, rays_o, rays_d, viewdirs, global_step, **render_kwargs)
 

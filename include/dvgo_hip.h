@@ -338,6 +338,33 @@ int dvgo_march_ray_bwd(const dvgo_rec2_t* rec2, const int32_t* n2, const int64_t
                        const float* grad_weights /* [M3] */, const float* grad_last /* [N] */,
                        const float* grad_feat /* [M3,C] */, float* grad_o, float* grad_d, void* stream);
 
+/* dvgo_march_ray_bwd_pts: dvgo_march_ray_bwd for a march that hands its caller the kept samples' POSITIONS in place of k0
+ *   features (fused_march(positions=True): HashVoxGO, VMTriPlaneVoxGO; csrc/march_pts_raygrad.hip).
+ *   Added without a bump of DVGO_ABI_VERSION.  Every argument up to Z as in dvgo_march_ray_bwd, from the same forward; both
+ *   record layouts (n_steps_cumsum, or rec_stride > 0); grad_last [N] or NULL; grad_weights may be NULL when M3 == 0.
+ *   grad_pts [M3,3] row-major in the M3 order of dvgo_march_gather: the gradient that arrived for the positions, or NULL: no
+ *   second term.  The walk, g_d, the position p, the cell, the weights, the in-range test and the density chain are
+ *   dvgo_march_ray_bwd's (the same functions: csrc/march_records.h, csrc/xyz_corners.h).  Per record:
+ *       dX = chain over the density grid;  ax = fmaf(g_d, dX, 0);  likewise ay, az
+ *       g_p = (ax * ((float)(X-1) / (xyz_max[0] - xyz_min[0])), ay * ..., az * ...)
+ *       for a record kept by dvgo_march_gather (index i in the M3 order), when grad_pts is given:
+ *           g_p = g_p + grad_pts[3 i .. 3 i + 2]                     one float32 addition per component
+ *       lam = t_min + dist / |d|
+ *   A record with g_d == 0 and no pts term loads nothing and contributes exact zeros.  Per ray, dvgo_march_ray_bwd's sums in
+ *   its order:  grad_o[ray] = sum g_p,  grad_d[ray] = sum (lam * g_p);  every ray < n_rays written with plain stores by one
+ *   lane, zeros for a ray without records; no atomics, no LDS, no workspace, bitwise repeatable.  With grad_pts NULL the result
+ *   has the bits of dvgo_march_ray_bwd called with C = 0 and grad_feat NULL.
+ *   n_rays == 0: no-op, no pointer looked at.  DVGO_EINVAL: negative n_rays, an axis < 1, stepdist <= 0, then null required
+ *   pointers, neither n_steps_cumsum nor rec_stride > 0.  DVGO_ERANGE: n_rays * 64 >= 2^31. */
+int dvgo_march_ray_bwd_pts(const dvgo_rec2_t* rec2, const int32_t* n2, const int64_t* n_steps,
+                           const int64_t* n_steps_cumsum, int64_t rec_stride, const int64_t* off3, int64_t n_rays,
+                           const float* rays_start, const float* rays_dir, float stepdist,
+                           const float* xyz_min, const float* xyz_max, const float* alphainv_last, float interval,
+                           const float* rays_o, const float* rays_d, float near, float far,
+                           const float* density, int X, int Y, int Z,
+                           const float* grad_weights /* [M3] */, const float* grad_last /* [N] */,
+                           const float* grad_pts /* [M3,3] or NULL */, float* grad_o, float* grad_d, void* stream);
+
 /* ---------------------------------------------------------------------------------
  * Brick scatter: the grid-gradient sums of grid_sampler_3d_backward (behind lib/dvgo.py:321; 8*C float atomics per
  * sample in the reference) without atomics.  The lattice is cut into 8x8x8-voxel bricks; a workgroup owns one brick,
@@ -1010,6 +1037,43 @@ int dvgo_march_vm_density_bwd(const dvgo_rec2_t* rec2, const int32_t* n2, const 
                               const float* alphainv_last, float interval,
                               const float* grad_weights /* [M3] */, const float* grad_last /* [N] or NULL */,
                               float* g_raw /* [M2] */, float* xyz2 /* [M2,3] */, void* stream);
+
+/* dvgo_march_vm_ray_bwd: the gradient of dvgo_march_vm_density with respect to its RAYS (csrc/march_pts_raygrad.hip;
+ *   camera-pose refinement of TensoRFVoxGO on the fused march).  Added without a bump of
+ *   DVGO_ABI_VERSION.  One wavefront per ray; records at r * rec_stride only, metric steps only, as that march.
+ *   rec2, n2, rec_stride, off3, rays_start, rays_dir, stepdist, alphainv_last, interval, grad_weights, grad_last: as
+ *   dvgo_march_vm_density_bwd, from the same forward; xyz_min, xyz_max HOST pointers; rays_o, rays_d, near, far: what the
+ *   forward's ray setup read (t_min and |d| are recomputed by the same expressions); planes, lines, R in the argument order of
+ *   dvgo_vm_density_fwd: they must hold what the forward read.  grad_pts [M3,3] in the M3 order of dvgo_march_gather: the
+ *   gradient that arrived for the kept samples' positions, or NULL.
+ *   The kernel does its own walk (dvgo_march_vm_density_bwd's, chunk by chunk the same function) and reads neither g_raw nor
+ *   xyz2 of that entry: it runs when the model is frozen and that entry is never launched.  Per record, with g_raw as
+ *   dvgo_march_vm_density_bwd would leave it and p = fmaf(rays_dir, dist, rays_start) (the forward's bits):
+ *       (ox, oy, oz) = dvgo_vm_density_bwd_xyz's row at p for grad_out = g_raw: for s = xy, yz, zx: for r = 0 .. R - 1:
+ *           t = g_raw * l, u = g_raw * p_;  Ah = fmaf(t, dh, Ah), Aw = fmaf(t, dw, Aw), An = fmaf(u, dn, An)
+ *         with that entry's cell, weights, dropped corners and nodes (dh, dw the signed corner chains, dn = node1 - node0),
+ *         then the plane's scale once -- Ah * ((float)(H - 1) / extent), likewise Aw, An -- added to the world axes the plane's
+ *         rows, columns and line follow.  16-byte loads under dvgo_march_vm_density's rule, element loads otherwise: same bits.
+ *       g_p = (ox, oy, oz);  for a kept record (index i in the M3 order), when grad_pts is given: g_p = g_p + grad_pts[3 i ..]
+ *       lam = t_min + dist / |d|
+ *   A record whose g_raw is exactly 0 and which has no pts term is passed over.  Per ray, dvgo_march_ray_bwd's sums in its
+ *   order: grad_o[ray] = sum g_p, grad_d[ray] = sum (lam * g_p); plain stores by one lane, zeros for a ray without records;
+ *   no atomics, no LDS, no workspace, bitwise repeatable.
+ *   n_rays == 0: no-op, no pointer looked at.  DVGO_EINVAL: negative n_rays, R < 1, a plane axis or line length < 1,
+ *   stepdist <= 0, rec_stride <= 0, then null pointers (grad_weights, grad_last and grad_pts may be NULL).  DVGO_ERANGE:
+ *   n_rays * 64 or rec_stride >= 2^31. */
+int dvgo_march_vm_ray_bwd(const dvgo_rec2_t* rec2, const int32_t* n2, int64_t rec_stride, const int64_t* off3,
+                          int64_t n_rays, const float* rays_start, const float* rays_dir, float stepdist,
+                          const float* xyz_min, const float* xyz_max, const float* alphainv_last, float interval,
+                          const float* rays_o, const float* rays_d, float near, float far,
+                          const float* xy, int H_xy, int W_xy, int64_t sC_xy, int64_t sH_xy, int64_t sW_xy,
+                          const float* yz, int H_yz, int W_yz, int64_t sC_yz, int64_t sH_yz, int64_t sW_yz,
+                          const float* zx, int H_zx, int W_zx, int64_t sC_zx, int64_t sH_zx, int64_t sW_zx,
+                          const float* l_xy, int N_xy, int64_t lC_xy, int64_t lN_xy,
+                          const float* l_yz, int N_yz, int64_t lC_yz, int64_t lN_yz,
+                          const float* l_zx, int N_zx, int64_t lC_zx, int64_t lN_zx,
+                          int R, const float* grad_weights /* [M3] */, const float* grad_last /* [N] or NULL */,
+                          const float* grad_pts /* [M3,3] or NULL */, float* grad_o, float* grad_d, void* stream);
 
 /* ---------------------------------------------------------------------------------
  * Fused ray march over the contracted space of unbounded scenes (csrc/march_contract.hip; INTEGRATION.md
