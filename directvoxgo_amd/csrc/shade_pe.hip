@@ -532,9 +532,14 @@ int dvgo_shade_pe_wgrad(const float* G1, const float* gz, const uint64_t* masks,
                         void* stream) {
   if (M < 0 || n_parts <= 0 || P < 0 || E < 0) return DVGO_EINVAL;
   if (!pe_shape_ok(width, P, E, d_in)) return DVGO_ERANGE;
-  if (!G1 || !gz || !masks || !W3 || !H1 || !H2 || !pts || !freq || !emb || !ray_id || !part || !total) return DVGO_EINVAL;
   const int rec = (int)dvgo_shade_pe_record_size(width, d_in);
   hipStream_t s = (hipStream_t)stream;
+  if (M == 0) {   // an empty batch: its arrays are empty, so their pointers may be null; the gradients are zeros
+    if (!total) return DVGO_EINVAL;
+    DVGO_HIP_TRY(hipMemsetAsync(total, 0, (size_t)rec * sizeof(float), s));
+    return 0;
+  }
+  if (!G1 || !gz || !masks || !W3 || !H1 || !H2 || !pts || !freq || !emb || !ray_id || !part || !total) return DVGO_EINVAL;
   pe_wgrad_kernel<<<n_parts, PE_WG_THREADS, 0, s>>>(G1, gz, (const unsigned long long*)masks, W3, H1, H2, pts, freq, P, emb, E,
                                                    ray_id, M, d_in, rec, part);
   DVGO_LAUNCH_CHECK();

@@ -528,7 +528,11 @@ int dvgo_shade_wgrad(const float* G1, const float* gz, const uint64_t* masks, co
  * dvgo_shade_pe_wgrad: n_parts workgroups write partial records (part: n_parts * dvgo_shade_pe_record_size floats) and a
  *   second launch sums them into `total`, the compact record of dvgo_shade_wgrad
  *   { dW2 [width][width], dW1 [width][d_in], dW3 [3][width], db1 [width], db2 [width], db3 [3] }; X is rebuilt from
- *   pts, freq, emb and ray_id exactly as in the forward. */
+ *   pts, freq, emb and ray_id exactly as in the forward.
+ * M == 0 (a batch in which no sample survives) is valid for all three: arguments that do not depend on M are checked
+ *   as usual, then the call returns 0 without a launch and without looking at the array pointers, which may be NULL
+ *   (an empty tensor has no storage).  dvgo_shade_pe_fwd and dvgo_shade_pe_bwd write nothing; dvgo_shade_pe_wgrad
+ *   zeroes `total` (required), so the gradients of an empty batch are zeros, and leaves `part` alone. */
 int dvgo_march_positions(const float* rays_start, const float* rays_dir, const int64_t* ray_id, const int64_t* step_id,
                          int64_t M, float stepdist, float* pts, void* stream);
 int dvgo_shade_pe_fwd(const float* pts, const float* freq, int P, const float* emb, int E, const int64_t* ray_id, int64_t M,

@@ -5,7 +5,8 @@ gradients of directvoxgo_amd.shade.shade_posenc (lib/dvgo.py:528-534), with a ma
     rgb = sigmoid(relu(relu(x W1^T + b1) W2^T + b2) W3^T + b3)           no diffuse term
 
 Once x is formed this is the direct form of the feature-grid head, so the chain, magnitudes and gradients are
-tests/shade_oracle.py's, evaluated with x in place of cat([feat, emb[ray_id]]).
+tests/shade_oracle.py's, evaluated with x in place of cat([feat, emb[ray_id]]).  `rows` hands out that chain's per-row
+intermediates (h1, h2, gz, G1, the ReLU decisions) for the arrays the kernels store (tests/test_gpu_posenc_oracle.py).
 
 The position features.  The argument p * 2^j is exact in float32 (scaling by a power of two), so the kernel's sinf /
 cosf and the float64 sin / cos here see the same argument; the kernel's result is within a few ulp of its own value
@@ -53,6 +54,38 @@ def forward(P, pts, freq, emb, ray_id):
     """rgb, its magnitude and the per-row ReLU margin (float64).  `emb` is the per-ray view embedding as the kernel
     reads it (the float32 output of viewdir_embed)."""
     return S.forward(P, pos_embed(pts, freq), emb, ray_id, diffuse=False)
+
+
+ROW_KEYS = ('rgb', 'h1', 'h2', 'gz', 'G1')
+
+
+def rows(P, pts, freq, emb, ray_id, g_rgb):
+    """The per-row quantities the kernels store, float64: dict of values and dict of magnitudes for rgb, h1, h2
+    (magnitudes A1m, A2m), gz (Bgz) and G1 (B1), all bound K_ROW: each is a prefix of the chain K_ROW was argued for.
+    The values dict also holds the ReLU decisions k1, k2 [M,width] (bool) and 'margin' [M].  These are the intermediates
+    of shade_oracle's chain, not a second statement of it."""
+    out = {k: [] for k in ROW_KEYS + ('k1', 'k2', 'margin')}
+    mags = {k: [] for k in ROW_KEYS}
+    x = pos_embed(pts, freq)
+    with torch.no_grad():
+        for s in range(0, x.shape[0], S.CHUNK):
+            sl = slice(s, s + S.CHUNK)
+            st = S._rows(P, x[sl], emb, ray_id[sl], False)
+            gz, Bgz, _, _, G1, B1 = S._back_rows(P, st, g_rgb[sl])
+            margin = torch.minimum(S._relu_margin(st['z1'], st['A1']), S._relu_margin(st['z2'], st['A2']))
+            for k, v, m in (('rgb', st['rgb'], st['rgb_mag']), ('h1', st['h1'], st['A1m']), ('h2', st['h2'], st['A2m']),
+                            ('gz', gz, Bgz), ('G1', G1, B1)):
+                out[k].append(v)
+                mags[k].append(m)
+            for k, v in (('k1', st['k1']), ('k2', st['k2']), ('margin', margin)):
+                out[k].append(v)
+    width = P[0].shape[0]
+    empty = dict(rgb=(0, 3), gz=(0, 3), margin=(0,))
+
+    def cat(k, parts, dtype=torch.float64):
+        return torch.cat(parts) if parts else torch.empty(empty.get(k, (0, width)), dtype=dtype, device=x.device)
+    return ({k: cat(k, v, torch.bool if k in ('k1', 'k2') else torch.float64) for k, v in out.items()},
+            {k: cat(k, v) for k, v in mags.items()})
 
 
 def forward_backward(P, pts, freq, emb, ray_id, g_rgb):

@@ -105,6 +105,20 @@ def _rows(P, feat, emb, ray_id, diffuse):
                 rgb_mag=ds * A3 + rgb + TINY)
 
 
+def _back_rows(P, st, g_rgb):
+    """The data gradients of the rows of `st` (= _rows(...)) down to layer 1, value and magnitude:
+    gz, Bgz [M,3]; G2, B2 and G1, B1 [M,width]."""
+    W1, b1, W2, b2, W3, b3 = P
+    g = g_rgb.double()
+    gz = g * st['ds']
+    Bgz = g.abs() * st['rgb_mag'] + gz.abs()
+    G2 = torch.where(st['k2'], gz @ W3, 0.0)
+    B2 = torch.where(st['k2'], Bgz @ W3.abs(), 0.0)
+    G1 = torch.where(st['k1'], G2 @ W2, 0.0)
+    B1 = torch.where(st['k1'], B2 @ W2.abs(), 0.0)
+    return gz, Bgz, G2, B2, G1, B1
+
+
 def forward_backward(P, feat, emb, ray_id, g_rgb, diffuse):
     """Everything, float64 on feat's device: dict of value / magnitude pairs
       rgb, g_feat: [M, 3], [M, C] (per row, bound K_ROW);  gW1 gb1 gW2 gb2 gW3 gb3 (batch sums, bound K_SUM);
@@ -125,13 +139,7 @@ def forward_backward(P, feat, emb, ray_id, g_rgb, diffuse):
             st = _rows(P, feat[sl], emb, ray_id[sl], diffuse)
             out['rgb'][sl], mags['rgb'][sl] = st['rgb'], st['rgb_mag']
             out['margin'][sl] = torch.minimum(_relu_margin(st['z1'], st['A1']), _relu_margin(st['z2'], st['A2']))
-            g = g_rgb[sl].double()
-            gz = g * st['ds']
-            Bgz = g.abs() * st['rgb_mag'] + gz.abs()
-            G2 = torch.where(st['k2'], gz @ W3, 0.0)
-            B2 = torch.where(st['k2'], Bgz @ W3.abs(), 0.0)
-            G1 = torch.where(st['k1'], G2 @ W2, 0.0)
-            B1 = torch.where(st['k1'], B2 @ W2.abs(), 0.0)
+            gz, Bgz, G2, B2, G1, B1 = _back_rows(P, st, g_rgb[sl])
             gx, Bx = G1 @ W1, B1 @ W1.abs()
             if diffuse:
                 out['g_feat'][sl] = torch.cat([gz, gx[:, :n_view]], 1)

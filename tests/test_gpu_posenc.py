@@ -81,6 +81,37 @@ def test_forward_matches_reference_orchestration(name, fused):
         np.testing.assert_allclose(p.grad.cpu().numpy(), g['grad_rgbnet_' + k], rtol=1e-3, atol=1e-6)
 
 
+@pytest.mark.parametrize('fused', [True, False])
+def test_batch_in_which_no_sample_survives(fused):
+    """Empty space everywhere (test_gpu_forward's case, for the positional-encoding model): no sample reaches the head,
+    which must answer with an empty colour array and, after backward, no or zero parameter gradients.  The model then
+    trains on a normal batch as if nothing had happened."""
+    g = load_golden('forward_fine_posenc')
+    m = build_model(g, fused)
+    with torch.no_grad():
+        m.density.fill_(-20.0)
+    ro, rd, vd = cu(g['rays_o']), cu(g['rays_d']), cu(g['viewdirs'])
+    res = m(ro, rd, vd, global_step=0, near=float(g['near']), far=float(g['far']), bg=1, stepsize=0.5, render_depth=True)
+    assert res['weights'].numel() == 0 and res['raw_rgb'].shape == (0, 3)
+    assert torch.allclose(res['rgb_marched'], torch.ones_like(res['rgb_marched']))      # pure background
+    assert torch.all(res['alphainv_last'] == 1) and torch.all(res['depth'] == 0)
+    loss_fn(res, cu(g['target']), ro.shape[0]).backward()
+    assert m.density.grad is None or float(m.density.grad.abs().sum()) == 0.0
+    for k, p in m.rgbnet.named_parameters():
+        assert p.grad is None or float(p.grad.abs().max()) == 0.0, k
+    assert m.k0.grad is None
+    # a normal batch next: the fixture's loss and gradients, to test_forward_matches_reference_orchestration's tolerances
+    with torch.no_grad():
+        m.density.copy_(torch.from_numpy(g['density']))
+    m.zero_grad(set_to_none=True)
+    res, loss = run(m, g)
+    assert np.array_equal(res['ray_id'].cpu().numpy(), g['out_ray_id'])
+    np.testing.assert_allclose(float(loss), float(g['loss']), rtol=1e-5)
+    np.testing.assert_allclose(m.density.grad.cpu().numpy(), g['grad_density'], rtol=1e-4, atol=1e-6)
+    for k, p in m.rgbnet.named_parameters():
+        np.testing.assert_allclose(p.grad.cpu().numpy(), g['grad_rgbnet_' + k], rtol=1e-3, atol=1e-6)
+
+
 def _head(P, seed, d_in=None):
     from directvoxgo_amd.dvgo import make_rgbnet
     torch.manual_seed(seed)

@@ -84,6 +84,54 @@ def test_reference_posenc_checkpoint_loads():
     assert 1 not in ck['optimizer_state_dict']['state'] and 0 in ck['optimizer_state_dict']['state']
 
 
+@pytest.mark.parametrize('P,E', [(4, 6), (4, 27)], ids=['dIn33', 'dIn54'])
+def test_oracle_rows_equal_float64_autograd(P, E):
+    """PO.rows against float64 torch autograd on the module tree, one odd and one even d_in: hooks on the two ReLUs give
+    h1 and h2, the gradients with respect to z1 and z3 give G1 and gz.  Both sides are float64 statements of the same
+    chain: they agree to float64 rounding, far inside anything float32 could tell apart."""
+    from directvoxgo_amd.dvgo import make_rgbnet
+    torch.manual_seed(7 + P + E)
+    M, N, d_in = 300, 17, 3 + 6 * P + E
+    net = make_rgbnet(d_in, 128, 3).double()
+    with torch.no_grad():
+        for p in net.parameters():
+            p.add_(torch.randn_like(p) * 0.05)
+    pts = torch.rand(M, 3) * 3 - 1.5
+    freq = torch.tensor([2.0 ** i for i in range(P)])
+    emb = torch.rand(N, E) * 2 - 1
+    rid = torch.randint(N, (M,))
+    g = torch.randn(M, 3)
+    seen = {}
+    hooks = [net[0].register_forward_hook(lambda mod, i, o: (seen.__setitem__('z1', o), o.clone())[1]),   # (ReLU is in place)
+             net[1].register_forward_hook(lambda mod, i, o: seen.__setitem__('h1', o.detach().clone())),
+             net[2][1].register_forward_hook(lambda mod, i, o: seen.__setitem__('h2', o.detach().clone()))]
+    x = torch.cat([PO.pos_embed(pts, freq), emb.double()[rid]], -1)
+    z3 = net(x)
+    for h in hooks:
+        h.remove()
+    rgb = torch.sigmoid(z3)
+    G1, gz = torch.autograd.grad(rgb, [seen['z1'], z3], g.double())
+    ref = dict(rgb=rgb.detach(), h1=seen['h1'], h2=seen['h2'], gz=gz, G1=G1)
+    out, mags = PO.rows(PO.params_of(net), pts, freq, emb, rid, g)
+    assert set(mags) == set(PO.ROW_KEYS) and set(out) == set(PO.ROW_KEYS) | {'k1', 'k2', 'margin'}
+    for k in PO.ROW_KEYS:
+        assert out[k].dtype == torch.float64 and out[k].shape == ref[k].shape == mags[k].shape, k
+        assert bool((mags[k] >= out[k].abs() * (1 - 1e-12)).all()), k        # a magnitude bounds its value
+        assert bool(((out[k] - ref[k]).abs() <= 1e-12 * mags[k]).all()), k
+    assert torch.equal(out['k1'], seen['z1'].detach() > 0) and torch.equal(out['k1'], ref['h1'] > 0)
+    assert torch.equal(out['k2'], ref['h2'] > 0)
+    assert 0.2 < float(out['k1'].double().mean()) < 0.8 and 0.2 < float(out['k2'].double().mean()) < 0.8
+    # the margin is forward()'s, and the batch sums of forward_backward are sums of these rows
+    assert torch.equal(out['margin'], PO.forward(PO.params_of(net), pts, freq, emb, rid)[2])
+    full, _ = PO.forward_backward(PO.params_of(net), pts, freq, emb, rid, g)
+    assert torch.allclose(full['gb1'], out['G1'].sum(0), rtol=1e-12, atol=1e-14)
+    assert torch.allclose(full['gb3'], out['gz'].sum(0), rtol=1e-12, atol=1e-14)
+    assert torch.allclose(full['gW1'], out['G1'].t() @ x.detach(), rtol=1e-10, atol=1e-13)
+    # an empty batch has empty rows of the right shapes
+    e, em = PO.rows(PO.params_of(net), pts[:0], freq, emb, rid[:0], g[:0])
+    assert e['rgb'].shape == (0, 3) and e['G1'].shape == (0, 128) and e['k1'].dtype == torch.bool and em['gz'].shape == (0, 3)
+
+
 @pytest.mark.parametrize('name', FIXTURES)
 def test_oracle_reproduces_the_reference_head(name):
     """The fixture keeps the rows the reference fed its colour head (positions first): the oracle's position encoding
