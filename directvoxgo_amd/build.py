@@ -11,7 +11,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 SO = os.path.join(CSRC, 'libdvgo_hip.so')
-SOURCES = ['sampling.hip', 'pointwise.hip', 'composite.hip', 'grid_sample.hip', 'march.hip', 'optim.hip', 'shade.hip', 'shade_x3.hip', 'loss.hip', 'brick.hip', 'maintain.hip', 'metrics.hip', 'mesh.hip', 'shade_pe.hip', 'contract.hip', 'triplane.hip', 'grid_sample_xyz.hip', 'liif.hip', 'plane_rows.hip', 'vm.hip', 'vm_density.hip', 'plane_tv.hip', 'hashgrid.hip', 'march_vm.hip', 'march_contract.hip', 'contract_raygrad.hip', 'hash_xyz.hip', 'vm_xyz.hip', 'march_pts_raygrad.hip']
+SOURCES = ['sampling.hip', 'pointwise.hip', 'composite.hip', 'grid_sample.hip', 'march.hip', 'optim.hip', 'shade.hip', 'shade_x3.hip', 'loss.hip', 'brick.hip', 'maintain.hip', 'metrics.hip', 'mesh.hip', 'shade_pe.hip', 'contract.hip', 'triplane.hip', 'grid_sample_xyz.hip', 'liif.hip', 'plane_rows.hip', 'vm.hip', 'vm_density.hip', 'plane_tv.hip', 'hashgrid.hip', 'march_vm.hip', 'march_contract.hip', 'contract_raygrad.hip', 'hash_xyz.hip', 'vm_xyz.hip', 'march_raygrad.hip']
 HEADERS = ['common.h', 'scan.h', 'x3.h', 'xyz_corners.h', 'plane2d.h', 'vm_common.h', 'hash_common.h', 'contract_common.h', 'march_records.h', os.path.join('..', '..', 'include', 'dvgo_hip.h')]
 
 # -ffp-contract=off : a*b+c is fused only where the source says fmaf(), so that index and

@@ -156,7 +156,7 @@ __device__ __forceinline__ void dvgo_sample_pos(const float* __restrict__ start,
 
 // K1 + K2 + K3 of one ray (render_utils_kernel.cu:11-73), expression for expression what sampling.hip's ray_setup_kernel
 // computes (same flags, hence the same bits): slab test -> t_min / t_max, step count, start point and unit direction.
-struct RaySetup { float tmin, tmax, sx, sy, sz, dx, dy, dz, rnorm; int64_t n; };     // rnorm = |d| (march.hip's ray gradient: lam)
+struct RaySetup { float tmin, tmax, sx, sy, sz, dx, dy, dz, rnorm; int64_t n; };     // rnorm = |d| (march_raygrad.hip: lam)
 __device__ __forceinline__ RaySetup dvgo_ray_setup(float ox, float oy, float oz, float dx, float dy, float dz,
                                                    float mnx, float mny, float mnz, float mxx, float mxy, float mxz,
                                                    float near, float far, float stepdist) {

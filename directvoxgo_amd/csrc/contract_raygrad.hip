@@ -14,6 +14,7 @@
 // contiguous bytes and the 64 rows of a chunk are 768 contiguous bytes.  No atomics, no LDS, no workspace, nothing to zero
 // beforehand: bitwise repeatable.
 #include "contract_common.h"
+#include "march_records.h"      // wave_sum
 
 struct ContractRayBwdParams {
   float cx, cy, cz, rx, ry, rz;   // centre and radius of the foreground box
@@ -45,12 +46,6 @@ __device__ __forceinline__ void contract_point_bwd(const ContractRay& R, float t
     else if (ay >= az)        hy = hy + (py < 0.0f ? -c : c);
     else                      hz = hz + (pz < 0.0f ? -c : c);
   }
-}
-
-__device__ __forceinline__ float contract_wave_sum(float v) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
-  return v;
 }
 
 __device__ __forceinline__ int64_t crb_clamp(int64_t v, int64_t lo, int64_t hi) { return v < lo ? lo : (v > hi ? hi : v); }
@@ -98,8 +93,8 @@ contract_ray_bwd_kernel(const float* __restrict__ rays_o, const float* __restric
     Ax = Ax + hx; Ay = Ay + hy; Az = Az + hz;
     Bx = Bx + t * hx; By = By + t * hy; Bz = Bz + t * hz;
   }
-  Ax = contract_wave_sum(Ax); Ay = contract_wave_sum(Ay); Az = contract_wave_sum(Az);
-  Bx = contract_wave_sum(Bx); By = contract_wave_sum(By); Bz = contract_wave_sum(Bz);
+  Ax = wave_sum(Ax); Ay = wave_sum(Ay); Az = wave_sum(Az);
+  Bx = wave_sum(Bx); By = wave_sum(By); Bz = wave_sum(Bz);
   const bool any_bad = __ballot(bad) != 0ull;
   if (lane != 0) return;
   float ox = Ax / P.rx, oy = Ay / P.ry, oz = Az / P.rz;

@@ -14,7 +14,7 @@
 // (common.h: dvgo_tri_value_c1 explains what the conditional form costs); a select drops the out-of-range ones, which
 // leaves the accumulation order above untouched.  Every row of grad_xyz is written by its lane with plain stores: no
 // atomics, no workspace, nothing to zero beforehand.
-#include "xyz_corners.h"   // XyzCorners, dvgo_xyz_corners, DVGO_XYZ_CHANNEL: shared with march.hip's ray-gradient kernel
+#include "xyz_corners.h"   // XyzCorners, dvgo_xyz_corners, DVGO_XYZ_CHANNEL: shared with march_raygrad.hip's dense kernels
 
 template <int VEC>   // VEC = 4: channels-last with C % 4 == 0 and 16-B aligned bases; 1: generic (element strides)
 __global__ void __launch_bounds__(DVGO_BLOCK)

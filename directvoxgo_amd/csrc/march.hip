@@ -20,7 +20,6 @@
 #include "common.h"
 #include "march_records.h"      // the lane mask, the suffix sum, the plain walk, the chunk commit and the backward chunk
 #include "scan.h"
-#include "xyz_corners.h"
 
 // inclusive product scan across the wave
 __device__ __forceinline__ float wave_prod_scan(float v, int lane) {
@@ -30,14 +29,6 @@ __device__ __forceinline__ float wave_prod_scan(float v, int lane) {
     if (lane >= d) v *= o;
   }
   return v;
-}
-
-// Scratch records of ray r start at cum[r]-n_steps[r] (exact, ray-major M0 layout) when the
-// inclusive cumsum is given, else at r*rec_stride (fixed stride = an upper bound of n_steps,
-// which saves the scan and the host read of M0).
-__device__ __forceinline__ int64_t rec_base(const int64_t* __restrict__ cum, const int64_t* __restrict__ n_steps,
-                                            int64_t rec_stride, int64_t ray) {
-  return cum ? (cum[ray] - n_steps[ray]) : ray * rec_stride;
 }
 
 // run-time selectable kernel variants (A/B measurements in one process; defaults = fastest measured)
@@ -504,12 +495,6 @@ march_gather_kernel(const dvgo_rec2_t* __restrict__ rec2, const int32_t* __restr
 // ----------------------------------------------------------------------------------
 // march_composite: one wavefront per ray over [off3[r], off3[r+1]).
 // ----------------------------------------------------------------------------------
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
-  return v;
-}
-
 __global__ void __launch_bounds__(DVGO_BLOCK)
 march_composite_kernel(const float* __restrict__ weights, const float* __restrict__ rgb,
                        const int64_t* __restrict__ step_id, const int64_t* __restrict__ off3,
@@ -876,122 +861,6 @@ march_density_bwd_kernel(const dvgo_rec2_t* __restrict__ rec2, const int32_t* __
   }
 }
 
-// ----------------------------------------------------------------------------------
-// march_ray_bwd: the derivative of the march with respect to its RAYS (camera-pose refinement, pose.py), the sibling of
-// march_density_bwd.  Same walk over the ray's rec2 records -- chunks of 64 from the far end through the same
-// march_bwd_chunk (march_records.h), the position p from the same expressions, hence the same bits -- but where
-// that kernel scatters g_d to the grid, this one keeps the record's position gradient
-//     g_p = scale * (g_d * d density / d g  +  sum_c grad_feat[kept, c] * d k0_c / d g)
-// (the corner chains of dvgo_grid_sample_bwd_xyz, xyz_corners.h: the density grid as the first channel, then, for a
-// record that survived into the M3 arrays, the feature channels ascending) and reduces it per ray with the sample's ray
-// parameter lam = t_min + dist / |d| (a constant of the derivative: INTEGRATION.md section 7):
-//     grad_o[ray] = sum g_p        grad_d[ray] = sum lam * g_p
-// in float32, a butterfly over the 64 lanes per chunk (inactive lanes add 0), chunks far to near into one accumulator per
-// component: a fixed order, so the result is bitwise repeatable.  Lane 0 writes both rows with plain stores, zeros for a
-// ray without records: no atomics, no LDS, no workspace, nothing to zero beforehand.
-// VEC = 4: k0 channels-last with C % 4 == 0 and 16-byte aligned k0 / grad_feat: the eight corner rows of a channel group
-// travel as float4s in flight together (the scheduling barrier keeps hipcc from sinking each load to its corner's fmaf:
-// profiles/raygrad/README.md); VEC = 1: element strides, one channel at a time.
-// ----------------------------------------------------------------------------------
-template <int VEC>
-__global__ void __launch_bounds__(DVGO_BLOCK)
-march_ray_bwd_kernel(const dvgo_rec2_t* __restrict__ rec2, const int32_t* __restrict__ n2,
-                     const int64_t* __restrict__ n_steps, const int64_t* __restrict__ cum,
-                     int64_t rec_stride, const int64_t* __restrict__ off3, int64_t n_rays,
-                     const float* __restrict__ rays_start, const float* __restrict__ rays_dir,
-                     MarchParams P, const float* __restrict__ alphainv_last,
-                     const float* __restrict__ rays_o, const float* __restrict__ rays_d, float near, float far,
-                     const float* __restrict__ density, const float* __restrict__ k0, int C, int64_t sC, int64_t sX,
-                     int64_t sY, int64_t sZ, const float* __restrict__ grad_weights,
-                     const float* __restrict__ grad_last, const float* __restrict__ grad_feat,
-                     float* __restrict__ grad_o, float* __restrict__ grad_d) {
-  const int64_t ray = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-  const int lane = threadIdx.x & 63;
-  if (ray >= n_rays) return;
-  const int c2 = __builtin_amdgcn_readfirstlane(n2[ray]);
-  float Ax = 0.f, Ay = 0.f, Az = 0.f, Bx = 0.f, By = 0.f, Bz = 0.f;
-  if (c2 > 0) {
-    const int64_t cs0 = rec_base(cum, n_steps, rec_stride, ray);
-    const int64_t o3 = off3[ray];
-    int c3_rem = (int)(off3[ray + 1] - o3);
-    const float sx = rays_start[3 * ray], sy = rays_start[3 * ray + 1], sz = rays_start[3 * ray + 2];
-    const float dx = rays_dir[3 * ray], dy = rays_dir[3 * ray + 1], dz = rays_dir[3 * ray + 2];
-    const RaySetup R = dvgo_ray_setup(rays_o[3 * ray], rays_o[3 * ray + 1], rays_o[3 * ray + 2], rays_d[3 * ray], rays_d[3 * ray + 1],
-                                      rays_d[3 * ray + 2], P.mnx, P.mny, P.mnz, P.mxx, P.mxy, P.mxz, near, far, P.stepdist);
-    const int64_t YZ = (int64_t)P.Y * P.Z;
-    const float scale_x = (float)(P.X - 1) / (P.mxx - P.mnx);
-    const float scale_y = (float)(P.Y - 1) / (P.mxy - P.mny);
-    const float scale_z = (float)(P.Z - 1) / (P.mxz - P.mnz);
-    const unsigned long long lt = lanemask_lt(lane);
-    float acc = (grad_last ? grad_last[ray] : 0.0f) * alphainv_last[ray];
-    for (int hi = c2; hi > 0; hi -= 64) {
-      const int lo = max(0, hi - 64);
-      const MarchBwdChunk ck = march_bwd_chunk(rec2, cs0, lo, hi - lo, lane, lt, o3, c3_rem, acc, grad_weights);
-      const bool act = ck.act, flag = ck.flag;
-      const int step = ck.step, rank = ck.rank;
-      float gx = 0.f, gy = 0.f, gz = 0.f, lam = 0.f;
-      if (act) {
-        const float g_d = ck.g_d(P.interval);
-        const float dist = march_dist(P.stepdist, step);
-        const float px = fmaf(dx, dist, sx), py = fmaf(dy, dist, sy), pz = fmaf(dz, dist, sz);
-        const TriSetup t = dvgo_tri_setup(px, py, pz, P.mnx, P.mny, P.mnz, P.mxx, P.mxy, P.mxz, P.X, P.Y, P.Z);
-        const bool feat = flag && grad_feat != nullptr && C > 0;
-        if (g_d != 0.0f || feat) {           // (else: exact zeros, no loads)
-          const XyzCorners k = dvgo_xyz_corners(t, P.X, P.Y, P.Z, YZ, (int64_t)P.Z, 1);     // offsets: the density grid's
-          float ax = 0.f, ay = 0.f, az = 0.f;
-          {
-            float dv[8];
-#pragma unroll
-            for (int c = 0; c < 8; ++c) dv[c] = density[k.off[c]];
-            __builtin_amdgcn_sched_barrier(0);
-            DVGO_XYZ_CHANNEL(dv[n], g_d);
-          }
-          if (feat) {
-            int64_t koff[8];                 // the same clamped corners in k0's strides
-#pragma unroll
-            for (int c = 0; c < 8; ++c) {
-              const int i = min(max(t.i0 + ((c >> 2) & 1), 0), P.X - 1);
-              const int j = min(max(t.j0 + ((c >> 1) & 1), 0), P.Y - 1);
-              const int kk = min(max(t.k0 + (c & 1), 0), P.Z - 1);
-              koff[c] = (int64_t)i * sX + (int64_t)j * sY + (int64_t)kk * sZ;
-            }
-            const float* __restrict__ grow = grad_feat + (o3 + rank) * (int64_t)C;
-            if (VEC == 4) {
-              for (int c = 0; c < C; c += 4) {
-                float4 fv[8];
-#pragma unroll
-                for (int q = 0; q < 8; ++q) fv[q] = *reinterpret_cast<const float4*>(k0 + koff[q] + c);
-                const float4 g = *reinterpret_cast<const float4*>(grow + c);
-                __builtin_amdgcn_sched_barrier(0);
-                DVGO_XYZ_CHANNEL(fv[n].x, g.x);
-                DVGO_XYZ_CHANNEL(fv[n].y, g.y);
-                DVGO_XYZ_CHANNEL(fv[n].z, g.z);
-                DVGO_XYZ_CHANNEL(fv[n].w, g.w);
-              }
-            } else {
-              for (int c = 0; c < C; ++c) {
-                float fv[8];
-#pragma unroll
-                for (int q = 0; q < 8; ++q) fv[q] = k0[c * sC + koff[q]];
-                const float g = grow[c];
-                DVGO_XYZ_CHANNEL(fv[n], g);
-              }
-            }
-          }
-          gx = ax * scale_x; gy = ay * scale_y; gz = az * scale_z;
-          lam = R.tmin + dist / R.rnorm;
-        }
-      }
-      Ax += wave_sum(gx); Ay += wave_sum(gy); Az += wave_sum(gz);
-      Bx += wave_sum(lam * gx); By += wave_sum(lam * gy); Bz += wave_sum(lam * gz);
-    }
-  }
-  if (lane == 0) {
-    grad_o[3 * ray] = Ax; grad_o[3 * ray + 1] = Ay; grad_o[3 * ray + 2] = Az;
-    grad_d[3 * ray] = Bx; grad_d[3 * ray + 1] = By; grad_d[3 * ray + 2] = Bz;
-  }
-}
-
 static MarchParams make_params(const float* mn, const float* mx, float stepdist, const float* sc,
                                const float* sh, int mX, int mY, int mZ, int X, int Y, int Z,
                                float act_shift, float interval, float thres) {
@@ -1235,39 +1104,6 @@ int dvgo_march_density_bwd(const dvgo_rec2_t* rec2, const int32_t* n2, const int
     march_density_bwd_kernel<false><<<dvgo_blocks(n_rays * 64, DVGO_BLOCK), DVGO_BLOCK, 0, (hipStream_t)stream>>>(
         rec2, n2, n_steps, n_steps_cumsum, rec_stride, off3, n_rays, rays_start, rays_dir, P, alphainv_last,
         grad_weights, grad_last, grad_density, grad_stride, grad_kept, brick_cursor, (int4*)brick_recs);
-  DVGO_LAUNCH_CHECK();
-  return 0;
-}
-
-int dvgo_march_ray_bwd(const dvgo_rec2_t* rec2, const int32_t* n2, const int64_t* n_steps,
-                       const int64_t* n_steps_cumsum, int64_t rec_stride, const int64_t* off3, int64_t n_rays,
-                       const float* rays_start, const float* rays_dir, float stepdist,
-                       const float* xyz_min, const float* xyz_max, const float* alphainv_last, float interval,
-                       const float* rays_o, const float* rays_d, float near, float far,
-                       const float* density, int X, int Y, int Z,
-                       const float* k0, int C, int64_t sC, int64_t sX, int64_t sY, int64_t sZ,
-                       const float* grad_weights, const float* grad_last, const float* grad_feat,
-                       float* grad_o, float* grad_d, void* stream) {
-  if (n_rays < 0 || C < 0 || X <= 0 || Y <= 0 || Z <= 0 || !(stepdist > 0.0f)) return DVGO_EINVAL;   // NDC spacing is not differentiated
-  if (n_rays == 0) return 0;
-  if (!rec2 || !n2 || !n_steps || !off3 || !rays_start || !rays_dir || !xyz_min || !xyz_max || !alphainv_last ||
-      !rays_o || !rays_d || !density || !grad_o || !grad_d)
-    return DVGO_EINVAL;       // grad_weights may be NULL when M3 == 0 (it is only read for flagged samples)
-  if (grad_feat && C > 0 && !k0) return DVGO_EINVAL;
-  if (!n_steps_cumsum && rec_stride <= 0) return DVGO_EINVAL;
-  if (!dvgo_fits(n_rays * 64)) return DVGO_ERANGE;
-  const MarchParams P = make_params(xyz_min, xyz_max, stepdist, nullptr, nullptr, 0, 0, 0, X, Y, Z, 0.f, interval, 0.f);
-  const bool vec = (sC == 1) && (C % 4 == 0) && (sX % 4 == 0) && (sY % 4 == 0) && (sZ % 4 == 0) &&
-                   ((((uintptr_t)k0) & 15) == 0) && ((((uintptr_t)grad_feat) & 15) == 0);
-  const int blocks = dvgo_blocks(n_rays * 64, DVGO_BLOCK);
-  if (vec)
-    march_ray_bwd_kernel<4><<<blocks, DVGO_BLOCK, 0, (hipStream_t)stream>>>(
-        rec2, n2, n_steps, n_steps_cumsum, rec_stride, off3, n_rays, rays_start, rays_dir, P, alphainv_last, rays_o, rays_d,
-        near, far, density, k0, C, sC, sX, sY, sZ, grad_weights, grad_last, grad_feat, grad_o, grad_d);
-  else
-    march_ray_bwd_kernel<1><<<blocks, DVGO_BLOCK, 0, (hipStream_t)stream>>>(
-        rec2, n2, n_steps, n_steps_cumsum, rec_stride, off3, n_rays, rays_start, rays_dir, P, alphainv_last, rays_o, rays_d,
-        near, far, density, k0, C, sC, sX, sY, sZ, grad_weights, grad_last, grad_feat, grad_o, grad_d);
   DVGO_LAUNCH_CHECK();
   return 0;
 }

@@ -1,6 +1,6 @@
 // What the fused marches share (march.hip: the dense grid; march_vm.hip: the decomposed density; march_contract.hip: the
-// contracted space), each piece stated once so that the three form the same bits by construction: the lane mask and the
-// suffix sum; forward, the activation (e and alpha), the plain transmittance walk and the commit of a chunk into
+// contracted space; march_raygrad.hip and contract_raygrad.hip: their ray gradients), each piece stated once so that all
+// form the same bits by construction: the lane mask, the wave sum, the suffix sum and where a ray's records start; forward, the activation (e and alpha), the plain transmittance walk and the commit of a chunk into
 // the ray's rec2 records; backward, one chunk of the walk over those records from the far end, and on top of it the walk
 // that leaves one raw-density gradient and one position per record and scatters nothing.  The occupancy lookup is
 // common.h's dvgo_mask_index.  Everything here must be called by all 64 lanes.
@@ -9,6 +9,21 @@
 
 __device__ __forceinline__ unsigned long long lanemask_lt(int lane) {
   return (lane == 0) ? 0ull : (~0ull >> (64 - lane));
+}
+
+// the sum of v over the 64 lanes, in every lane: a butterfly, so the order is fixed
+__device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
+  return v;
+}
+
+// Scratch records of ray r start at cum[r]-n_steps[r] (exact, ray-major M0 layout) when the
+// inclusive cumsum is given, else at r*rec_stride (fixed stride = an upper bound of n_steps,
+// which saves the scan and the host read of M0).
+__device__ __forceinline__ int64_t rec_base(const int64_t* __restrict__ cum, const int64_t* __restrict__ n_steps,
+                                            int64_t rec_stride, int64_t ray) {
+  return cum ? (cum[ray] - n_steps[ray]) : ray * rec_stride;
 }
 
 // exclusive suffix sum across the wave: sum of v over lanes > lane

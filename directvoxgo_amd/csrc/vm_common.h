@@ -1,6 +1,7 @@
 // What the vector-matrix translation units share (vm.hip: the [M, 3R] feature sampler; vm_density.hip: the sampler
 // that sums the 3R products on chip; march_vm.hip: the ray march over that sum, which uses the line descriptor and value,
-// the pack of the line scalars and the vector-load predicate).  Device: the line descriptor, the line value, the node-sum flush, one lane's walk of
+// the pack of the line scalars and the vector-load predicate; vm_xyz.hip and march_raygrad.hip: the position derivative).
+// Device: the line descriptor, the line value, the position derivative of planes times lines, the node-sum flush, one lane's walk of
 // the gradient scatter and the scatter's kernel body (lane decode, the LDS table of mode 2).  Host: the pack of the 12 line
 // scalars of an entry point, the vector-load predicate, the argument check and the launch shape of the scatter.
 // include/dvgo_hip.h (the VM block) states the arithmetic.
@@ -66,6 +67,79 @@ __device__ __forceinline__ float vm_blend(const VmNodes<VEC>& k, int i, float w0
   l = k.ok0 ? fmaf(k.v0.v[i], w0, l) : l;
   l = k.ok1 ? fmaf(k.v1.v[i], w1, l) : l;
   return l;
+}
+
+// The incoming gradient of vm_xyz below, of components c .. c + VEC - 1 of plane s: `load` is issued with the group's
+// gathers, ahead of the scheduling barrier, and `at` reads component c + i after it.
+struct VmGradScalar {            // one gradient for all 3R products (the density: vm_xyz.hip, march_raygrad.hip)
+  float g;
+  struct Piece {};
+  template <int VEC> __device__ __forceinline__ Piece load(int, int) const { return Piece{}; }
+  __device__ __forceinline__ float at(const Piece&, int) const { return g; }
+};
+
+struct VmGradRow {               // the sample's row of grad_out [M, 3R] (the features: vm_xyz.hip)
+  const float* __restrict__ row;
+  int R;
+  template <int VEC> __device__ __forceinline__ TpVal<VEC> load(int s, int c) const { return tp_load<VEC>(row + (int64_t)s * R + c, 1); }
+  template <int VEC> __device__ __forceinline__ float at(const TpVal<VEC>& p, int i) const { return p.v[i]; }
+};
+
+// The position derivative of sum_{s,r} g_{s,r} * plane_{s,r}(p) * line_{s,r}(p) at p = (p[0], p[1], p[2]) in the box
+// (mn, mx), added to (ox, oy, oz): per product g * l * (dp/dh, dp/dw) along the plane's two axes + g * p * dl/dn along the
+// line's.  The cell, the node and the weights are the forward's (tp_setup, tp_axis on dvgo_src_index), and so are p and l
+// (tp_blend, vm_blend on the corners and nodes of tp_gather, vm_gather); a corner or node the forward drops is dropped.
+// Planes s = xy, yz, zx in turn, within a plane the components upwards, VEC at a time: the order of every sum.
+template <int VEC, class Grad>
+__device__ __forceinline__ void vm_xyz(const TpPlane& PA, const TpPlane& PB, const TpPlane& PC, const VmLine& LA, const VmLine& LB,
+                                       const VmLine& LC, int R, const float (&p)[3], const float (&mn)[3], const float (&mx)[3],
+                                       const Grad& grad, float& ox, float& oy, float& oz) {
+#pragma unroll
+  for (int s = 0; s < 3; ++s) {
+    int ah, aw, al;
+    const TpPlane q = tp_pick(PA, PB, PC, s, ah, aw);
+    const VmLine ln = vm_pick(LA, LB, LC, s, al);
+    const BiSetup b = tp_setup(p[ah], p[aw], mn[ah], mx[ah], mn[aw], mx[aw], q.H, q.W);
+    int n0;
+    float w0, w1;
+    tp_axis(dvgo_src_index(p[al], mn[al], mx[al], ln.N), n0, w0, w1);
+    const float k00 = b.wh0 * b.ww0, k01 = b.wh0 * b.ww1, k10 = b.wh1 * b.ww0, k11 = b.wh1 * b.ww1;
+    float Ah = 0.f, Aw = 0.f, An = 0.f;
+    for (int c = 0; c < R; c += VEC) {
+      const VmNodes<VEC> nd = vm_gather<VEC>(ln, c, n0);
+      const TpCorners<VEC> k = tp_gather<VEC>(q, b, c);
+      const auto gv = grad.template load<VEC>(s, c);
+      // hipcc otherwise sinks each load to its first use (one round trip per corner); nothing crosses this
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int i = 0; i < VEC; ++i) {
+        const float l = vm_blend<VEC>(nd, i, w0, w1);
+        const float pv = tp_blend<VEC>(k, i, k00, k01, k10, k11);
+        float dh = 0.f, dw = 0.f;
+        dh = (k.okh0 & k.okw0) ? fmaf(k.v00.v[i], -b.ww0, dh) : dh;
+        dh = (k.okh0 & k.okw1) ? fmaf(k.v01.v[i], -b.ww1, dh) : dh;
+        dh = (k.okh1 & k.okw0) ? fmaf(k.v10.v[i], b.ww0, dh) : dh;
+        dh = (k.okh1 & k.okw1) ? fmaf(k.v11.v[i], b.ww1, dh) : dh;
+        dw = (k.okh0 & k.okw0) ? fmaf(k.v00.v[i], -b.wh0, dw) : dw;
+        dw = (k.okh0 & k.okw1) ? fmaf(k.v01.v[i], b.wh0, dw) : dw;
+        dw = (k.okh1 & k.okw0) ? fmaf(k.v10.v[i], -b.wh1, dw) : dw;
+        dw = (k.okh1 & k.okw1) ? fmaf(k.v11.v[i], b.wh1, dw) : dw;
+        const float dn = (nd.ok1 ? nd.v1.v[i] : 0.f) - (nd.ok0 ? nd.v0.v[i] : 0.f);
+        const float gi = grad.at(gv, i);
+        const float t = gi * l, u = gi * pv;
+        Ah = fmaf(t, dh, Ah);
+        Aw = fmaf(t, dw, Aw);
+        An = fmaf(u, dn, An);
+      }
+    }
+    // the plane's scale once, after its last component; (ah, aw, al) is a permutation of the world axes
+    const float th = Ah * ((float)(q.H - 1) / (mx[ah] - mn[ah]));
+    const float tw = Aw * ((float)(q.W - 1) / (mx[aw] - mn[aw]));
+    const float tn = An * ((float)(ln.N - 1) / (mx[al] - mn[al]));
+    ox = ox + ((ah == 0) ? th : (aw == 0) ? tw : tn);
+    oy = oy + ((ah == 1) ? th : (aw == 1) ? tw : tn);
+    oz = oz + ((ah == 2) ? th : (aw == 2) ? tw : tn);
+  }
 }
 
 // VEC components from c on of line q in the interval (n0, n0 + 1) with the weights (w0, w1)

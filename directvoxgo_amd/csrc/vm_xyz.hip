@@ -5,7 +5,8 @@
 // block) states the arithmetic.
 //
 // One kernel body, two entries: the incoming gradient of component (s, r) is grad_out[m, sR + r] for the features and
-// grad_out[m] for the density.  Both are sums over the 3R products of
+// grad_out[m] for the density.  The derivative itself is vm_common.h's vm_xyz, which march_raygrad.hip's VM kernel calls per
+// record of a ray; what follows describes it as this unit runs it.  Both are sums over the 3R products of
 //     g * d(p * l)/dxyz = g * l * (dp/dh, dp/dw) along the plane's two axes  +  g * p * dl/dn along the line's axis.
 //
 // One lane per sample, as in vmd_fwd_kernel and hash_xyz.hip: the lane walks s = xy, yz, zx and, within a plane, the
@@ -49,55 +50,12 @@ vm_bwd_xyz_kernel(TpPlane PA, TpPlane PB, TpPlane PC, VmLine LA, VmLine LB, VmLi
       return;
     }
   }
-#pragma unroll
-  for (int s = 0; s < 3; ++s) {
-    int ah, aw, al;
-    const TpPlane q = tp_pick(PA, PB, PC, s, ah, aw);
-    const VmLine ln = vm_pick(LA, LB, LC, s, al);
-    const BiSetup b = tp_setup(xyz, mn, mx, m, ah, aw, q.H, q.W);
-    int n0;
-    float w0, w1;
-    tp_axis(dvgo_src_index(xyz[3 * m + al], mn[al], mx[al], ln.N), n0, w0, w1);
-    const float k00 = b.wh0 * b.ww0, k01 = b.wh0 * b.ww1, k10 = b.wh1 * b.ww0, k11 = b.wh1 * b.ww1;
-    const float* g = nullptr;
-    if constexpr (PER_COMP) g = grad_out + m * (3 * (int64_t)R) + (int64_t)s * R;
-    float Ah = 0.f, Aw = 0.f, An = 0.f;
-    for (int c = 0; c < R; c += VEC) {
-      const VmNodes<VEC> nd = vm_gather<VEC>(ln, c, n0);
-      const TpCorners<VEC> k = tp_gather<VEC>(q, b, c);
-      TpVal<VEC> gv;
-      if constexpr (PER_COMP) gv = tp_load<VEC>(g + c, 1);
-      // hipcc otherwise sinks each load to its first use (one round trip per corner); nothing crosses this
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int i = 0; i < VEC; ++i) {
-        const float l = vm_blend<VEC>(nd, i, w0, w1);
-        const float p = tp_blend<VEC>(k, i, k00, k01, k10, k11);
-        float dh = 0.f, dw = 0.f;
-        dh = (k.okh0 & k.okw0) ? fmaf(k.v00.v[i], -b.ww0, dh) : dh;
-        dh = (k.okh0 & k.okw1) ? fmaf(k.v01.v[i], -b.ww1, dh) : dh;
-        dh = (k.okh1 & k.okw0) ? fmaf(k.v10.v[i], b.ww0, dh) : dh;
-        dh = (k.okh1 & k.okw1) ? fmaf(k.v11.v[i], b.ww1, dh) : dh;
-        dw = (k.okh0 & k.okw0) ? fmaf(k.v00.v[i], -b.wh0, dw) : dw;
-        dw = (k.okh0 & k.okw1) ? fmaf(k.v01.v[i], b.wh0, dw) : dw;
-        dw = (k.okh1 & k.okw0) ? fmaf(k.v10.v[i], -b.wh1, dw) : dw;
-        dw = (k.okh1 & k.okw1) ? fmaf(k.v11.v[i], b.wh1, dw) : dw;
-        const float dn = (nd.ok1 ? nd.v1.v[i] : 0.f) - (nd.ok0 ? nd.v0.v[i] : 0.f);
-        const float gi = PER_COMP ? gv.v[i] : gd;
-        const float t = gi * l, u = gi * p;
-        Ah = fmaf(t, dh, Ah);
-        Aw = fmaf(t, dw, Aw);
-        An = fmaf(u, dn, An);
-      }
-    }
-    // the plane's scale once, after its last component; (ah, aw, al) is a permutation of the world axes
-    const float th = Ah * ((float)(q.H - 1) / (mx[ah] - mn[ah]));
-    const float tw = Aw * ((float)(q.W - 1) / (mx[aw] - mn[aw]));
-    const float tn = An * ((float)(ln.N - 1) / (mx[al] - mn[al]));
-    ox = ox + ((ah == 0) ? th : (aw == 0) ? tw : tn);
-    oy = oy + ((ah == 1) ? th : (aw == 1) ? tw : tn);
-    oz = oz + ((ah == 2) ? th : (aw == 2) ? tw : tn);
-  }
+  const float p[3] = {xyz[3 * m], xyz[3 * m + 1], xyz[3 * m + 2]};
+  const float lo[3] = {mn[0], mn[1], mn[2]}, hi[3] = {mx[0], mx[1], mx[2]};
+  if constexpr (PER_COMP)
+    vm_xyz<VEC>(PA, PB, PC, LA, LB, LC, R, p, lo, hi, VmGradRow{grad_out + m * (3 * (int64_t)R), R}, ox, oy, oz);
+  else
+    vm_xyz<VEC>(PA, PB, PC, LA, LB, LC, R, p, lo, hi, VmGradScalar{gd}, ox, oy, oz);
   grad_xyz[3 * m + 0] = ox;
   grad_xyz[3 * m + 1] = oy;
   grad_xyz[3 * m + 2] = oz;

@@ -1,5 +1,5 @@
 // The corner table of the trilinear sample's POSITION derivative, shared by grid_sample_xyz.hip (one lane per sample) and
-// march.hip's ray-gradient kernel (one lane per record of a ray): signed two-weight products, clamped offsets, in-range
+// march_raygrad.hip's dense kernels (one lane per record of a ray): signed two-weight products, clamped offsets, in-range
 // flags, and the per-channel corner chains.  include/dvgo_hip.h (dvgo_grid_sample_bwd_xyz) states the arithmetic.
 #pragma once
 #include "common.h"

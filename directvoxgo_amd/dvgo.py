@@ -12,7 +12,7 @@ Two execution paths produce the same dict:
                render_utils.py / ops.py (what a maintainer gets by only swapping the bindings).
 Rays that require grad (camera-pose refinement, pose.py) take a third, op-by-op path that is also differentiable with respect
 to the rays: `_forward_raygrad`; with the class switch `fused_raygrad` set (pose.refine_poses(fused=True) sets it for its
-loop) they stay on the fused march, whose backward then also returns the ray gradients (csrc/march.hip: march_ray_bwd).
+loop) they stay on the fused march, whose backward then also returns the ray gradients (csrc/march_raygrad.hip: march_ray_bwd).
 `posbase_pe=P > 0` (lib/dvgo.py:97-107,528-534, the switch of configs/nerf and configs/nsvf) colours a sample from
 the positional encoding of its position instead of the feature grid: the colour head's input is
 cat([pts, sin(pts (x) posfreq), cos(pts (x) posfreq), viewdirs_emb]), there is no diffuse term, and k0 -- still allocated,

@@ -23,7 +23,7 @@ needs five.
                      position gradient and csrc/contract_raygrad.hip (camera-pose refinement of unbounded scenes).
 
 `fused_march(..., positions=True, raygrad=True)` and `fused_march_vm(..., raygrad=True)` differentiate their rays as well
-(csrc/march_pts_raygrad.hip: dvgo_march_ray_bwd_pts, dvgo_march_vm_ray_bwd, one wavefront per ray over the march's own
+(csrc/march_raygrad.hip: dvgo_march_ray_bwd_pts, dvgo_march_vm_ray_bwd, one wavefront per ray over the march's own
 records): the returned positions are differentiable, and the backward's first launch sums, per ray, the density's share
 of every record and the gradient that arrived for the positions.  The defaults refuse such rays, as before.
 """
@@ -33,7 +33,8 @@ import torch
 
 from . import _lib as L
 from ._lib import check_f32, check_input, f3, stream_of
-from .ops import _grid_geom
+from .ops import _grid_geom, _kernel_tensors, _plane_list, _vm_geom, _vm_grad_buffers, vm_density_bwd
+from .shade import march_positions          # (shade.py imports nothing of this module: no cycle to break)
 
 # scratch budget for fixed-stride records (16 B per potential sample)
 _MAX_STRIDE_SCRATCH_BYTES = 4 << 30
@@ -325,7 +326,6 @@ class _FusedMarch(torch.autograd.Function):
             L.call('dvgo_march_gather', rec2, n2, n_steps, cum, stride, off3, N, M3, start, dirs, cfg.stepdist, cfg.xyz_min_h,
                    cfg.xyz_max_h, k0, C, X, Y, Z, sC, sX, sY, sZ, ray_id, step_id, weights, alpha, feat, st)
             if positions:              # the kept samples' positions in place of the (zero-channel) features
-                from .shade import march_positions
                 feat = march_positions(start, dirs, ray_id, step_id, cfg.stepdist)
         ctx.cfg = cfg
         ctx.geom = (X, Y, Z, C, sC, sX, sY, sZ, stride, N)
@@ -359,26 +359,20 @@ class _FusedMarch(torch.autograd.Function):
                 gw = g_w.contiguous() if g_w is not None else torch.zeros(M3, dtype=torch.float32, device=dev)
                 gl = g_last.contiguous() if g_last is not None else None
             rays = (None, None)
-            if ctx.ray_grad:
+            if ctx.ray_grad or ctx.pts_grad:
                 # FIRST, before any other launch of this backward: the brick scatter below may apply the optimizer's
                 # update to both grids in place (grid_rows_capture.adam), and this kernel must read the grids the
                 # forward read.  Same stream, so launch order is execution order.
                 rays_o, rays_d = ctx.saved_tensors[10:]
                 go = torch.empty((N, 3), dtype=torch.float32, device=dev)
                 gd = torch.empty((N, 3), dtype=torch.float32, device=dev)
-                L.call('dvgo_march_ray_bwd', rec2, n2, n_steps, cum if stride == 0 else None, stride, off3, N, start, dirs,
+                if ctx.ray_grad:       # the k0 grid and the gradient of its features
+                    entry, colour, g_rows = 'dvgo_march_ray_bwd', (ctx.k0_meta, C, sC, sX, sY, sZ), g_feat if C > 0 else None
+                else:                  # `g_feat` is the gradient that arrived for the positions (None: none did)
+                    entry, colour, g_rows = 'dvgo_march_ray_bwd_pts', (), g_feat
+                L.call(entry, rec2, n2, n_steps, cum if stride == 0 else None, stride, off3, N, start, dirs,
                        cfg.stepdist, cfg.xyz_min_h, cfg.xyz_max_h, last, cfg.interval, rays_o, rays_d, cfg.near, cfg.far,
-                       ctx.density_meta, X, Y, Z, ctx.k0_meta, C, sC, sX, sY, sZ, gw, gl,
-                       g_feat.contiguous() if (g_feat is not None and C > 0) else None, go, gd, st)
-                rays = (go if ctx.needs_input_grad[2] else None, gd if ctx.needs_input_grad[3] else None)
-            elif ctx.pts_grad:
-                # the same rule: first.  `g_feat` is the gradient that arrived for the positions (None: none did)
-                rays_o, rays_d = ctx.saved_tensors[10:]
-                go = torch.empty((N, 3), dtype=torch.float32, device=dev)
-                gd = torch.empty((N, 3), dtype=torch.float32, device=dev)
-                L.call('dvgo_march_ray_bwd_pts', rec2, n2, n_steps, cum if stride == 0 else None, stride, off3, N, start, dirs,
-                       cfg.stepdist, cfg.xyz_min_h, cfg.xyz_max_h, last, cfg.interval, rays_o, rays_d, cfg.near, cfg.far,
-                       ctx.density_meta, X, Y, Z, gw, gl, g_feat.contiguous() if g_feat is not None else None, go, gd, st)
+                       ctx.density_meta, X, Y, Z, *colour, gw, gl, g_rows.contiguous() if g_rows is not None else None, go, gd, st)
                 rays = (go if ctx.needs_input_grad[2] else None, gd if ctx.needs_input_grad[3] else None)
 
             def density_bwd(dst, dst_stride, kept, cursor=None, recs=None):
@@ -504,10 +498,10 @@ def fused_march(density, k0, rays_o, rays_d, cfg, capacity=False, positions=Fals
     first off3[N] rows are defined (pass `off3[N:]` as `m_dev` to the consumers).
     `positions=True` (positional-encoding colour head): k0 must have zero channels (nothing is read from it) and the
     fourth output is the kept samples' positions [M3,3] instead of the features, with no gradient.
-    `rays_o` / `rays_d` that require grad get one (csrc/march.hip: march_ray_bwd, launched first in the backward; the
+    `rays_o` / `rays_d` that require grad get one (csrc/march_raygrad.hip: march_ray_bwd, launched first in the backward; the
     stop-gradients are DirectVoxGO._forward_raygrad's); with `positions=True` or NDC sampling that is a NotImplementedError.
     `positions=True, raygrad=True` (HashVoxGO, VMTriPlaneVoxGO with raygrad='fused'): the same launches and the same bits, the
-    returned positions are differentiable, and the backward launches dvgo_march_ray_bwd_pts first (csrc/march_pts_raygrad.hip:
+    returned positions are differentiable, and the backward launches dvgo_march_ray_bwd_pts first (csrc/march_raygrad.hip:
     the density's share per record plus the gradient that arrived for the positions, summed per ray with the same
     stop-gradients).  NDC sampling stays refused."""
     if torch.is_grad_enabled() and (rays_o.requires_grad or rays_d.requires_grad) and (
@@ -554,20 +548,13 @@ class _FusedMarchVM(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, rays_o, rays_d, cfg, stride, raygrad, *tensors):
-        from .ops import PLANE_KEYS, _kernel_tensors, _line_geom, _plane_pack
-        from .shade import march_positions
         for x, n in ((rays_o, 'rays_o'), (rays_d, 'rays_d')):
             check_input(x, n); check_f32(x, n)
         dev = rays_o.device
         N = rays_o.shape[0]
         cap = stride * N
         kt = _kernel_tensors(ctx, list(tensors), cap)        # the rule looks at the three planes; cap: the steps a launch may take
-        R = kt[0].shape[1]
-        if any(t.dim() != 4 or t.shape[1] != R for t in kt):
-            raise RuntimeError('the three planes [1,R,H,W] and the three lines [1,R,N,1] must share their component count')
-        g = _plane_pack(kt[:3])
-        for ln, k in zip(kt[3:], PLANE_KEYS):
-            g += [ln, *_line_geom(ln, k + '_line')]
+        g, R = _vm_geom(kt)
         st = stream_of(rays_o)
         n_steps = torch.empty(N, dtype=torch.int64, device=dev)
         start = torch.empty((N, 3), dtype=torch.float32, device=dev)
@@ -582,10 +569,8 @@ class _FusedMarchVM(torch.autograd.Function):
         mshape = mask.shape if mask is not None else (0, 0, 0)
         with L.device_of(rays_o):
             L.call('dvgo_march_vm_density', start, dirs, n_steps, stride, N, cfg.xyz_min_h, cfg.xyz_max_h, cfg.stepdist, mask,
-                   mshape[0], mshape[1], mshape[2], cfg.scale_h, cfg.shift_h, g[0], g[1], g[2], g[3], g[4], g[5], g[6], g[7],
-                   g[8], g[9], g[10], g[11], g[12], g[13], g[14], g[15], g[16], g[17], g[18], g[19], g[20], g[21], g[22], g[23],
-                   g[24], g[25], g[26], g[27], g[28], g[29], R, cfg.act_shift, cfg.interval, cfg.thres, rec2, n2, n3, last,
-                   rays_o, rays_d, cfg.near, cfg.far, st)
+                   mshape[0], mshape[1], mshape[2], cfg.scale_h, cfg.shift_h, *g, R, cfg.act_shift, cfg.interval, cfg.thres,
+                   rec2, n2, n3, last, rays_o, rays_d, cfg.near, cfg.far, st)
             M3, M2, ray_id, step_id, weights, alpha = _records_to_samples(rec2, n2, n3, off3, off2, N, stride, cfg, st, start,
                                                                           dirs, cfg.stepdist, n_steps=n_steps)
             pts = march_positions(start, dirs, ray_id, step_id, cfg.stepdist)
@@ -601,7 +586,6 @@ class _FusedMarchVM(torch.autograd.Function):
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, g_w, _g_alpha, g_last, g_pts, _g_rid, _g_sid, _g_off):
-        from .ops import _vm_grad_buffers, vm_density_bwd
         rec2, n2, n_steps, off3, off2, start, dirs, last, *kt = ctx.saved_tensors[:14]
         stride, N, M2, M3 = ctx.counts
         cfg = ctx.cfg
@@ -613,19 +597,14 @@ class _FusedMarchVM(torch.autograd.Function):
         if ctx.ray_grad:
             # FIRST (the rule of _FusedMarch.backward), and also when the model is frozen: the kernel does its own walk over
             # the records and reads the planes and lines the forward read
-            from .ops import PLANE_KEYS, _line_geom, _plane_pack
             rays_o, rays_d = ctx.saved_tensors[14:]
-            g = _plane_pack(kt[:3])
-            for ln, k in zip(kt[3:], PLANE_KEYS):
-                g += [ln, *_line_geom(ln, k + '_line')]
+            g, R = _vm_geom(kt)
             go = torch.empty((N, 3), dtype=torch.float32, device=dev)
             gd = torch.empty((N, 3), dtype=torch.float32, device=dev)
             gw = g_w.contiguous() if g_w is not None else torch.zeros(M3, dtype=torch.float32, device=dev)
             with L.device_of(start):
                 L.call('dvgo_march_vm_ray_bwd', rec2, n2, stride, off3, N, start, dirs, cfg.stepdist, cfg.xyz_min_h, cfg.xyz_max_h,
-                       last, cfg.interval, rays_o, rays_d, cfg.near, cfg.far, g[0], g[1], g[2], g[3], g[4], g[5], g[6], g[7], g[8],
-                       g[9], g[10], g[11], g[12], g[13], g[14], g[15], g[16], g[17], g[18], g[19], g[20], g[21], g[22], g[23], g[24],
-                       g[25], g[26], g[27], g[28], g[29], kt[0].shape[1], gw,
+                       last, cfg.interval, rays_o, rays_d, cfg.near, cfg.far, *g, R, gw,
                        g_last.contiguous() if g_last is not None else None,
                        g_pts.contiguous() if g_pts is not None else None, go, gd, stream_of(start))
             go, gd = (go if ctx.needs_input_grad[0] else None), (gd if ctx.needs_input_grad[1] else None)
@@ -649,10 +628,9 @@ def fused_march_vm(density_planes, density_lines, rays_o, rays_d, cfg, raygrad=F
     Returns None when no fixed record stride exists for `cfg` (`_rec_stride`: an infinite `far`, or scratch over the
     budget): the caller then takes its op-by-op path.  NDC sampling and rays that require grad are refused, the latter unless
     `raygrad=True`: then the forward is the same launches and the same bits, the returned positions are differentiable, and
-    the backward launches dvgo_march_vm_ray_bwd first (csrc/march_pts_raygrad.hip: per record the raw-density gradient through
+    the backward launches dvgo_march_vm_ray_bwd first (csrc/march_raygrad.hip: per record the raw-density gradient through
     the position derivative of planes times lines, plus the gradient that arrived for the positions, summed per ray; it
     runs also when none of the six tensors takes a gradient).  The stop-gradients are DirectVoxGO._forward_raygrad's."""
-    from .ops import _plane_list
     if cfg.ndc_samples > 0:
         raise NotImplementedError('fused_march_vm: NDC sampling is not built for the decomposed density')
     if not raygrad and torch.is_grad_enabled() and (rays_o.requires_grad or rays_d.requires_grad):

@@ -289,15 +289,24 @@ def _line_geom(line, name):
     return line.shape[2], line.stride(1), line.stride(2)
 
 
-def _vm_args(planes, lines, xyz):
-    """-> (planes, lines, the 27 geometry scalars interleaved with their tensors in call order, R, M)"""
-    planes, lines = _plane_list(planes), _plane_list(lines)
+def _vm_geom(tensors):
+    """The three planes, then the three lines, of a VM kernel -> (its 30 plane-and-line arguments: each tensor followed by
+    its geometry scalars, in call order; R)"""
+    planes, lines = list(tensors[:3]), list(tensors[3:])
     R = planes[0].shape[1]
     if any(t.dim() != 4 or t.shape[1] != R for t in planes + lines):
         raise RuntimeError('the three planes [1,R,H,W] and the three lines [1,R,N,1] must share their component count')
     geom = _plane_pack(planes)
     for ln, k in zip(lines, PLANE_KEYS):
         geom += [ln, *_line_geom(ln, k + '_line')]
+    assert len(geom) == 30              # (callers splat it into launches whose other arguments tests/test_abi.py counts)
+    return geom, R
+
+
+def _vm_args(planes, lines, xyz):
+    """-> (planes, lines, `_vm_geom`'s argument list, R, M)"""
+    planes, lines = _plane_list(planes), _plane_list(lines)
+    geom, R = _vm_geom(planes + lines)
     check_input(xyz, 'xyz'); check_f32(xyz, 'xyz')
     if xyz.dim() != 2 or xyz.shape[1] != 3:
         raise RuntimeError('xyz must be [M,3]')

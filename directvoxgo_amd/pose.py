@@ -7,7 +7,7 @@ hold.  This module makes the poses learnable: `CameraRefiner` holds one se(3) co
 rays that are differentiable in it, `DirectVoxGO.forward` renders such rays with gradients flowing back through the sample
 positions (ops.ray_points, ops.grid_sample's position gradient: csrc/grid_sample_xyz.hip), and `refine_poses` is the
 eager optimisation loop -- poses alone against a trained model (registration of new images included), or poses and model
-together.  `refine_poses(..., fused=True)` keeps the render on the fused march (csrc/march.hip: march_ray_bwd returns the
+together.  `refine_poses(..., fused=True)` keeps the render on the fused march (csrc/march_raygrad.hip: march_ray_bwd returns the
 ray gradients from the march's own backward) and, with `train_model`, steps the model by a train.TrainStep: the brick
 scatter with the Adam update inside it, as in any other training step.  For the contracted model the positions are the
 contraction of their rays (ops.contract_points; csrc/contract_raygrad.hip applies the contraction's Jacobian and sums per
@@ -16,7 +16,7 @@ hashed gather's own position derivative (ops.hash_sample(position_grad=True); cs
 For the two vector-matrix models it comes from the position derivative of planes times lines (ops.vm_sample and, for
 TensoRFVoxGO's density, ops.vm_density with position_grad=True; csrc/vm_xyz.hip), on the op-by-op path as well.  Constructed
 with raygrad='fused', those three models keep such rays on their fused march: the march's own ray backward
-(csrc/march_pts_raygrad.hip) sums, per ray, the density's share of every record and the gradient the samplers returned for the
+(csrc/march_raygrad.hip) sums, per ray, the density's share of every record and the gradient the samplers returned for the
 kept samples' positions.
 
 Pure torch: everything but `refine_poses`' model call runs on CPU tensors too.
@@ -176,7 +176,7 @@ def refine_poses(model, refiner, images, cfg_train, render_kwargs, n_iters, n_ra
     is csrc/hash_xyz.hip) whatever `model.fused` says: `fused=True` is a ValueError for it, and `train_model` steps density,
     table and head by the eager optimiser.  A `HashVoxGO(raygrad='fused')` (the instance carries `fused_raygrad`) is accepted
     with `fused=True`: the render is `fused_march(positions=True, raygrad=True)`, `delta`'s gradient comes from
-    dvgo_march_ray_bwd_pts (csrc/march_pts_raygrad.hip), and with `train_model` the model is stepped by a `train.TrainStep`.
+    dvgo_march_ray_bwd_pts (csrc/march_raygrad.hip), and with `train_model` the model is stepped by a `train.TrainStep`.
 
     A `VMTriPlaneVoxGO(raygrad=True)` and a `TensoRFVoxGO(raygrad=True)` render such rays op by op as well
     (DirectVoxGO._forward_raygrad; the position derivative of planes times lines is csrc/vm_xyz.hip, for the features and,

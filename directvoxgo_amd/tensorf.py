@@ -38,7 +38,7 @@ model only with this option.
 
 `raygrad='fused'` (the base's: `raygrad` plus the instance attribute `fused_raygrad`; `load_model(TensoRFVoxGO, path,
 raygrad='fused')`): with `fused` and `fused_march=True`, rays that require grad stay on the VM march --
-`fused_march_vm(..., raygrad=True)`, whose backward launches dvgo_march_vm_ray_bwd (csrc/march_pts_raygrad.hip) first: per
+`fused_march_vm(..., raygrad=True)`, whose backward launches dvgo_march_vm_ray_bwd (csrc/march_raygrad.hip) first: per
 record the raw-density gradient through the position derivative of planes times lines, plus what `vm_sample(...,
 position_grad=True) @ basis` returned for the positions, summed per ray; it runs with the model frozen too -- with the
 fused march's bits in every key and the same stop-gradients; `viewdirs` is detached.  Without `fused_march`, or where the

@@ -23,7 +23,7 @@ the option, are untouched by it.
 
 `raygrad='fused'` sets `raygrad` and, on the instance, `fused_raygrad` (no `get_kwargs` key either, not in checkpoints:
 `load_model(VMTriPlaneVoxGO, path, raygrad='fused')`): with `self.fused`, rays that require grad stay on the fused march --
-`fused_march(positions=True, raygrad=True)`, whose backward launches dvgo_march_ray_bwd_pts (csrc/march_pts_raygrad.hip)
+`fused_march(positions=True, raygrad=True)`, whose backward launches dvgo_march_ray_bwd_pts (csrc/march_raygrad.hip)
 first: the density's share of every record plus what `vm_sample(..., position_grad=True)` returned for the positions, summed
 per ray -- with the fused forward's bits in every key and the same stop-gradients; `viewdirs` is detached.  With
 `fused=False` such rays take `_forward_raygrad` as before.  `pose.refine_poses(fused=True)` accepts the model only with it.

@@ -301,7 +301,7 @@ int dvgo_march_density_bwd(const dvgo_rec2_t* rec2, const int32_t* n2, const int
                            int32_t* brick_cursor, void* brick_recs,
                            void* stream);
 
-/* dvgo_march_ray_bwd: the gradient of the fused march with respect to its RAYS (csrc/march.hip; DESIGN.md section 6h;
+/* dvgo_march_ray_bwd: the gradient of the fused march with respect to its RAYS (csrc/march_raygrad.hip; DESIGN.md section 6h;
  *   camera-pose refinement on the fused path).  One wavefront per ray; metric steps only
  *   (stepdist > 0: NDC spacing is not differentiated).
  *   rec2 .. alphainv_last, interval, grad_weights, grad_last: as dvgo_march_density_bwd, from the same forward.  The walk
@@ -339,7 +339,7 @@ int dvgo_march_ray_bwd(const dvgo_rec2_t* rec2, const int32_t* n2, const int64_t
                        const float* grad_feat /* [M3,C] */, float* grad_o, float* grad_d, void* stream);
 
 /* dvgo_march_ray_bwd_pts: dvgo_march_ray_bwd for a march that hands its caller the kept samples' POSITIONS in place of k0
- *   features (fused_march(positions=True): HashVoxGO, VMTriPlaneVoxGO; csrc/march_pts_raygrad.hip).
+ *   features (fused_march(positions=True): HashVoxGO, VMTriPlaneVoxGO; csrc/march_raygrad.hip).
  *   Added without a bump of DVGO_ABI_VERSION.  Every argument up to Z as in dvgo_march_ray_bwd, from the same forward; both
  *   record layouts (n_steps_cumsum, or rec_stride > 0); grad_last [N] or NULL; grad_weights may be NULL when M3 == 0.
  *   grad_pts [M3,3] row-major in the M3 order of dvgo_march_gather: the gradient that arrived for the positions, or NULL: no
@@ -1042,7 +1042,7 @@ int dvgo_march_vm_density_bwd(const dvgo_rec2_t* rec2, const int32_t* n2, const 
                               const float* grad_weights /* [M3] */, const float* grad_last /* [N] or NULL */,
                               float* g_raw /* [M2] */, float* xyz2 /* [M2,3] */, void* stream);
 
-/* dvgo_march_vm_ray_bwd: the gradient of dvgo_march_vm_density with respect to its RAYS (csrc/march_pts_raygrad.hip;
+/* dvgo_march_vm_ray_bwd: the gradient of dvgo_march_vm_density with respect to its RAYS (csrc/march_raygrad.hip;
  *   camera-pose refinement of TensoRFVoxGO on the fused march).  Added without a bump of
  *   DVGO_ABI_VERSION.  One wavefront per ray; records at r * rec_stride only, metric steps only, as that march.
  *   rec2, n2, rec_stride, off3, rays_start, rays_dir, stepdist, alphainv_last, interval, grad_weights, grad_last: as

@@ -1,4 +1,4 @@
-"""The cases of dvgo_march_ray_bwd_pts and dvgo_march_vm_ray_bwd (csrc/march_pts_raygrad.hip) that the host tests
+"""The cases of dvgo_march_ray_bwd_pts and dvgo_march_vm_ray_bwd (csrc/march_raygrad.hip) that the host tests
 (tests/test_march_pts_raygrad_host.py: on the CPU oracle's records) and the GPU tests (tests/test_gpu_march_pts_raygrad.py: on
 the device's) share: test infrastructure, CPU only, numpy.
 

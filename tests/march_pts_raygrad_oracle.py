@@ -1,4 +1,4 @@
-"""Float64 statement of `dvgo_march_ray_bwd_pts` and `dvgo_march_vm_ray_bwd` (csrc/march_pts_raygrad.hip): the ray gradient
+"""Float64 statement of `dvgo_march_ray_bwd_pts` and `dvgo_march_vm_ray_bwd` (csrc/march_raygrad.hip): the ray gradient
 of the fused marches that hand positions to their caller.  Test infrastructure, CPU only, numpy.  It adds no constant of its
 own and composes what exists:
 

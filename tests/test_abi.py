@@ -178,7 +178,8 @@ def test_call_refuses_a_wrong_argument_list_before_the_device(so_path):
 def test_every_literal_call_site_matches_the_header():
     """Static: each `call('dvgo_...', ...)` in the package names a declared function and, where its argument list has no
     `*`, passes the declared number of arguments.  fused.py may splat only the Adam group of `grid_step_args` (its length
-    is asserted where it is splatted), and neither fused.py nor masked_adam.py wraps a pointer by hand."""
+    is asserted where it is splatted) and, at the two VM launches, the 30 plane-and-line arguments of `ops._vm_geom` (their
+    number is asserted where the list is built, and the launch's other arguments are counted here), and neither fused.py nor masked_adam.py wraps a pointer by hand."""
     import ast
     decl, bad, sites, splats = _declared(), [], 0, []
     pkg = os.path.join(REPO, 'directvoxgo_amd')
@@ -197,13 +198,21 @@ def test_every_literal_call_site_matches_the_header():
             if name not in decl:
                 bad.append((fname, node.lineno, name, 'not declared'))
             elif any(isinstance(a, ast.Starred) for a in args):
-                splats.append((fname, name, [ast.unparse(a.value) for a in args if isinstance(a, ast.Starred)]))
+                starred = [ast.unparse(a.value) for a in args if isinstance(a, ast.Starred)]
+                splats.append((fname, name, starred))
                 if len(args) - 1 > decl[name][1]:
                     bad.append((fname, node.lineno, name, 'more arguments than declared'))
+                if fname == 'fused.py' and starred == ['g'] and len(args) - 1 + 30 != decl[name][1]:     # ops._vm_geom's 30
+                    bad.append((fname, node.lineno, name, len(args) - 1 + 30, decl[name][1]))
             elif len(args) != decl[name][1]:
                 bad.append((fname, node.lineno, name, len(args), decl[name][1]))
     assert not bad, bad
     assert sites >= 50                                   # (the walk found the call sites at all)
-    assert [s for s in splats if s[0] == 'fused.py'] == [('fused.py', 'dvgo_brick_accumulate', ['adam'])]
+    assert sorted(s for s in splats if s[0] == 'fused.py') == [('fused.py', 'dvgo_brick_accumulate', ['adam']),
+                                                                ('fused.py', 'dvgo_march_vm_density', ['g']),
+                                                                ('fused.py', 'dvgo_march_vm_ray_bwd', ['g'])]
+    src = open(os.path.join(pkg, 'ops.py')).read()
+    assert src.count('assert len(geom) == 30') == 1
     src = open(os.path.join(pkg, 'fused.py')).read()
+    assert src.count('g, R = _vm_geom(kt)') == 2         # `g` is that list and nothing else at both launches
     assert 'assert len(adam) == len(_NO_ADAM)' in src and re.search(r'^_NO_ADAM = \((.*)\)$', src, flags=re.M).group(1).count(',') == 13

@@ -1,4 +1,4 @@
-"""GPU: the ray gradient of the fused marches that return positions (csrc/march_pts_raygrad.hip: dvgo_march_ray_bwd_pts,
+"""GPU: the ray gradient of the fused marches that return positions (csrc/march_raygrad.hip: dvgo_march_ray_bwd_pts,
 dvgo_march_vm_ray_bwd), from the kernels to pose.refine_poses(fused=True) for HashVoxGO, VMTriPlaneVoxGO and TensoRFVoxGO.
 
   dense kernel  called on what a fused_march(positions=True, raygrad=True) forward saved, outputs pre-filled with NaN, every ray

@@ -1,4 +1,4 @@
-"""GPU: the fused march's gradient with respect to its rays (csrc/march.hip: dvgo_march_ray_bwd), from the kernel to
+"""GPU: the fused march's gradient with respect to its rays (csrc/march_raygrad.hip: dvgo_march_ray_bwd), from the kernel to
 pose.refine_poses(fused=True).
 
   kernel      called directly on what a fused_march forward saved, grad_o / grad_d pre-filled with NaN, every ray inside the

@@ -1,4 +1,4 @@
-"""The compiler's resource summary of the ray-gradient kernels of the fused march (csrc/march.hip: march_ray_bwd_kernel, both
+"""The compiler's resource summary of the ray-gradient kernels of the fused march (csrc/march_raygrad.hip: march_ray_bwd_kernel, both
 dispatch variants), compiled with the library's own flags (build.FLAGS) as tests/test_hazards_raygrad.py does for the sampler's
 position gradient: no private memory, no spilled register.  Reads the kernel descriptors' metadata only; the wait-state rules
 of the whole translation unit are tests/test_hazards.py's."""
@@ -21,9 +21,9 @@ pytestmark = pytest.mark.skipif(not os.path.exists(HIPCC), reason='needs hipcc')
 
 @pytest.fixture(scope='module')
 def meta(tmp_path_factory):
-    assert 'march.hip' in SOURCES and 'xyz_corners.h' in HEADERS
-    out = tmp_path_factory.mktemp('march_raygrad') / 'march.s'
-    subprocess.run([HIPCC] + FLAGS + [os.path.join(REPO, 'directvoxgo_amd', 'csrc', 'march.hip'), '-o', str(out)], check=True,
+    assert 'march_raygrad.hip' in SOURCES and 'xyz_corners.h' in HEADERS
+    out = tmp_path_factory.mktemp('march_raygrad') / 'march_raygrad.s'
+    subprocess.run([HIPCC] + FLAGS + [os.path.join(REPO, 'directvoxgo_amd', 'csrc', 'march_raygrad.hip'), '-o', str(out)], check=True,
                    capture_output=True)
     text = out.read_text()
     return text[text.index('amdhsa.kernels:'):]

@@ -1,4 +1,4 @@
-"""Host side of the ray gradient of the marches that return positions (csrc/march_pts_raygrad.hip; no GPU):
+"""Host side of the ray gradient of the marches that return positions (csrc/march_raygrad.hip; no GPU):
 
   boundary      include/dvgo_hip.h declares dvgo_march_ray_bwd_pts and dvgo_march_vm_ray_bwd, _lib types them, the library
                 exports them, and their staged argument checks answer without a device;
@@ -7,8 +7,8 @@
                 each planted mistake is outside it;
   models        raygrad='fused': both attributes, no get_kwargs / state-dict key, load_model; what refine_poses(fused=True)
                 accepts and refuses;
-  resources     the compiler's metadata of every kernel of the new translation unit: no private memory, no spilled register
-                (in the manner of tests/test_hazards_march_raygrad.py).
+  resources     the compiler's metadata of every kernel of the translation unit, march_ray_bwd_kernel's two variants
+                included: no private memory, no spilled register (in the manner of tests/test_hazards_vm_xyz.py).
 """
 import ctypes
 import os
@@ -39,7 +39,7 @@ def lib():
 
 def test_header_declares_both_entries_and_lib_types_them(lib):
     from directvoxgo_amd import _lib, build
-    assert 'march_pts_raygrad.hip' in build.SOURCES and all(h in build.HEADERS for h in ('march_records.h', 'xyz_corners.h', 'vm_common.h'))
+    assert 'march_raygrad.hip' in build.SOURCES and all(h in build.HEADERS for h in ('march_records.h', 'xyz_corners.h', 'vm_common.h'))
     with open(_lib.HEADER_PATH) as f:
         text = f.read()
     decl = _lib.declarations(text)
@@ -353,8 +353,8 @@ def test_kernels_of_the_unit_use_no_private_memory_and_spill_nothing(tmp_path):
     """one metadata entry per kernel: from its `.agpr_count` (the first key of an entry) to the next one's"""
     from directvoxgo_amd.build import FLAGS as BUILD_FLAGS
     flags = [f for f in BUILD_FLAGS if f not in ('-shared', '-Wall', '-Wno-unused-function')] + ['-S', '--cuda-device-only']
-    out = tmp_path / 'march_pts_raygrad.s'
-    subprocess.run([HIPCC] + flags + [os.path.join(REPO, 'directvoxgo_amd', 'csrc', 'march_pts_raygrad.hip'), '-o', str(out)],
+    out = tmp_path / 'march_raygrad.s'
+    subprocess.run([HIPCC] + flags + [os.path.join(REPO, 'directvoxgo_amd', 'csrc', 'march_raygrad.hip'), '-o', str(out)],
                    check=True, capture_output=True)
     text = out.read_text()
     entries = text[text.index('amdhsa.kernels:'):].split('  - .agpr_count:')[1:]
@@ -364,7 +364,10 @@ def test_kernels_of_the_unit_use_no_private_memory_and_spill_nothing(tmp_path):
         assert len(name) == 1, name
         found[name[0]] = tuple(int(re.search(rf'\.{k}:\s*(\d+)', e).group(1))
                                for k in ('private_segment_fixed_size', 'vgpr_spill_count', 'sgpr_spill_count'))
-    assert len(found) == 3 and sum('march_vm_ray_bwd_kernel' in n for n in found) == 2, sorted(found)
-    assert any('march_pts_ray_bwd_kernel' in n for n in found)
-    assert any('ILi4E' in n for n in found) and any('ILi1E' in n for n in found)
+    # the unit's three kernels, five with their dispatch variants (march_ray_bwd_kernel moved here from march.hip)
+    assert len(found) == 5, sorted(found)
+    for kernel in ('march_ray_bwd_kernel', 'march_vm_ray_bwd_kernel'):
+        for vec in ('ILi4E', 'ILi1E'):
+            assert sum(kernel + vec in n for n in found) == 1, (kernel, vec, sorted(found))
+    assert sum('march_pts_ray_bwd_kernel' in n for n in found) == 1, sorted(found)
     assert all(v == (0, 0, 0) for v in found.values()), found

@@ -1,5 +1,5 @@
 """What a camera-pose iteration costs on the fused march for HashVoxGO, VMTriPlaneVoxGO and TensoRFVoxGO (raygrad='fused':
-csrc/march_pts_raygrad.hip, dvgo_march_ray_bwd_pts / dvgo_march_vm_ray_bwd) beside the same iteration op by op
+csrc/march_raygrad.hip, dvgo_march_ray_bwd_pts / dvgo_march_vm_ray_bwd) beside the same iteration op by op
 (DirectVoxGO._forward_raygrad), at the sizes of tools/hash_raygrad_bench.py --pose and tools/vm_raygrad_bench.py --pose:
 scenes.synthetic_scene at 160^3, --rays random pixels of 24 views of 128 x 128; the hash table L = 16, F = 2; planes and lines
 R = 16 following the grid; TensoRFVoxGO(fused_march=True) on a density of separable bumps.
